@@ -17,12 +17,13 @@ into CSR.  For N > 1 one invocation measures the decompositions, each over W war
   rows       output rows sharded over the ranks, operands replicated, no exchange (SURVEY.md 8e's fallback for products whose
              exchange dominates).
 All of them stay under "decompositions"; "fabric" says which backend, world size and devices the ranks saw.
-Every run ends with an untimed whole-result check (1^T C 1 = (1^T A)(B 1)).  At N = 1: the CPU reference is timed on a
-k-slab of the same matrix and the GPU's result for that slab is compared with it (indices exact, values <= 1e-6
-relative); a plain copy is timed on the library's stream first (roofline.peak_measured: both fractions, of the data
-sheet's 8 TB/s and of that copy); the default run adds five secondary workloads (extra_workloads), two of them --
-the web-Google shape and the uniform R-MAT-22 -- with the CPU reference run IN FULL beside them and the whole GPU
-result compared with it.  Rank 0 prints ONE JSON line.
+Every run at N > 1 ends with an untimed whole-result check (1^T C 1 = (1^T A)(B 1)).  At N = 1 a plain run does only what
+its headline needs: operands, warm-up, the K timed steps, --dump-outputs if given, the line.  With --full it also runs the
+whole-result check and times a plain copy on the library's stream first (roofline.peak_measured: both fractions, of the
+data sheet's 8 TB/s and of that copy); the CPU reference is timed on a k-slab of the same matrix and the GPU's result for
+that slab is compared with it (indices exact, values <= 1e-6 relative); the default workload adds five secondary
+workloads (extra_workloads), two of them -- the web-Google shape and the uniform R-MAT-22 -- with the CPU reference run
+IN FULL beside them and the whole GPU result compared with it.  Rank 0 prints ONE JSON line.
 """
 import argparse
 import json
@@ -51,6 +52,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: measure and check everything beside the headline too -- copy probe, whole-result check, per-kernel "
+                         "roofline, CPU reference and parity (--cpu-baseline), ingest (--ingest), cost model, secondary workloads "
+                         "(--extras); off: only the K timed steps and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: write a fixed, seeded sample of the last timed step's result C to DIR/*.npy (OutputSample)")
     ap.add_argument("--scale", type=int, default=22)
     ap.add_argument("--edge-factor", type=int, default=16)
     ap.add_argument("--rmat", default="mild",
@@ -65,7 +72,7 @@ def parse():
     ap.add_argument("--no-transpose-b", action="store_true",
                     help="with --a-mtx: multiply A * B; default A * B^T, as the reference CLI does (SimSpGEMM.cpp:852-856)")
     ap.add_argument("--ingest", type=int, default=1,
-                    help="N=1: report the ingest beside the product -- host parse of the .mtx text (a bounded sample file for "
+                    help="with --full, N=1: report the ingest beside the product -- host parse of the .mtx text (a bounded sample file for "
                          "synthetic workloads) and COO -> CSC/CSR on the device, next to the reference's Read Matrix / COO2CSR timers")
     ap.add_argument("--ingest-sample", type=int, default=4_000_000, help="entries of the sample file the parsers are timed on")
     ap.add_argument("--seed", type=int, default=1)
@@ -73,11 +80,13 @@ def parse():
     ap.add_argument("--partial-capacity", type=int, default=0)
     ap.add_argument("--algorithm", default="outer", choices=["outer", "rowwise"],
                     help="outer (default, the metric's algorithm) or the row-wise variant for rows that fit one merge tile")
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU reference on a k-slab (rank 0, N=1) and check the GPU against it")
+    ap.add_argument("--cpu-baseline", type=int, default=1,
+                    help="with --full: time the CPU reference on a k-slab (rank 0, N=1) and check the GPU against it")
     ap.add_argument("--cpu-partials", type=float, default=2.5e8, help="partial products in the CPU sample slab")
     ap.add_argument("--extras", type=int, default=1,
-                    help="N=1, default workload only: also measure three secondary workloads (3 steps each) and report them "
-                         "under 'extra_workloads': Graph500 parameters at scale 20 (streamed), uniform R-MAT-22, the web-Google shape")
+                    help="with --full, N=1, default workload only: also measure five secondary workloads (2-5 steps each) and "
+                         "report them under 'extra_workloads': Graph500 parameters at scales 22 and 20 (streamed), uniform "
+                         "R-MAT-22, the cage15 shape, the web-Google shape")
     ap.add_argument("--stream-output", action="store_true",
                     help="single GPU: hand every finished row panel to a consumer (checksum) and drop it; C is never resident")
     ap.add_argument("--shard", default="both", choices=["both", "k", "rows"],
@@ -95,7 +104,12 @@ def parse():
                          "reports it under decompositions.k_library; the other ranks wait")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = rehearsal only: exchange staged through host memory, ranks may share a GPU")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus != 1 or args.force_dist):
+        ap.error("--dump-outputs samples the product of one GPU: use it with --gpus 1 and without --force-dist")
+    return args
 
 
 # ---- launching N ranks from a plain `python bench.py --gpus N` ------------------------------------------------------------
@@ -578,27 +592,89 @@ def make_step(ctx, n, csr, csc, np_dtype, tdtype, device, partial_capacity, stre
     if stream_output:
         # C never resident: every finished row panel is checksummed on the device and dropped (the way to run
         # products whose result does not fit, e.g. Graph500 parameters at scale 22)
-        def step(checksum=False):
+        def step(checksum=False, sample=None):
             acc = {"sum": 0.0, "nnz": 0}
 
             def on_panel(p):
                 acc["nnz"] += p["nnz"]
                 if checksum and p["nnz"]:
                     acc["sum"] += float(_as_tensor(p["vals"], p["nnz"], vt, device, tdtype).sum(dtype=torch.float64))
+                if sample is not None:
+                    sample.add(p["rowptr"], p["colidx"], p["vals"], p["row_begin"], p["row_end"], p["nnz"])
             info = ctx.spgemm_csc_csr_panels(np_dtype, n, n, n, ptrs, on_panel, partial_capacity=partial_capacity)
             assert acc["nnz"] == info["nnz_c"]
             info["val_sum_global"] = acc["sum"]
             return info
     else:
-        def step(checksum=False):
+        def step(checksum=False, keep=False):
             res = ctx.spgemm_csc_csr_device(np_dtype, n, n, n, ptrs, validate=False, partial_capacity=partial_capacity)
             info = res.info
             if checksum:
                 _, _, va = res.device_ptrs()
                 info["val_sum_global"] = float(_as_tensor(va, res.nnz, vt, device, tdtype).sum(dtype=torch.float64))
-            res.close()
+            if keep:
+                info["result"] = res   # the caller closes it
+            else:
+                res.close()
             return info
     return step, ptrs
+
+
+DUMP_ROWS = 1 << 20   # rows of C in the --dump-outputs sample: 4 arrays of at most 8 bytes per row, <= 32 MiB in all
+
+
+class OutputSample:
+    """--dump-outputs: the result C = A*B a caller of the timed path receives (CSR), reduced to a fixed, seeded sample that
+    two builds can compare array for array.  R = min(M, 2^20) rows, one drawn from each of R equal strata of the M rows,
+    each with its entry count and ONE of its entries at a seeded position (column, value; -1 and 0 for an empty row), and
+    [M, N, nnz(C), sum of all values].  Fed panel by panel (a streamed product) or once with the whole result."""
+
+    def __init__(self, M, N, np_dtype, device):
+        import torch
+        R = min(M, DUMP_ROWS)
+        g = torch.Generator().manual_seed(20260101)
+        self.rows = ((torch.arange(R, dtype=torch.float64) + torch.rand(R, generator=g, dtype=torch.float64)) * (M / R)).long().clamp_(max=M - 1)
+        self.pick = torch.rand(R, generator=g, dtype=torch.float64)   # where in its row the sampled entry lies, [0, 1)
+        self.M, self.N, self.np_dtype, self.device = M, N, np_dtype, device
+        self.row_nnz = np.zeros(R, np.float64)
+        self.cols = np.full(R, -1.0)
+        self.vals = np.zeros(R, np_dtype)
+        self.nnz, self.val_sum = 0, 0.0
+
+    def add(self, rowptr, colidx, vals, row_begin, row_end, nnz):
+        """One piece of C: output rows [row_begin, row_end), device addresses of its CSR arrays (rowptr relative to the piece)."""
+        import torch
+        from outerspace_amd.distributed import _as_tensor
+        dev = self.device
+        vt, tdt = ("<f8", torch.float64) if np.dtype(self.np_dtype) == np.float64 else ("<f4", torch.float32)
+        self.nnz += int(nnz)
+        if nnz:
+            self.val_sum += float(_as_tensor(vals, nnz, vt, dev, tdt).sum(dtype=torch.float64))
+        i0, i1 = (int(x) for x in torch.searchsorted(self.rows, torch.tensor([row_begin, row_end])))
+        if i1 == i0:
+            return
+        rp = _as_tensor(rowptr, row_end - row_begin + 1, "<i8", dev, torch.int64)
+        r = (self.rows[i0:i1] - row_begin).to(dev)
+        lo = rp[r]
+        cnt = rp[r + 1] - lo
+        self.row_nnz[i0:i1] = cnt.cpu().numpy()
+        if not nnz:
+            return
+        off = torch.minimum((self.pick[i0:i1].to(dev) * cnt).long(), (cnt - 1).clamp_min(0))
+        pos = torch.where(cnt > 0, lo + off, torch.zeros_like(lo))   # inside [0, nnz): an empty row reads entry 0, masked below
+        c = _as_tensor(colidx, nnz, "<i4", dev, torch.int32)[pos]
+        v = _as_tensor(vals, nnz, vt, dev, tdt)[pos]
+        self.cols[i0:i1] = torch.where(cnt > 0, c.long(), -1).cpu().numpy()
+        self.vals[i0:i1] = torch.where(cnt > 0, v, torch.zeros_like(v)).cpu().numpy()
+
+    def save(self, out_dir):
+        os.makedirs(out_dir, exist_ok=True)
+        arrays = {"C_sample_rows": self.rows.numpy().astype(np.float64), "C_sample_row_nnz": self.row_nnz,
+                  "C_sample_cols": self.cols, "C_sample_vals": self.vals,
+                  "C_summary": np.array([self.M, self.N, self.nnz, self.val_sum], np.float64)}
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+        return sorted(arrays)
 
 
 def library_id():
@@ -738,14 +814,18 @@ def kernel_roofline(infos, n, E, serial=None):
             "ms_per_launch": kernels[dom]["ms_per_launch"], "kernels": kernels}
 
 
-def timed(step, steps, warmup, sync, barrier=None, reduce_max=None):
+def timed(step, steps, warmup, sync, barrier=None, reduce_max=None, keep_last=False):
+    """keep_last: the last timed step keeps its result (info["result"]) for the caller, who closes it."""
     for _ in range(warmup):
         step()
     sync()
     if barrier:
         barrier()
     t0 = time.perf_counter()
-    infos = [step() for _ in range(steps)]
+    if keep_last:
+        infos = [step() for _ in range(steps - 1)] + [step(keep=True)]
+    else:
+        infos = [step() for _ in range(steps)]
     sync()
     if barrier:
         barrier()
@@ -944,7 +1024,7 @@ def main():
                          f"duplicates removed, self-product C=A*A, CSC x CSR -> CSR")
     nnz_a = int(csr[0][-1])
     note(f"operands on the device: n = {n}, nnz = {nnz_a}")
-    want_sum = expected_value_sum(n, csr, csc, device)
+    want_sum = expected_value_sum(n, csr, csc, device) if use_dist or args.full else None
     torch.cuda.synchronize()
     ctx = S.Context(dev_index)
     ctx.algorithm = args.algorithm
@@ -960,20 +1040,31 @@ def main():
 
     if not use_dist:
         # ================================================= one GPU =================================================
-        # what a plain copy reaches on this box, in this run (the pool's 4 GiB go back before the product sizes its buffers)
-        copy_gbps = ctx.stream_copy_gbps()
-        ctx.trim()
-        note(f"stream copy: {copy_gbps:.0f} GB/s (read + written)")
+        copy_gbps = None
+        if args.full:
+            # what a plain copy reaches on this box, in this run (the pool's 4 GiB go back before the product sizes its buffers)
+            copy_gbps = ctx.stream_copy_gbps()
+            ctx.trim()
+            note(f"stream copy: {copy_gbps:.0f} GB/s (read + written)")
         step, ptrs = make_step(ctx, n, csr, csc, np_dtype, tdtype, device, args.partial_capacity, args.stream_output)
-        dt, infos = timed(step, args.steps, args.warmup, torch.cuda.synchronize)
+        dt, infos = timed(step, args.steps, args.warmup, torch.cuda.synchronize,
+                          keep_last=bool(args.dump_outputs) and not args.stream_output)
         info = infos[-1]
         note(f"{args.steps} timed steps: {dt / args.steps * 1e3:.1f} ms per step")
-        chk = check_sum(step(checksum=True)["val_sum_global"], want_sum, args.dtype, "single GPU")
-        note("whole-result check passed")
+        if args.dump_outputs:
+            sample = OutputSample(n, n, np_dtype, device)
+            if args.stream_output:
+                # a streamed product hands every panel over once and drops it: the sample is taken from one more product of
+                # the same operands (the library's products are deterministic)
+                step(sample=sample)
+            else:
+                res = info.pop("result")
+                ctx.trim()   # the pool holds the product's staging memory: torch needs room for the sample (the result stays)
+                sample.add(*res.device_ptrs(), 0, n, res.nnz)
+                res.close()
+            note(f"outputs written to {args.dump_outputs}: {', '.join(sample.save(args.dump_outputs))}")
         nnz_c, P = info["nnz_c"], info["partials"]
         ms_step = dt / args.steps * 1e3
-        serial = serial_steps(step, infos)
-        roof = add_measured_peak(kernel_roofline(infos, n, E, serial), copy_gbps)
         alg_total = 2 * E * P + E * (2 * nnz_a + nnz_c) + 8 * (3 * n + 3)   # whole product
         out.update({
             "value": nnz_c / (ms_step * 1e-3), "ms_per_step": ms_step,
@@ -981,12 +1072,10 @@ def main():
                        "parallelism": "single GPU, output streamed panel by panel (never resident)" if args.stream_output else "single GPU"},
             "gflops": 2 * P / (ms_step * 1e-3) / 1e9, "partials_per_s": P / (ms_step * 1e-3),
             "whole_product": {"algorithmic_bytes": alg_total, "GBps": alg_total / (ms_step * 1e-3) / 1e9,
-                              "frac_of_peak": alg_total / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                              "frac_of_measured": alg_total / (ms_step * 1e-3) / 1e9 / copy_gbps},
+                              "frac_of_peak": alg_total / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
             "library_id": library_id(),
             "phases_ms": {k: float(np.mean([i[k] for i in infos])) for k in ("ms_symbolic", "ms_multiply", "ms_merge", "ms_compact", "ms_total")},
             "panels": info["panels"], "plans_beside_the_previous_multiply": info["plans_overlapped"],
-            "ms_per_step_plans_in_line": float(np.mean([i["ms_total"] for i in serial])) if serial else None,
             "long_rows": info["heavy_rows"], "long_row_partials": info["heavy_partials"],
             # long rows the multiply wrote straight into their column ranges (no split pass), and the ones split afterwards
             "long_rows_direct": info["direct_rows"], "long_row_partials_direct": info["direct_partials"],
@@ -998,17 +1087,23 @@ def main():
             "long_rows_hub": info["hub_rows"], "long_row_partials_hub": info["hub_partials"], "hub_cells": info["hub_cells"],
             "long_row_partials_split_by_one_workgroup": info["split_partials"],
             "segments_global_sorted": info["sorted_segments"], "segment_partials_global_sorted": info["sorted_partials"],
-            "roofline": roof,
             # per-step device times (ms): how much the numbers above move from one product to the next
             "steps_ms": {"total": [round(i["ms_total"], 2) for i in infos],
                          "multiply_kernel": [round(i["ms_multiply_kernel"], 2) for i in infos],
                          "merge_kernel": [round(i["ms_merge_kernel"], 2) for i in infos],
                          "split_row_kernel": [round(i["ms_split_kernel"], 2) for i in infos],
                          "direct_plan_kernel": [round(i["ms_direct_plan_kernel"], 2) for i in infos]},
-            "result_check": chk,
         })
         status = 0
-        if args.cpu_baseline:
+        if args.full:
+            chk = check_sum(step(checksum=True)["val_sum_global"], want_sum, args.dtype, "single GPU")
+            note("whole-result check passed")
+            serial = serial_steps(step, infos)
+            roof = add_measured_peak(kernel_roofline(infos, n, E, serial), copy_gbps)
+            out["whole_product"]["frac_of_measured"] = alg_total / (ms_step * 1e-3) / 1e9 / copy_gbps
+            out.update({"ms_per_step_plans_in_line": float(np.mean([i["ms_total"] for i in serial])) if serial else None,
+                        "roofline": roof, "result_check": chk})
+        if args.full and args.cpu_baseline:
             out["cpu_baseline"], out["slab_parity"] = cpu_baseline(ctx, csc, csr, n, args.cpu_partials, np_dtype, ptrs)
             note(f"CPU baseline {out['cpu_baseline']['value'] / 1e6:.1f} M nnz/s; slab parity: {out['slab_parity']['status']}")
             out["speedup_vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]
@@ -1028,34 +1123,35 @@ def main():
                 if out["row_slab_parity"]["status"] != "ok":
                     status = 3
                 ctx.trim()
-        if args.ingest and not args.stream_output:
+        if args.full and args.ingest and not args.stream_output:
             note("ingest: device COO -> CSC/CSR of the full operands, host parse")
             out["ingest"] = ingest_report(ctx, n, csr, csc, np_dtype, device, args, ingest, bool(args.cpu_baseline))
             note(f"ingest: device {out['ingest']['device_coo_to_compressed']['ms']:.1f} ms, host parse "
                  f"{out['ingest']['host_parse'][0]['M_entries_per_s']:.1f} M entries/s")
-        # the reference's own closed-form prediction for this input (SimOuterSPACE.cpp:176-238), beside the
-        # measurement: simulated cycles of a 256-PE OuterSPACE at 85 B/cycle of DRAM, and the DRAM bytes it prices
-        from outerspace_amd import cost_model
-        torch.cuda.synchronize()
-        ctx.trim()   # the library's pool may hold every free byte of the device: torch needs a few hundred MB for this
-        pred = cost_model.analytical(csc[0], csc[1], csr[0], value_size=np.dtype(np_dtype).itemsize)
-        note("cost model evaluated")
-        pred["note"] = ("OuterSPACE analytical model restated from the reference (not a measurement): cycles of the "
-                        "simulated accelerator, 64-B-aligned DRAM bytes per task")
-        out["cost_model"] = pred
-        # HBM bytes per launch of the dominant kernel from the PMC counters: they cannot be collected from inside
-        # this process (rocprofv3 --pmc wraps it, separate passes), so the figure recorded for exactly this
-        # workload under profiles/ is attached when there is one; otherwise null
-        t = recorded_traffic(workload_name, args.dtype, roof["kernel"])
-        if t:
-            roof["traffic"], roof["traffic_source"], roof["traffic_library_id"] = t
-            # a recorded figure, not a property of this run: stale when the kernels have changed since the PMC passes
-            # (the same binary, or a build of the same sources: either hash matching means the counters belong to these kernels)
-            rec_id, cur_id = roof["traffic_library_id"] or {}, out["library_id"]
-            roof["traffic_stale"] = not any(rec_id.get(k) is not None and rec_id.get(k) == cur_id.get(k) for k in ("kernel_source_sha16", "so_sha16"))
+        if args.full:
+            # the reference's own closed-form prediction for this input (SimOuterSPACE.cpp:176-238), beside the
+            # measurement: simulated cycles of a 256-PE OuterSPACE at 85 B/cycle of DRAM, and the DRAM bytes it prices
+            from outerspace_amd import cost_model
+            torch.cuda.synchronize()
+            ctx.trim()   # the library's pool may hold every free byte of the device: torch needs a few hundred MB for this
+            pred = cost_model.analytical(csc[0], csc[1], csr[0], value_size=np.dtype(np_dtype).itemsize)
+            note("cost model evaluated")
+            pred["note"] = ("OuterSPACE analytical model restated from the reference (not a measurement): cycles of the "
+                            "simulated accelerator, 64-B-aligned DRAM bytes per task")
+            out["cost_model"] = pred
+            # HBM bytes per launch of the dominant kernel from the PMC counters: they cannot be collected from inside
+            # this process (rocprofv3 --pmc wraps it, separate passes), so the figure recorded for exactly this
+            # workload under profiles/ is attached when there is one; otherwise null
+            t = recorded_traffic(workload_name, args.dtype, roof["kernel"])
+            if t:
+                roof["traffic"], roof["traffic_source"], roof["traffic_library_id"] = t
+                # a recorded figure, not a property of this run: stale when the kernels have changed since the PMC passes
+                # (the same binary, or a build of the same sources: either hash matching means the counters belong to these kernels)
+                rec_id, cur_id = roof["traffic_library_id"] or {}, out["library_id"]
+                roof["traffic_stale"] = not any(rec_id.get(k) is not None and rec_id.get(k) == cur_id.get(k) for k in ("kernel_source_sha16", "so_sha16"))
         default_workload = (args.workload == "rmat" and args.rmat == "mild" and args.scale == 22 and not args.stream_output
                             and args.partial_capacity == 0 and a_mtx is None)
-        if args.extras and default_workload and status == 0:
+        if args.full and args.extras and default_workload and status == 0:
             # driver-observed numbers for the workloads the headline does not cover (3 steps each, same checks)
             del csr, csc, step, ptrs
             ctx.trim()

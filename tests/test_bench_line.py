@@ -1,5 +1,5 @@
-"""The bench line the driver reads (bench.py's contract), checked on the line committed under profiles/: the keys the contract
-names, and the arithmetic between them.  CPU-only: it reads a JSON file."""
+"""The bench line the driver reads (bench.py's contract), checked on the `bench.py --full` line committed under profiles/: the
+keys the contract names, and the arithmetic between them.  CPU-only: it reads a JSON file."""
 import glob
 import json
 import os
