@@ -20,6 +20,8 @@
  *   assert(csc.pos.size()==csr.pos.size())  SimSpGEMM.cpp:267,882  OSP_ERR_DIM
  *   main(argv[1]=A.mtx, argv[2]=B.mtx)      SimSpGEMM.cpp:819-894  osp_spgemm_mtx / outerspace_amd/osp_spgemm
  *   x = relu(fc(x)) between two layers      NN_models/models.py:17-31  osp_csr_bias_relu (+ osp_result_coo_rows: the next product's operand)
+ *   Unfold -> swapaxes -> reshape (conv)    NN_models/get_mtx_files.py:98-133  osp_im2col_csc, osp_spgemm_conv2d
+ *   MaxPool2d(2) between two conv layers    NN_models/models.py:35-84  osp_csr_maxpool2d
  *   (nothing: one process, one thread)      SURVEY.md 8e          osp_multi_* -- the k-sharded product over the GPUs of a node
  *
  * Conventions: plain pointers and sizes only; no exceptions cross the ABI; every function
@@ -42,11 +44,13 @@
 extern "C" {
 #endif
 
-#define OSP_VERSION 5   /* round of the build: 3 = osp_multi_*, osp_csr_bias_relu, osp_result_coo_rows, direct-row counters;
+#define OSP_VERSION 6   /* round of the build: 3 = osp_multi_*, osp_csr_bias_relu, osp_result_coo_rows, direct-row counters;
                             4 = per-destination exchange streams (osp_multi_rank_info_t grew);
                             5 = osp_result_info_t grew (gathered_*, expand_*): since this version the two reference functions
                                 of osp_spgemm_csc_csr are ONE kernel for most rows -- the merge forms the partial products
-                                cscMulcsr would stage (same products, same order, same bits) */
+                                cscMulcsr would stage (same products, same order, same bits);
+                            6 = osp_conv2d_geometry_t, osp_im2col_csc, osp_spgemm_conv2d, osp_csr_maxpool2d (no existing
+                                struct changed) */
 
 typedef enum osp_status {
     OSP_OK = 0,
@@ -88,6 +92,17 @@ typedef struct osp_config {
     int algorithm;              /* osp_algorithm_t (0 = outer product) */
     int reserved[5];
 } osp_config_t;
+
+/* Geometry of a 2-D convolution (torch.nn.Conv2d / torch.nn.Unfold with zero padding).  Every field but `reserved`
+ * must be >= 1 except the paddings; `reserved` must be zero.  Output size per axis:
+ * OH = (H + 2*pad_h - dil_h*(kh - 1) - 1) / stride_h + 1 (floor), likewise OW. */
+typedef struct osp_conv2d_geometry {
+    uint32_t kh, kw;
+    uint32_t stride_h, stride_w;
+    uint32_t pad_h, pad_w;
+    uint32_t dil_h, dil_w;
+    uint32_t reserved[8];
+} osp_conv2d_geometry_t;
 
 /* What one multiply did.  Times are device milliseconds measured with HIP events on the
  * context's stream. */
@@ -341,6 +356,48 @@ int osp_csr_bias_relu(osp_result_t in, const void *bias, osp_memspace_t bias_spa
 /* The row index of every entry of a CSR result (nnz_c values, DEVICE memory of the caller): with the result's colidx /
  * vals arrays that is the COO form osp_spgemm_coo takes, so an activation feeds the next product without leaving the GPU. */
 int osp_result_coo_rows(osp_result_t r, uint32_t *rows_device);
+
+/* ---- between the layers of a sparse LeNet (NN_models/models.py:35-84) -------------------- */
+/*
+ * Activations of the conv stage are "pixel x channel" matrices: row n*H*W + y*W + x, column c (NHWC -- the layout a
+ * product's result already has).  The input x of N images, C channels, H x W pixels comes as COO (x_rows = pixel, x_cols
+ * = channel, any order, no duplicates) in `space`.
+ *
+ * im2col of x into the unfold matrix A in CSC, zero padding: A is (N*OH*OW) x (C*kh*kw), row n*OH*OW + oy*OW + ox, column
+ * c*kh*kw + ky*kw + kx -- exactly what get_mtx_files.py:98-133 writes (Unfold -> swapaxes(1, 2) -> reshape(-1, C*kh*kw)),
+ * with the zeros dropped.  Only x is sorted (by channel, on the device); every column of A comes out with ascending rows
+ * by construction.  Values are copied, so they equal torch.nn.Unfold's bit for bit.
+ * Two calls: with a_colptr, a_rowidx and a_vals all NULL only *nnz_a is reported; then the caller passes DEVICE buffers
+ * of C*kh*kw + 1, nnz_a and nnz_a entries and they are filled (*nnz_a again).  OSP_ERR_ARG: a zero size, a bad geometry
+ * or an empty output; OSP_ERR_RANGE: N*OH*OW, N*H*W or C*kh*kw does not fit the u32 index type, or an index of x lies
+ * outside its dimension (always checked: the channel grouping needs it; `validate` is accepted for symmetry);
+ * OSP_ERR_DUPLICATE: a coordinate of x given twice.
+ */
+int osp_im2col_csc(osp_context_t ctx, osp_dtype_t dtype, uint64_t N, uint64_t C, uint64_t H, uint64_t W, uint64_t nnz_x,
+                   const uint32_t *x_rows, const uint32_t *x_cols, const void *x_vals, osp_memspace_t space,
+                   const osp_conv2d_geometry_t *geom, int validate, uint64_t *nnz_a, int64_t *a_colptr, uint32_t *a_rowidx,
+                   void *a_vals);
+/*
+ * A conv layer as the CLI's product act * W^T (get_mtx_files.py:98-133): A = im2col(x) as above, W the OC x (C*kh*kw)
+ * weight (conv.weight.reshape(OC, -1)) in COO, B = W^T in CSR built on the device as osp_spgemm_coo builds it; then the
+ * product of osp_spgemm_csc_csr on the device arrays (internal buffers from the context's pool).  The result is the CSR
+ * (N*OH*OW) x OC, NHWC -- the conv bias is a per-column bias, so osp_csr_bias_relu finishes the layer.  Bit-identical to
+ * osp_spgemm_coo on the unfold matrix and W (same operands, same product: no summation of its own).  cfg as for
+ * osp_spgemm_coo (validate checks the weight's ranges; the algorithm and the panel capacity apply to the product).
+ * info.ms_ingest holds the device time of im2col and of the weight's conversion.
+ */
+int osp_spgemm_conv2d(osp_context_t ctx, osp_dtype_t dtype, uint64_t N, uint64_t C, uint64_t H, uint64_t W, uint64_t nnz_x,
+                      const uint32_t *x_rows, const uint32_t *x_cols, const void *x_vals, uint64_t OC, uint64_t nnz_w,
+                      const uint32_t *w_rows, const uint32_t *w_cols, const void *w_vals, osp_memspace_t space,
+                      const osp_conv2d_geometry_t *geom, const osp_config_t *cfg, osp_result_t *result);
+/*
+ * MaxPool2d(kernel (kh, kw), stride (stride_h, stride_w)) of a CSR activation `in` of N*H*W rows (pixel x channel): out
+ * is (N*PH*PW) x C with PH = (H - kh) / stride_h + 1 (no padding, no dilation, floor mode), every entry the max over its
+ * window with an absent entry counting as 0 -- F.max_pool2d on the densified input -- and the zeros dropped.  Same
+ * contract as osp_csr_bias_relu: `in` stays valid, row pointers are exact, columns ascend.
+ */
+int osp_csr_maxpool2d(osp_result_t in, uint64_t N, uint64_t H, uint64_t W, uint32_t kh, uint32_t kw, uint32_t stride_h,
+                      uint32_t stride_w, osp_result_t *out);
 
 /* ---- measurement aid: what a plain stream reaches on this device ------------------------------------------------------ */
 /* A 16-bytes-per-lane copy of `bytes` bytes, `reps` times on the context's stream; *gbps = (read + written) / time in GB/s.

@@ -64,6 +64,13 @@ class Panel(C.Structure):
                 ("index", C.c_uint32), ("count", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class Conv2dGeometry(C.Structure):
+    """osp_conv2d_geometry_t"""
+    _fields_ = [("kh", C.c_uint32), ("kw", C.c_uint32), ("stride_h", C.c_uint32), ("stride_w", C.c_uint32),
+                ("pad_h", C.c_uint32), ("pad_w", C.c_uint32), ("dil_h", C.c_uint32), ("dil_w", C.c_uint32),
+                ("reserved", C.c_uint32 * 8)]
+
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -100,7 +107,7 @@ EXPORTS = [
     "osp_merge_csr_parts", "osp_result_info", "osp_result_copy_csr", "osp_result_device_ptrs",
     "osp_result_destroy", "osp_mtx_read", "osp_host_free", "osp_coo_to_compressed_f32",
     "osp_coo_to_compressed_f64", "osp_spgemm_mtx", "osp_result_write_mtx", "osp_csr_bias_relu", "osp_result_coo_rows",
-    "osp_stream_copy_probe",
+    "osp_stream_copy_probe", "osp_im2col_csc", "osp_spgemm_conv2d", "osp_csr_maxpool2d",
     "osp_multi_context_create", "osp_multi_context_destroy", "osp_multi_operands_create", "osp_multi_operands_destroy", "osp_spgemm_multi",
     "osp_spgemm_csc_csr_multi", "osp_multi_result_info", "osp_multi_result_shard", "osp_multi_result_copy_csr", "osp_multi_result_destroy",
 ]
@@ -175,6 +182,12 @@ def lib():
     L.osp_multi_result_destroy.argtypes = [vp]
     L.osp_csr_bias_relu.argtypes = [vp, vp, i32, i32, C.POINTER(vp)]
     L.osp_result_coo_rows.argtypes = [vp, vp]
+    L.osp_im2col_csc.argtypes = [vp, i32, u64, u64, u64, u64, u64, vp, vp, vp, i32, C.POINTER(Conv2dGeometry), i32, C.POINTER(u64),
+                                 vp, vp, vp]
+    L.osp_spgemm_conv2d.argtypes = [vp, i32, u64, u64, u64, u64, u64, vp, vp, vp, u64, u64, vp, vp, vp, i32, C.POINTER(Conv2dGeometry),
+                                    C.POINTER(Config), C.POINTER(vp)]
+    u32 = C.c_uint32
+    L.osp_csr_maxpool2d.argtypes = [vp, u64, u64, u64, u32, u32, u32, u32, C.POINTER(vp)]
     _lib = L
     return L
 

@@ -24,6 +24,7 @@
 #include "osp_split.h"
 #include "osp_sort.h"
 #include "osp_epilogue.h"
+#include "osp_conv.h"
 
 namespace osp {
 
@@ -614,6 +615,134 @@ static void bias_relu_impl(Context *ctx, const Result *in, Result *res, const T 
     res->info.ms_total = ev.ms();
 }
 
+// ---- the conv stage of a sparse LeNet (osp_conv.h) ----
+// The checks every conv entry point shares: the output size per axis, and every index of A and of the input within u32.
+static ConvGeom conv_geometry(uint64_t N, uint64_t C, uint64_t H, uint64_t W, const osp_conv2d_geometry_t *geom) {
+    if (!geom) throw Error(OSP_ERR_ARG, "null geometry");
+    for (uint32_t r : geom->reserved)
+        if (r) throw Error(OSP_ERR_ARG, "geometry: reserved fields must be zero");
+    if (!N || !C || !H || !W) throw Error(OSP_ERR_ARG, "N, C, H and W must be >= 1");
+    if (!geom->kh || !geom->kw || !geom->stride_h || !geom->stride_w || !geom->dil_h || !geom->dil_w)
+        throw Error(OSP_ERR_ARG, "geometry: kernel, stride and dilation must be >= 1");
+    const uint64_t lim = 0xffffffffull;
+    if (C >= lim || H >= lim || W >= lim || (unsigned __int128)N * H * W >= lim)
+        throw Error(OSP_ERR_RANGE, "N*H*W or C does not fit the u32 index type");
+    const uint64_t eh = (uint64_t)geom->dil_h * (geom->kh - 1) + 1, ew = (uint64_t)geom->dil_w * (geom->kw - 1) + 1;
+    const uint64_t hp = H + 2ull * geom->pad_h, wp = W + 2ull * geom->pad_w;
+    if (hp < eh || wp < ew) throw Error(OSP_ERR_ARG, "geometry: the (dilated) kernel is larger than the padded input: empty output");
+    const uint64_t OH = (hp - eh) / geom->stride_h + 1, OW = (wp - ew) / geom->stride_w + 1;
+    if ((unsigned __int128)N * OH * OW >= lim) throw Error(OSP_ERR_RANGE, "N*OH*OW does not fit the u32 index type");
+    if ((uint64_t)C * geom->kh * geom->kw >= lim) throw Error(OSP_ERR_RANGE, "C*kh*kw does not fit the u32 index type");
+    return ConvGeom{(uint32_t)H, (uint32_t)W, geom->kh, geom->kw, geom->stride_h, geom->stride_w, geom->pad_h, geom->pad_w,
+                    geom->dil_h, geom->dil_w, (uint32_t)OH, (uint32_t)OW};
+}
+
+// A = im2col(x) in CSC, x as device COO.  Returns nnz(A); with `fill`, writes A to colptr / rowidx / vals (allocated in
+// `sc` when colptr is null on entry).  x is grouped by channel with the COO ingest (this also checks its ranges and
+// duplicates), then units (column k, chunk of channel c) are counted, scanned in column-major order and written.
+template <class T>
+static uint64_t im2col_impl(Context *ctx, Scratch &sc, uint64_t N, uint64_t C, const ConvGeom &g, uint64_t nnz_x, const uint32_t *xr,
+                            const uint32_t *xc, const T *xv, bool fill, int64_t *&colptr, uint32_t *&rowidx, T *&vals) {
+    hipStream_t s = ctx->stream;
+    const uint32_t khkw = g.kh * g.kw;
+    const uint64_t K = C * khkw;
+    int64_t *xptr;
+    uint32_t *xpix;
+    T *xval;
+    coo_to_compressed_device<T>(ctx, sc, C, N * g.H * g.W, nnz_x, xc, xr, xv, "x (COO)", &xptr, &xpix, &xval);
+    // units per channel: a few host words (C + 1), the one round trip of the layout
+    std::vector<int64_t> hp(C + 1);
+    copy_d2h(hp.data(), xptr, (C + 1) * sizeof(int64_t), s);
+    std::vector<uint64_t> ub(C + 1);
+    ub[0] = 0;
+    for (uint64_t c = 0; c < C; c++) ub[c + 1] = ub[c] + (uint64_t)((hp[c + 1] - hp[c] + kConvChunk - 1) / kConvChunk) * khkw;
+    const uint64_t U = ub[C];
+    uint64_t *ubase = sc.get<uint64_t>(C + 1);
+    copy_h2d(ubase, ub.data(), (C + 1) * sizeof(uint64_t), s);
+    uint32_t *cnt = sc.get<uint32_t>(U);
+    uint64_t *off = sc.get<uint64_t>(U + 1);
+    uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(U + 1));
+    const unsigned grid = grid_for(std::max<uint64_t>(U, 1) * kWave, 256);
+    if (U)
+        im2col_units_kernel<T, false><<<grid, 256, 0, s>>>(xptr, xpix, xval, ubase, (uint32_t)C, g, U, cnt, nullptr, nullptr, nullptr);
+    device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{cnt}, U, off, tmp, s);
+    const uint64_t nnz = d2h(off + U, s);
+    if (!fill) return nnz;
+    if (!colptr) {
+        colptr = sc.get<int64_t>(K + 1);
+        rowidx = sc.get<uint32_t>(nnz);
+        vals = sc.get<T>(nnz);
+    } else if (nnz && (!rowidx || !vals)) {
+        throw Error(OSP_ERR_ARG, "null a_rowidx or a_vals for a non-empty A");
+    }
+    im2col_colptr_kernel<<<grid_for(K + 1, 256), 256, 0, s>>>(ubase, off, (uint32_t)C, khkw, U, colptr);
+    if (nnz) im2col_units_kernel<T, true><<<grid, 256, 0, s>>>(xptr, xpix, xval, ubase, (uint32_t)C, g, U, nullptr, off, rowidx, vals);
+    OSP_HIP(hipStreamSynchronize(s));
+    OSP_HIP(hipGetLastError());
+    return nnz;
+}
+
+template <class T>
+static void spgemm_conv2d_impl(Context *ctx, Result *res, uint64_t N, uint64_t C, const ConvGeom &g, uint64_t nnz_x, const uint32_t *x_rows,
+                               const uint32_t *x_cols, const T *x_vals, uint64_t OC, uint64_t nnz_w, const uint32_t *w_rows,
+                               const uint32_t *w_cols, const T *w_vals, osp_memspace_t space, const osp_config_t &cfg) {
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint32_t *xr = to_device(sc, x_rows, nnz_x, space, s), *xc = to_device(sc, x_cols, nnz_x, space, s);
+    const uint32_t *wr = to_device(sc, w_rows, nnz_w, space, s), *wc = to_device(sc, w_cols, nnz_w, space, s);
+    const T *xv = to_device(sc, x_vals, nnz_x, space, s), *wv = to_device(sc, w_vals, nnz_w, space, s);
+    const uint64_t M = N * g.OH * g.OW, K = C * g.kh * g.kw;
+    int64_t *ap = nullptr, *bp;
+    uint32_t *ai = nullptr, *bi;
+    T *av = nullptr, *bv;
+    im2col_impl<T>(ctx, sc, N, C, g, nnz_x, xr, xc, xv, true, ap, ai, av);
+    coo_to_compressed_device<T>(ctx, sc, K, OC, nnz_w, wc, wr, wv, "W (COO)", &bp, &bi, &bv);   // B = W^T in CSR = W in CSC
+    OSP_HIP(hipEventRecord(ev.b, s));
+    osp_config_t c2 = cfg;
+    c2.validate = 0;  // A is well formed by construction; W's ranges and duplicates were just checked
+    res->info.M = M; res->info.K = K; res->info.N = OC;
+    spgemm_impl<T>(ctx, res, M, K, OC, ap, ai, av, bp, bi, bv, OSP_DEVICE, c2);
+    const float ms = ev.ms();
+    res->info.ms_ingest = ms;
+    res->info.ms_total += ms;
+}
+
+// MaxPool2d of a CSR activation, the zeros dropped, as a new CSR (osp_conv.h)
+template <class T>
+static void maxpool_impl(Context *ctx, const Result *in, Result *res, uint64_t N, uint32_t H, uint32_t W, uint32_t kh, uint32_t kw,
+                         uint32_t sh, uint32_t sw) {
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint32_t C = (uint32_t)in->info.N, PH = (H - kh) / sh + 1, PW = (W - kw) / sw + 1;
+    const uint64_t M = N * PH * PW;
+    res->info = in->info;
+    res->info.M = M;
+    res->info.row_begin = 0;
+    res->info.row_end = M;
+    res->rowptr = (int64_t *)ctx->alloc((M + 1) * sizeof(int64_t));
+    uint32_t *cnt = sc.get<uint32_t>(M + 1);
+    uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(M + 1));
+    const unsigned grid = grid_for(std::max<uint64_t>(M, 1) * kWave, 256);
+    csr_maxpool_rows_kernel<T, false><<<grid, 256, 0, s>>>(in->rowptr, in->colidx, (const T *)in->vals, C, H, W, PH, PW, kh, kw, sh, sw, M, cnt,
+                                                           nullptr, nullptr, nullptr);
+    device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{cnt}, M, (uint64_t *)res->rowptr, tmp, s);
+    const uint64_t nnz = (uint64_t)d2h(res->rowptr + M, s);
+    res->colidx = (uint32_t *)ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(uint32_t));
+    res->vals = ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(T));
+    if (nnz)
+        csr_maxpool_rows_kernel<T, true><<<grid, 256, 0, s>>>(in->rowptr, in->colidx, (const T *)in->vals, C, H, W, PH, PW, kh, kw, sh, sw, M,
+                                                              nullptr, res->rowptr, res->colidx, (T *)res->vals);
+    OSP_HIP(hipEventRecord(ev.b, s));
+    OSP_HIP(hipStreamSynchronize(s));
+    OSP_HIP(hipGetLastError());
+    res->info.nnz_c = nnz;
+    res->info.ms_total = ev.ms();
+}
+
 static void destroy_result(Result *r) {
     if (!r) return;
     if (r->ctx) {
@@ -1061,6 +1190,114 @@ int osp_result_coo_rows(osp_result_t r_, uint32_t *rows_device) {
     OSP_HIP(hipGetLastError());
     return OSP_OK;
     OSP_GUARD_END
+}
+
+int osp_im2col_csc(osp_context_t ctx_, osp_dtype_t dtype, uint64_t N, uint64_t C, uint64_t H, uint64_t W, uint64_t nnz_x,
+                   const uint32_t *x_rows, const uint32_t *x_cols, const void *x_vals, osp_memspace_t space,
+                   const osp_conv2d_geometry_t *geom, int validate, uint64_t *nnz_a, int64_t *a_colptr, uint32_t *a_rowidx,
+                   void *a_vals) {
+    Context *ctx = (Context *)ctx_;
+    (void)validate;   // the channel grouping checks x's ranges and duplicates in every case
+    if (!ctx || !nnz_a) return fail(OSP_ERR_ARG, "null context or nnz_a pointer");
+    if (nnz_x && (!x_rows || !x_cols || !x_vals)) return fail(OSP_ERR_ARG, "null operand array");
+    if (dtype != OSP_F32 && dtype != OSP_F64) return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
+    if (space != OSP_HOST && space != OSP_DEVICE) return fail(OSP_ERR_ARG, "bad memory space");
+    if (nnz_x >= 0xffffffffull) return fail(OSP_ERR_ARG, "nnz exceeds the u32 index type");
+    const bool fill = a_colptr || a_rowidx || a_vals;
+    if (fill && !a_colptr) return fail(OSP_ERR_ARG, "a_colptr is null but other output arrays are not");
+    try {
+        OSP_HIP(hipSetDevice(ctx->device));
+        const ConvGeom g = conv_geometry(N, C, H, W, geom);
+        hipStream_t s = ctx->stream;
+        Scratch sc(ctx);
+        // (a_rowidx / a_vals are checked once the count is known: an A without entries needs only its colptr)
+        auto run = [&](auto tag) {
+            using T = decltype(tag);
+            const uint32_t *xr = to_device(sc, x_rows, nnz_x, space, s), *xc = to_device(sc, x_cols, nnz_x, space, s);
+            const T *xv = to_device(sc, (const T *)x_vals, nnz_x, space, s);
+            T *va = (T *)a_vals;
+            *nnz_a = im2col_impl<T>(ctx, sc, N, C, g, nnz_x, xr, xc, xv, fill, a_colptr, a_rowidx, va);
+        };
+        if (dtype == OSP_F32) run(float{});
+        else run(double{});
+    } catch (const Error &e) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return fail(e.status, "%s", e.what());
+    } catch (const std::exception &e) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return fail(OSP_ERR_ALLOC, "%s", e.what());
+    }
+    return OSP_OK;
+}
+
+int osp_spgemm_conv2d(osp_context_t ctx_, osp_dtype_t dtype, uint64_t N, uint64_t C, uint64_t H, uint64_t W, uint64_t nnz_x,
+                      const uint32_t *x_rows, const uint32_t *x_cols, const void *x_vals, uint64_t OC, uint64_t nnz_w,
+                      const uint32_t *w_rows, const uint32_t *w_cols, const void *w_vals, osp_memspace_t space,
+                      const osp_conv2d_geometry_t *geom, const osp_config_t *cfg_, osp_result_t *result) {
+    Context *ctx = (Context *)ctx_;
+    if (!ctx || !result) return fail(OSP_ERR_ARG, "null context or result pointer");
+    if ((nnz_x && (!x_rows || !x_cols || !x_vals)) || (nnz_w && (!w_rows || !w_cols || !w_vals))) return fail(OSP_ERR_ARG, "null operand array");
+    if (dtype != OSP_F32 && dtype != OSP_F64) return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
+    if (space != OSP_HOST && space != OSP_DEVICE) return fail(OSP_ERR_ARG, "bad memory space");
+    if (!OC || OC > 0xffffffffull || nnz_x >= 0xffffffffull || nnz_w >= 0xffffffffull)
+        return fail(OSP_ERR_ARG, "OC must be >= 1; OC or nnz exceeds the u32 index type");
+    osp_config_t cfg;
+    if (cfg_) cfg = *cfg_; else osp_config_default(&cfg);
+    Result *res = new Result;
+    res->ctx = ctx;
+    res->dtype = dtype;
+    res->info.dtype = dtype;
+    note_variants(ctx, res);
+    try {
+        OSP_HIP(hipSetDevice(ctx->device));
+        const ConvGeom g = conv_geometry(N, C, H, W, geom);
+        if (dtype == OSP_F32)
+            spgemm_conv2d_impl<float>(ctx, res, N, C, g, nnz_x, x_rows, x_cols, (const float *)x_vals, OC, nnz_w, w_rows, w_cols,
+                                      (const float *)w_vals, space, cfg);
+        else
+            spgemm_conv2d_impl<double>(ctx, res, N, C, g, nnz_x, x_rows, x_cols, (const double *)x_vals, OC, nnz_w, w_rows, w_cols,
+                                       (const double *)w_vals, space, cfg);
+    } catch (const Error &e) {
+        (void)hipStreamSynchronize(ctx->stream);
+        destroy_result(res);
+        return fail(e.status, "%s", e.what());
+    } catch (const std::exception &e) {
+        (void)hipStreamSynchronize(ctx->stream);
+        destroy_result(res);
+        return fail(OSP_ERR_ALLOC, "%s", e.what());
+    }
+    *result = (osp_result_t)res;
+    return OSP_OK;
+}
+
+int osp_csr_maxpool2d(osp_result_t in_, uint64_t N, uint64_t H, uint64_t W, uint32_t kh, uint32_t kw, uint32_t stride_h,
+                      uint32_t stride_w, osp_result_t *out) {
+    Result *in = (Result *)in_;
+    if (!in || !out) return fail(OSP_ERR_ARG, "null argument");
+    if (in->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
+    if (!N || !H || !W || !kh || !kw || !stride_h || !stride_w) return fail(OSP_ERR_ARG, "sizes, kernel and stride must be >= 1");
+    if (H < kh || W < kw) return fail(OSP_ERR_ARG, "the pooling window is larger than the input: empty output");
+    if (H >= 0xffffffffull || W >= 0xffffffffull || (unsigned __int128)N * H * W != in->info.M)
+        return fail(OSP_ERR_ARG, "N*H*W must equal the rows of the input");
+    Context *ctx = in->ctx;
+    Result *res = new Result;
+    res->ctx = ctx;
+    res->dtype = in->dtype;
+    try {
+        OSP_HIP(hipSetDevice(ctx->device));
+        if (in->dtype == OSP_F32) maxpool_impl<float>(ctx, in, res, N, (uint32_t)H, (uint32_t)W, kh, kw, stride_h, stride_w);
+        else maxpool_impl<double>(ctx, in, res, N, (uint32_t)H, (uint32_t)W, kh, kw, stride_h, stride_w);
+    } catch (const Error &e) {
+        (void)hipStreamSynchronize(ctx->stream);
+        destroy_result(res);
+        return fail(e.status, "%s", e.what());
+    } catch (const std::exception &e) {
+        (void)hipStreamSynchronize(ctx->stream);
+        destroy_result(res);
+        return fail(OSP_ERR_ALLOC, "%s", e.what());
+    }
+    *out = (osp_result_t)res;
+    return OSP_OK;
 }
 
 // ---- what a plain stream reaches on this device (bench.py: roofline.peak_measured) ----

@@ -28,6 +28,27 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data if a.size else 0)
 
 
+def _pair(v):
+    return (int(v), int(v)) if np.isscalar(v) else (int(v[0]), int(v[1]))
+
+
+def conv2d_geometry(kernel_size, stride=1, padding=0, dilation=1):
+    """``osp_conv2d_geometry_t`` from torch-style arguments (an int or an (h, w) pair each)."""
+    g = _lib.Conv2dGeometry()
+    g.kh, g.kw = _pair(kernel_size)
+    g.stride_h, g.stride_w = _pair(stride)
+    g.pad_h, g.pad_w = _pair(padding)
+    g.dil_h, g.dil_w = _pair(dilation)
+    return g
+
+
+def conv2d_output_size(size, kernel, stride=1, padding=0, dilation=1):
+    """Output extent of one axis: ``(size + 2*padding - dilation*(kernel - 1) - 1) // stride + 1`` (torch.nn.Conv2d's
+    formula, floor mode); 0 when the dilated kernel does not fit the padded input."""
+    span = size + 2 * padding - dilation * (kernel - 1) - 1
+    return span // stride + 1 if span >= 0 else 0
+
+
 class CsrResult:
     """Library-owned CSR result.  ``rowptr``/``colidx``/``vals`` copy to the host on first use."""
 
@@ -76,6 +97,17 @@ class CsrResult:
             raise ValueError(f"bias must have {self.shape[1]} entries")
         h = C.c_void_p()
         _lib.check(_lib.lib().osp_csr_bias_relu(self._h, _ptr(b) if b is not None else None, _lib.OSP_HOST, int(bool(relu)), C.byref(h)))
+        return CsrResult(self._ctx, h)
+
+    def maxpool2d(self, N, H, W, kernel_size, stride=None):
+        """MaxPool2d of this CSR read as a "pixel x channel" activation of N images of H x W pixels (row n*H*W + y*W + x):
+        a new (N*PH*PW) x C CSR result on the device (``osp_csr_maxpool2d``).  An absent entry counts as 0 and zeros are
+        dropped, so it equals ``F.max_pool2d`` on the densified input.  No padding, no dilation, floor mode; stride
+        defaults to the kernel size, as in torch."""
+        kh, kw = _pair(kernel_size)
+        sh, sw = _pair(kernel_size if stride is None else stride)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_csr_maxpool2d(self._h, int(N), int(H), int(W), kh, kw, sh, sw, C.byref(h)))
         return CsrResult(self._ctx, h)
 
     def coo_rows_into(self, rows_device_ptr):
@@ -239,6 +271,29 @@ class Context:
         h = C.c_void_p()
         _lib.check(_lib.lib().osp_spgemm_coo(self._h, _DT[np.dtype(dtype)], M, K, N, int(nnz_a), *[C.c_void_p(int(p)) for p in a_ptrs],
                                              int(nnz_b), *[C.c_void_p(int(p)) for p in b_ptrs], _lib.OSP_DEVICE, C.byref(cfg), C.byref(h)))
+        return CsrResult(self, h)
+
+    def im2col_device(self, dtype, N, C_, H, W, nnz_x, x_ptrs, geom, *, out_ptrs=None, validate=True):
+        """im2col of a "pixel x channel" activation into CSC (``osp_im2col_csc``).  x_ptrs = (rows, cols, vals) DEVICE
+        addresses of the input's COO (row n*H*W + y*W + x, column c; any order), geom = ``conv2d_geometry(...)``.  Without
+        ``out_ptrs`` only nnz(A) is computed; with out_ptrs = (colptr, rowidx, vals) device addresses of C*kh*kw + 1,
+        nnz(A) and nnz(A) entries A is written there.  Returns nnz(A)."""
+        n = C.c_uint64()
+        outs = [None, None, None] if out_ptrs is None else [C.c_void_p(int(p)) if p else None for p in out_ptrs]
+        _lib.check(_lib.lib().osp_im2col_csc(self._h, _DT[np.dtype(dtype)], int(N), int(C_), int(H), int(W), int(nnz_x),
+                                             *[C.c_void_p(int(p)) if p else None for p in x_ptrs], _lib.OSP_DEVICE, C.byref(geom),
+                                             int(bool(validate)), C.byref(n), *outs))
+        return n.value
+
+    def spgemm_conv2d_device(self, dtype, N, C_, H, W, nnz_x, x_ptrs, OC, nnz_w, w_ptrs, geom, *, validate=True, partial_capacity=0):
+        """A conv layer as the CLI's product im2col(x) * W^T (``osp_spgemm_conv2d``): x as in ``im2col_device``, W the
+        OC x (C*kh*kw) weight as (rows, cols, vals) DEVICE addresses.  Returns the (N*OH*OW) x OC CSR result (NHWC)."""
+        cfg = self._config(validate, partial_capacity, None)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_spgemm_conv2d(self._h, _DT[np.dtype(dtype)], int(N), int(C_), int(H), int(W), int(nnz_x),
+                                                *[C.c_void_p(int(p)) if p else None for p in x_ptrs], int(OC), int(nnz_w),
+                                                *[C.c_void_p(int(p)) if p else None for p in w_ptrs], _lib.OSP_DEVICE, C.byref(geom),
+                                                C.byref(cfg), C.byref(h)))
         return CsrResult(self, h)
 
     def spgemm_csc_csr_device(self, dtype, M, K, N, ptrs, *, validate=False, partial_capacity=0, k_range=None, row_shard=None):
