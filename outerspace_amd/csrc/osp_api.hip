@@ -57,6 +57,25 @@ static void check_flags(uint32_t f, const char *what) {
     if (f & kFlagUnsorted) throw Error(OSP_ERR_UNSORTED, std::string(what) + ": indices inside a segment are not ascending");
 }
 
+// The end of a timed call: waits for its stream, then its time and every phase's time into the result (a phase the call
+// never began reads 0).
+static void finish_timing(Result *res, EventPair &ev, PhaseTimer &tm, hipStream_t s) {
+    OSP_HIP(hipEventRecord(ev.b, s));
+    OSP_HIP(hipStreamSynchronize(s));
+    osp_result_info_t &i = res->info;
+    i.ms_total = ev.ms();
+    i.ms_symbolic = tm.total(PH_SYM);
+    i.ms_multiply = tm.total(PH_MUL);
+    i.ms_merge = tm.total(PH_MERGE);
+    i.ms_compact = tm.total(PH_COMPACT);
+    i.ms_multiply_kernel = tm.total(PH_MUL_K);
+    i.ms_merge_kernel = tm.total(PH_MERGE_K);
+    i.ms_split_kernel = tm.total(PH_SPLIT_K);
+    i.ms_direct_plan_kernel = tm.total(PH_PLAN_K);
+    i.ms_hub_plan_kernel = tm.total(PH_HUB_K);
+    i.ms_expand_kernel = tm.total(PH_EXPAND_K);
+}
+
 // *out += sum_k nnz(A[:,k]) * nnz(B[k,:]) over all k (one atomic per workgroup)
 __global__ void count_partials_kernel(const int64_t *a_colptr, const int64_t *b_rowptr, uint64_t K, unsigned long long *out) {
     __shared__ uint64_t scratch[256 / kWave + 1];
@@ -78,6 +97,7 @@ static void spgemm_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
     PhaseTimer tm(s);
     EventPair ev;
     OSP_HIP(hipEventRecord(ev.a, s));
+    res->info.M = M; res->info.K = K; res->info.N = N;
 
     // pointer arrays first: nnz comes from their last entries
     const int64_t *a_colptr = to_device(sc, a_colptr_in, K + 1, space, s);
@@ -331,12 +351,7 @@ static void spgemm_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
         tm.begin(PH_MUL);
         if (P) prod.produce(0, M, true, 0, P, (Part<T> *)res->vals, tm, nullptr, nullptr);
         tm.end(PH_MUL);
-        OSP_HIP(hipEventRecord(ev.b, s));
-        OSP_HIP(hipStreamSynchronize(s));
-        res->info.ms_total = ev.ms();
-        res->info.ms_symbolic = tm.total(PH_SYM);
-        res->info.ms_multiply = tm.total(PH_MUL);
-        res->info.ms_multiply_kernel = tm.total(PH_MUL_K);
+        finish_timing(res, ev, tm, s);
         return;
     }
     // row-sharded: A holds this rank's rows only, so the staging offsets start at 0 at r_lo and P is the shard's count
@@ -344,9 +359,7 @@ static void spgemm_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
     merge_pipeline<T>(ctx, res, prod, M, N, row_off, P_rows, cfg.partial_capacity, tm, r_lo, r_hi, off_lo, sink,
                       rowwise ? &ct : nullptr, (direct && nnz) ? &dsrc : nullptr, nullptr, gather_short ? &srun : nullptr);
 
-    OSP_HIP(hipEventRecord(ev.b, s));
-    OSP_HIP(hipStreamSynchronize(s));
-    const float ms = ev.ms();
+    finish_timing(res, ev, tm, s);
     if (gather_short) res->info.gathered_short_partials = res->info.partials - res->info.heavy_partials;
     if (dsrc.gstat && res->info.direct_rows) {
         uint64_t gs[3] = {0, 0, 0};
@@ -354,20 +367,9 @@ static void spgemm_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
         res->info.gathered_rows = gs[0]; res->info.gathered_partials = gs[1]; res->info.gathered_runs = gs[2];
     }
     if (getenv("OSP_VERBOSE")) {
-        fprintf(stderr, "[osp] product done in %.1f ms; pool misses so far: %llu hipMalloc calls, %.1f GB, %.1f ms\n", ms,
+        fprintf(stderr, "[osp] product done in %.1f ms; pool misses so far: %llu hipMalloc calls, %.1f GB, %.1f ms\n", res->info.ms_total,
                 (unsigned long long)ctx->malloc_calls, ctx->malloc_bytes / 1e9, ctx->malloc_ms);
     }
-    res->info.ms_total = ms;
-    res->info.ms_symbolic = tm.total(PH_SYM);
-    res->info.ms_multiply = tm.total(PH_MUL);
-    res->info.ms_merge = tm.total(PH_MERGE);
-    res->info.ms_compact = tm.total(PH_COMPACT);
-    res->info.ms_multiply_kernel = tm.total(PH_MUL_K);
-    res->info.ms_merge_kernel = tm.total(PH_MERGE_K);
-    res->info.ms_split_kernel = tm.total(PH_SPLIT_K);
-    res->info.ms_direct_plan_kernel = tm.total(PH_PLAN_K);
-    res->info.ms_hub_plan_kernel = tm.total(PH_HUB_K);
-    res->info.ms_expand_kernel = tm.total(PH_EXPAND_K);
 }
 
 // COO (device arrays, any order) -> compressed by `seg` with ascending `inner` indices; all outputs in `sc`.
@@ -462,6 +464,26 @@ static void spgemm_aos_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, u
     spgemm_impl<T>(ctx, res, M, K, N, ap, ai, av, bp, bi, bv, OSP_DEVICE, cfg);
 }
 
+// The symbolic phase of a parts merge: the candidate chunks -- chunk (r, p) = row r of part p -- scanned into every row's
+// offset into the staging (prod.row_off); info.partials = P, the entries of all parts.  `prod` reads the parts' rows
+// through d_rp, the device array of their row pointers.
+template <class Producer>
+static void parts_symbolic(Context *ctx, Scratch &sc, PhaseTimer &tm, Result *res, const int64_t *const *d_rp, int nparts, uint64_t M,
+                           Producer &prod) {
+    hipStream_t s = ctx->stream;
+    tm.begin(PH_SYM);
+    const uint64_t ncand = M * (uint64_t)nparts;
+    uint64_t *row_off = sc.get<uint64_t>(M + 1);
+    uint64_t *offs = sc.get<uint64_t>(ncand + 1);
+    uint64_t *scan_tmp = sc.get<uint64_t>(scan_scratch_entries(ncand));
+    device_exclusive_scan<PartsChunkLen, uint64_t>(PartsChunkLen{d_rp, nparts}, ncand, offs, scan_tmp, s);
+    parts_rows_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(offs, nparts, M, row_off);
+    const uint64_t P = d2h(offs + ncand, s);
+    tm.end(PH_SYM);
+    res->info.partials = P;
+    prod.ctx = ctx; prod.d_rowptrs = d_rp; prod.nparts = nparts; prod.row_off = row_off;
+}
+
 template <class T>
 static void merge_parts_impl(Context *ctx, Result *res, uint64_t M, uint64_t N, int nparts,
                              const int64_t *const *rowptrs, const uint32_t *const *colidxs, const void *const *valss,
@@ -471,6 +493,7 @@ static void merge_parts_impl(Context *ctx, Result *res, uint64_t M, uint64_t N, 
     PhaseTimer tm(s);
     EventPair ev;
     OSP_HIP(hipEventRecord(ev.a, s));
+    res->info.M = M; res->info.N = N;
     std::vector<const int64_t *> rp(nparts);
     std::vector<const uint32_t *> ci(nparts);
     std::vector<const T *> va(nparts);
@@ -493,31 +516,11 @@ static void merge_parts_impl(Context *ctx, Result *res, uint64_t M, uint64_t N, 
     copy_h2d(d_rp, rp.data(), nparts * sizeof(void *), s);
     copy_h2d(d_ci, ci.data(), nparts * sizeof(void *), s);
     copy_h2d(d_va, va.data(), nparts * sizeof(void *), s);
-    tm.begin(PH_SYM);
-    const uint64_t ncand = M * (uint64_t)nparts;  // candidate chunk (r, p) = row r of part p
-    uint64_t *row_off = sc.get<uint64_t>(M + 1);
-    uint64_t *offs = sc.get<uint64_t>(ncand + 1);
-    uint64_t *scan_tmp = sc.get<uint64_t>(scan_scratch_entries(ncand));
-    const PartsChunkLen plen{d_rp, nparts};
-    device_exclusive_scan<PartsChunkLen, uint64_t>(plen, ncand, offs, scan_tmp, s);
-    parts_rows_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(offs, nparts, M, row_off);
-    const uint64_t P = d2h(offs + ncand, s);
-    tm.end(PH_SYM);
-    res->info.partials = P;
     PartsProducer<T> prod;
-    prod.ctx = ctx; prod.d_rowptrs = d_rp; prod.d_colidxs = d_ci; prod.d_valss = d_va;
-    prod.nparts = nparts; prod.row_off = row_off;
-    merge_pipeline<T>(ctx, res, prod, M, N, row_off, P, cfg.partial_capacity, tm);
-    OSP_HIP(hipEventRecord(ev.b, s));
-    OSP_HIP(hipStreamSynchronize(s));
-    res->info.ms_total = ev.ms();
-    res->info.ms_symbolic = tm.total(PH_SYM);
-    res->info.ms_multiply = tm.total(PH_MUL);
-    res->info.ms_merge = tm.total(PH_MERGE);
-    res->info.ms_compact = tm.total(PH_COMPACT);
-    res->info.ms_multiply_kernel = tm.total(PH_MUL_K);
-    res->info.ms_merge_kernel = tm.total(PH_MERGE_K);
-    res->info.ms_split_kernel = tm.total(PH_SPLIT_K);
+    prod.d_colidxs = d_ci; prod.d_valss = d_va;
+    parts_symbolic(ctx, sc, tm, res, d_rp, nparts, M, prod);
+    merge_pipeline<T>(ctx, res, prod, M, N, prod.row_off, res->info.partials, cfg.partial_capacity, tm);
+    finish_timing(res, ev, tm, s);
 }
 
 template <class T>
@@ -530,6 +533,7 @@ static void merge_record_parts_impl(Context *ctx, Result *res, uint64_t M, uint6
     PhaseTimer tm(s);
     EventPair ev;
     OSP_HIP(hipEventRecord(ev.a, s));
+    res->info.M = M; res->info.N = N;
     std::vector<const int64_t *> rp(nparts);
     std::vector<const Part<T> *> rc(nparts);
     uint64_t nnz_in = 0;
@@ -556,28 +560,12 @@ static void merge_record_parts_impl(Context *ctx, Result *res, uint64_t M, uint6
     const Part<T> **d_rc = (const Part<T> **)sc.get<void *>(nparts);
     copy_h2d(d_rp, rp.data(), nparts * sizeof(void *), s);
     copy_h2d(d_rc, rc.data(), nparts * sizeof(void *), s);
-    tm.begin(PH_SYM);
-    const uint64_t ncand = M * (uint64_t)nparts;  // candidate chunk (r, p) = row r of part p
-    uint64_t *row_off = sc.get<uint64_t>(M + 1);
-    uint64_t *offs = sc.get<uint64_t>(ncand + 1);
-    uint64_t *scan_tmp = sc.get<uint64_t>(scan_scratch_entries(ncand));
-    device_exclusive_scan<PartsChunkLen, uint64_t>(PartsChunkLen{d_rp, nparts}, ncand, offs, scan_tmp, s);
-    parts_rows_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(offs, nparts, M, row_off);
-    const uint64_t P = d2h(offs + ncand, s);
-    tm.end(PH_SYM);
-    res->info.partials = P;
     RecordPartsProducer<T> prod;
-    prod.ctx = ctx; prod.d_rowptrs = d_rp; prod.d_recs = d_rc; prod.nparts = nparts; prod.row_off = row_off; prod.before = before;
-    merge_pipeline<T>(ctx, res, prod, M, N, row_off, P, cfg.partial_capacity, tm, 0, ~0ull, 0, nullptr, nullptr, nullptr, cuts);
-    OSP_HIP(hipEventRecord(ev.b, s));
-    OSP_HIP(hipStreamSynchronize(s));
-    res->info.ms_total = ev.ms();
-    res->info.ms_symbolic = tm.total(PH_SYM);
-    res->info.ms_multiply = tm.total(PH_MUL);
-    res->info.ms_merge = tm.total(PH_MERGE);
-    res->info.ms_compact = tm.total(PH_COMPACT);
-    res->info.ms_merge_kernel = tm.total(PH_MERGE_K);
-    res->info.ms_split_kernel = tm.total(PH_SPLIT_K);
+    prod.d_recs = d_rc; prod.before = before;
+    parts_symbolic(ctx, sc, tm, res, d_rp, nparts, M, prod);
+    merge_pipeline<T>(ctx, res, prod, M, N, prod.row_off, res->info.partials, cfg.partial_capacity, tm, 0, ~0ull, 0, nullptr, nullptr,
+                      nullptr, cuts);
+    finish_timing(res, ev, tm, s);
 }
 
 // which of the two exact variants of the order-sensitive steps this context runs (visible in every result)
@@ -702,7 +690,6 @@ static void spgemm_conv2d_impl(Context *ctx, Result *res, uint64_t N, uint64_t C
     OSP_HIP(hipEventRecord(ev.b, s));
     osp_config_t c2 = cfg;
     c2.validate = 0;  // A is well formed by construction; W's ranges and duplicates were just checked
-    res->info.M = M; res->info.K = K; res->info.N = OC;
     spgemm_impl<T>(ctx, res, M, K, OC, ap, ai, av, bp, bi, bv, OSP_DEVICE, c2);
     const float ms = ev.ms();
     res->info.ms_ingest = ms;
@@ -753,6 +740,54 @@ static void destroy_result(Result *r) {
     delete r;
 }
 
+// ---- what the entry points share ----
+static void check_dtype(int dtype) {
+    if (dtype != OSP_F32 && dtype != OSP_F64) throw Error(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
+}
+static void check_space(int space) {
+    if (space != OSP_HOST && space != OSP_DEVICE) throw Error(OSP_ERR_ARG, "bad memory space");
+}
+static void check_dims(uint64_t M, uint64_t K, uint64_t N) {   // (K = 0: no inner dimension)
+    if (M >= 0xffffffffull || N > 0xffffffffull || K >= 0xffffffffull) throw Error(OSP_ERR_ARG, "dimension exceeds the u32 index type");
+}
+static osp_config_t config_or_default(const osp_config_t *cfg) {
+    osp_config_t c;
+    if (cfg) c = *cfg; else osp_config_default(&c);
+    return c;
+}
+// body(T{}) with T the value type of a checked dtype
+template <class F>
+static void with_type(int dtype, F &&body) {
+    if (dtype == OSP_F32) body(float{});
+    else body(double{});
+}
+// Runs `body` on ctx's device.  When it throws, the stream is drained before the exception travels on: no buffer goes back
+// to the pool while work queued on it may still use it.
+template <class F>
+static void on_device(Context *ctx, F &&body) {
+    try {
+        OSP_HIP(hipSetDevice(ctx->device));
+        body();
+    } catch (...) {
+        (void)hipStreamSynchronize(ctx->stream);
+        throw;
+    }
+}
+// The frame of an entry point that makes a result: body(T{}, res) fills a new result on ctx's device, T the value type of
+// `dtype`.  *out gets it when body returns; when body throws, it is released (after the stream is drained) and *out is left
+// as it was.
+template <class F>
+static int new_result(Context *ctx, int dtype, osp_result_t *out, F &&body) {
+    std::unique_ptr<Result, void (*)(Result *)> res(new Result, destroy_result);
+    res->ctx = ctx;
+    res->dtype = dtype;
+    res->info.dtype = dtype;
+    note_variants(ctx, res.get());
+    on_device(ctx, [&] { with_type(dtype, [&](auto tag) { body(tag, res.get()); }); });
+    *out = (osp_result_t)res.release();
+    return OSP_OK;
+}
+
 }  // namespace osp
 
 #include "osp_multi.h"
@@ -760,13 +795,6 @@ static void destroy_result(Result *r) {
 using namespace osp;
 
 // ---- C ABI ---------------------------------------------------------------------------------------
-#define OSP_GUARD_BEGIN try {
-#define OSP_GUARD_END                                                 \
-    }                                                                 \
-    catch (const Error &e) { return fail(e.status, "%s", e.what()); } \
-    catch (const std::bad_alloc &) { return fail(OSP_ERR_ALLOC, "host allocation failed"); } \
-    catch (const std::exception &e) { return fail(OSP_ERR_HIP, "%s", e.what()); }
-
 extern "C" {
 
 const char *osp_status_string(int st) {
@@ -793,64 +821,64 @@ void osp_config_default(osp_config_t *cfg) {
 
 static int context_create(int device, void *stream, bool own, osp_context_t *out) {
     if (!out) return fail(OSP_ERR_ARG, "null context pointer");
-    OSP_GUARD_BEGIN
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        throw Error(OSP_ERR_HIP, "no HIP device visible: this library has no CPU path");
-    if (device < 0 || device >= ndev) throw Error(OSP_ERR_ARG, "device ordinal out of range");
-    OSP_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    OSP_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        throw Error(OSP_ERR_HIP, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
-    Context *c = new Context;
-    c->device = device;
-    c->cus = (uint32_t)prop.multiProcessorCount;
-    if (own) { OSP_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
-    else c->stream = (hipStream_t)stream;
-    try {
-        // Which stable rank this context uses.  The atomic one needs a property of LDS atomics that is not documented, so
-        // it is tested here on THIS device; when the test fails the context falls back to the ballot instantiations of the
-        // same kernels (slower -- merge +20 % -- and just as exact) instead of refusing to work.
-        const char *force = getenv("OSP_RANK");   // "ballot" | "atomic": debugging and tests/test_gpu_parity.py
-        if (force && strcmp(force, "ballot") == 0) c->rank_atomic = false;
-        else if (force && strcmp(force, "atomic") == 0) c->rank_atomic = true;
-        if (c->rank_atomic) {
-            Scratch sc(c);
-            uint32_t *bad = sc.get<uint32_t>(1);
-            OSP_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), c->stream));
-            rank_order_selftest_kernel<<<64, 256, 0, c->stream>>>(bad);
-            if (d2h(bad, c->stream) != 0) {
-                c->rank_atomic = false;
-                if (getenv("OSP_VERBOSE")) fprintf(stderr, "[osp] LDS atomics do not return old values in lane order on this device: using ballot ranks\n");
+    return guard([&] {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+            throw Error(OSP_ERR_HIP, "no HIP device visible: this library has no CPU path");
+        if (device < 0 || device >= ndev) throw Error(OSP_ERR_ARG, "device ordinal out of range");
+        OSP_HIP(hipSetDevice(device));
+        hipDeviceProp_t prop;
+        OSP_HIP(hipGetDeviceProperties(&prop, device));
+        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+            throw Error(OSP_ERR_HIP, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
+        Context *c = new Context;
+        c->device = device;
+        c->cus = (uint32_t)prop.multiProcessorCount;
+        if (own) { OSP_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
+        else c->stream = (hipStream_t)stream;
+        try {
+            // Which stable rank this context uses.  The atomic one needs a property of LDS atomics that is not documented, so
+            // it is tested here on THIS device; when the test fails the context falls back to the ballot instantiations of the
+            // same kernels (slower -- merge +20 % -- and just as exact) instead of refusing to work.
+            const char *force = getenv("OSP_RANK");   // "ballot" | "atomic": debugging and tests/test_gpu_parity.py
+            if (force && strcmp(force, "ballot") == 0) c->rank_atomic = false;
+            else if (force && strcmp(force, "atomic") == 0) c->rank_atomic = true;
+            if (c->rank_atomic) {
+                Scratch sc(c);
+                uint32_t *bad = sc.get<uint32_t>(1);
+                OSP_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), c->stream));
+                rank_order_selftest_kernel<<<64, 256, 0, c->stream>>>(bad);
+                if (d2h(bad, c->stream) != 0) {
+                    c->rank_atomic = false;
+                    if (getenv("OSP_VERBOSE")) fprintf(stderr, "[osp] LDS atomics do not return old values in lane order on this device: using ballot ranks\n");
+                }
             }
-        }
-        const char *fadd = getenv("OSP_DENSE_ADD");
-        for (int wide = 0; wide < 2; wide++) {
-            if (fadd && strcmp(fadd, "ballot") == 0) c->dense_atomic[wide] = false;
-            else if (fadd && strcmp(fadd, "atomic") == 0) c->dense_atomic[wide] = true;
-            if (!c->dense_atomic[wide]) continue;
-            Scratch sc(c);
-            uint32_t *bad = sc.get<uint32_t>(1);
-            OSP_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), c->stream));
-            if (wide) fadd_order_selftest_kernel<double><<<64, 256, 0, c->stream>>>(bad);
-            else fadd_order_selftest_kernel<float><<<64, 256, 0, c->stream>>>(bad);
-            if (d2h(bad, c->stream) != 0) {
-                c->dense_atomic[wide] = false;
-                if (getenv("OSP_VERBOSE"))
-                    fprintf(stderr, "[osp] LDS %s atomics do not add in lane order (or flush subnormals) on this device: dense segments by ballot ranks\n",
-                            wide ? "f64" : "f32");
+            const char *fadd = getenv("OSP_DENSE_ADD");
+            for (int wide = 0; wide < 2; wide++) {
+                if (fadd && strcmp(fadd, "ballot") == 0) c->dense_atomic[wide] = false;
+                else if (fadd && strcmp(fadd, "atomic") == 0) c->dense_atomic[wide] = true;
+                if (!c->dense_atomic[wide]) continue;
+                Scratch sc(c);
+                uint32_t *bad = sc.get<uint32_t>(1);
+                OSP_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), c->stream));
+                if (wide) fadd_order_selftest_kernel<double><<<64, 256, 0, c->stream>>>(bad);
+                else fadd_order_selftest_kernel<float><<<64, 256, 0, c->stream>>>(bad);
+                if (d2h(bad, c->stream) != 0) {
+                    c->dense_atomic[wide] = false;
+                    if (getenv("OSP_VERBOSE"))
+                        fprintf(stderr, "[osp] LDS %s atomics do not add in lane order (or flush subnormals) on this device: dense segments by ballot ranks\n",
+                                wide ? "f64" : "f32");
+                }
             }
+        } catch (...) {
+            c->trim();
+            if (c->own_stream) (void)hipStreamDestroy(c->stream);
+            delete c;
+            throw;
         }
-    } catch (...) {
-        c->trim();
-        if (c->own_stream) (void)hipStreamDestroy(c->stream);
-        delete c;
-        throw;
-    }
-    *out = (osp_context_t)c;
-    return OSP_OK;
-    OSP_GUARD_END
+        *out = (osp_context_t)c;
+        return OSP_OK;
+    });
 }
 int osp_context_create(int device, osp_context_t *ctx) { return context_create(device, nullptr, true, ctx); }
 int osp_context_create_on_stream(int device, void *hip_stream, osp_context_t *ctx) {
@@ -864,11 +892,11 @@ int osp_context_trim(osp_context_t c) {
 int osp_context_alloc(osp_context_t c_, uint64_t bytes, void **device_ptr) {
     Context *c = (Context *)c_;
     if (!c || !device_ptr) return fail(OSP_ERR_ARG, "null argument");
-    OSP_GUARD_BEGIN
-    OSP_HIP(hipSetDevice(c->device));
-    *device_ptr = c->alloc((size_t)bytes);
-    return OSP_OK;
-    OSP_GUARD_END
+    return guard([&] {
+        OSP_HIP(hipSetDevice(c->device));
+        *device_ptr = c->alloc((size_t)bytes);
+        return OSP_OK;
+    });
 }
 int osp_context_free(osp_context_t c_, void *device_ptr) {
     Context *c = (Context *)c_;
@@ -897,35 +925,14 @@ int osp_spgemm_csc_csr(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint64
     Context *ctx = (Context *)ctx_;
     if (!ctx || !result) return fail(OSP_ERR_ARG, "null context or result pointer");
     if (!a_colptr || !b_rowptr) return fail(OSP_ERR_ARG, "null pointer array");
-    if (dtype != OSP_F32 && dtype != OSP_F64) return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
-    if (space != OSP_HOST && space != OSP_DEVICE) return fail(OSP_ERR_ARG, "bad memory space");
-    if (M >= 0xffffffffull || N > 0xffffffffull || K >= 0xffffffffull) return fail(OSP_ERR_ARG, "dimension exceeds the u32 index type");
-    osp_config_t cfg;
-    if (cfg_) cfg = *cfg_; else osp_config_default(&cfg);
-    Result *res = new Result;
-    res->ctx = ctx;
-    res->dtype = dtype;
-    res->info.M = M; res->info.K = K; res->info.N = N; res->info.dtype = dtype;
-    note_variants(ctx, res);
-    try {
-        OSP_HIP(hipSetDevice(ctx->device));
-        if (dtype == OSP_F32)
-            spgemm_impl<float>(ctx, res, M, K, N, a_colptr, a_rowidx, (const float *)a_vals, b_rowptr, b_colidx,
-                               (const float *)b_vals, space, cfg);
-        else
-            spgemm_impl<double>(ctx, res, M, K, N, a_colptr, a_rowidx, (const double *)a_vals, b_rowptr, b_colidx,
-                                (const double *)b_vals, space, cfg);
-    } catch (const Error &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(e.status, "%s", e.what());
-    } catch (const std::exception &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(OSP_ERR_ALLOC, "%s", e.what());
-    }
-    *result = (osp_result_t)res;
-    return OSP_OK;
+    return guard([&] {
+        check_dtype(dtype); check_space(space); check_dims(M, K, N);
+        const osp_config_t cfg = config_or_default(cfg_);
+        return new_result(ctx, dtype, result, [&](auto tag, Result *res) {
+            using T = decltype(tag);
+            spgemm_impl<T>(ctx, res, M, K, N, a_colptr, a_rowidx, (const T *)a_vals, b_rowptr, b_colidx, (const T *)b_vals, space, cfg);
+        });
+    });
 }
 
 int osp_spgemm_csc_csr_aos(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint64_t K, uint64_t N, const uint64_t *a_pos,
@@ -934,31 +941,13 @@ int osp_spgemm_csc_csr_aos(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, ui
     Context *ctx = (Context *)ctx_;
     if (!ctx || !result) return fail(OSP_ERR_ARG, "null context or result pointer");
     if (!a_pos || !b_pos) return fail(OSP_ERR_ARG, "null pointer array");
-    if (dtype != OSP_F32 && dtype != OSP_F64) return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
-    if (space != OSP_HOST && space != OSP_DEVICE) return fail(OSP_ERR_ARG, "bad memory space");
-    if (M >= 0xffffffffull || N > 0xffffffffull || K >= 0xffffffffull) return fail(OSP_ERR_ARG, "dimension exceeds the u32 index type");
-    osp_config_t cfg;
-    if (cfg_) cfg = *cfg_; else osp_config_default(&cfg);
-    Result *res = new Result;
-    res->ctx = ctx;
-    res->dtype = dtype;
-    res->info.M = M; res->info.K = K; res->info.N = N; res->info.dtype = dtype;
-    note_variants(ctx, res);
-    try {
-        OSP_HIP(hipSetDevice(ctx->device));
-        if (dtype == OSP_F32) spgemm_aos_impl<float>(ctx, res, M, K, N, a_pos, a_data, b_pos, b_data, space, cfg);
-        else spgemm_aos_impl<double>(ctx, res, M, K, N, a_pos, a_data, b_pos, b_data, space, cfg);
-    } catch (const Error &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(e.status, "%s", e.what());
-    } catch (const std::exception &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(OSP_ERR_ALLOC, "%s", e.what());
-    }
-    *result = (osp_result_t)res;
-    return OSP_OK;
+    return guard([&] {
+        check_dtype(dtype); check_space(space); check_dims(M, K, N);
+        const osp_config_t cfg = config_or_default(cfg_);
+        return new_result(ctx, dtype, result, [&](auto tag, Result *res) {
+            spgemm_aos_impl<decltype(tag)>(ctx, res, M, K, N, a_pos, a_data, b_pos, b_data, space, cfg);
+        });
+    });
 }
 
 int osp_spgemm_csc_csr_panels(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint64_t K, uint64_t N,
@@ -969,36 +958,20 @@ int osp_spgemm_csc_csr_panels(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M,
     Context *ctx = (Context *)ctx_;
     if (!ctx || !fn) return fail(OSP_ERR_ARG, "null context or panel callback");
     if (!a_colptr || !b_rowptr) return fail(OSP_ERR_ARG, "null pointer array");
-    if (dtype != OSP_F32 && dtype != OSP_F64) return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
-    if (space != OSP_HOST && space != OSP_DEVICE) return fail(OSP_ERR_ARG, "bad memory space");
-    if (M >= 0xffffffffull || N > 0xffffffffull || K >= 0xffffffffull) return fail(OSP_ERR_ARG, "dimension exceeds the u32 index type");
-    osp_config_t cfg;
-    if (cfg_) cfg = *cfg_; else osp_config_default(&cfg);
-    Result *res = new Result;  // carries the counters only: no output arrays are attached in streaming mode
-    res->ctx = ctx;
-    res->dtype = dtype;
-    res->info.M = M; res->info.K = K; res->info.N = N; res->info.dtype = dtype;
-    note_variants(ctx, res);
-    const PanelSink sink{fn, user};
-    int st = OSP_OK;
-    try {
-        OSP_HIP(hipSetDevice(ctx->device));
-        if (dtype == OSP_F32)
-            spgemm_impl<float>(ctx, res, M, K, N, a_colptr, a_rowidx, (const float *)a_vals, b_rowptr, b_colidx,
-                               (const float *)b_vals, space, cfg, &sink);
-        else
-            spgemm_impl<double>(ctx, res, M, K, N, a_colptr, a_rowidx, (const double *)a_vals, b_rowptr, b_colidx,
-                                (const double *)b_vals, space, cfg, &sink);
-        if (info) *info = res->info;
-    } catch (const Error &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        st = fail(e.status, "%s", e.what());
-    } catch (const std::exception &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        st = fail(OSP_ERR_ALLOC, "%s", e.what());
-    }
-    destroy_result(res);
-    return st;
+    return guard([&] {
+        check_dtype(dtype); check_space(space); check_dims(M, K, N);
+        const osp_config_t cfg = config_or_default(cfg_);
+        const PanelSink sink{fn, user};
+        osp_result_t r = nullptr;   // carries the counters only: no output arrays are attached in streaming mode
+        new_result(ctx, dtype, &r, [&](auto tag, Result *res) {
+            using T = decltype(tag);
+            spgemm_impl<T>(ctx, res, M, K, N, a_colptr, a_rowidx, (const T *)a_vals, b_rowptr, b_colidx, (const T *)b_vals, space, cfg,
+                           &sink);
+            if (info) *info = res->info;
+        });
+        destroy_result((Result *)r);
+        return OSP_OK;
+    });
 }
 
 int osp_spgemm_coo(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint64_t K, uint64_t N, uint64_t nnz_a,
@@ -1008,36 +981,17 @@ int osp_spgemm_coo(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint64_t K
     Context *ctx = (Context *)ctx_;
     if (!ctx || !result) return fail(OSP_ERR_ARG, "null context or result pointer");
     if ((nnz_a && (!a_rows || !a_cols || !a_vals)) || (nnz_b && (!b_rows || !b_cols || !b_vals))) return fail(OSP_ERR_ARG, "null operand array");
-    if (dtype != OSP_F32 && dtype != OSP_F64) return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
-    if (space != OSP_HOST && space != OSP_DEVICE) return fail(OSP_ERR_ARG, "bad memory space");
-    if (M >= 0xffffffffull || N > 0xffffffffull || K >= 0xffffffffull || nnz_a >= 0xffffffffull || nnz_b >= 0xffffffffull)
-        return fail(OSP_ERR_ARG, "dimension or nnz exceeds the u32 index type");
-    osp_config_t cfg;
-    if (cfg_) cfg = *cfg_; else osp_config_default(&cfg);
-    Result *res = new Result;
-    res->ctx = ctx;
-    res->dtype = dtype;
-    res->info.M = M; res->info.K = K; res->info.N = N; res->info.dtype = dtype;
-    note_variants(ctx, res);
-    try {
-        OSP_HIP(hipSetDevice(ctx->device));
-        if (dtype == OSP_F32)
-            spgemm_coo_impl<float>(ctx, res, M, K, N, nnz_a, a_rows, a_cols, (const float *)a_vals, nnz_b, b_rows, b_cols,
-                                   (const float *)b_vals, space, cfg);
-        else
-            spgemm_coo_impl<double>(ctx, res, M, K, N, nnz_a, a_rows, a_cols, (const double *)a_vals, nnz_b, b_rows, b_cols,
-                                    (const double *)b_vals, space, cfg);
-    } catch (const Error &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(e.status, "%s", e.what());
-    } catch (const std::exception &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(OSP_ERR_ALLOC, "%s", e.what());
-    }
-    *result = (osp_result_t)res;
-    return OSP_OK;
+    return guard([&] {
+        check_dtype(dtype); check_space(space);
+        if (M >= 0xffffffffull || N > 0xffffffffull || K >= 0xffffffffull || nnz_a >= 0xffffffffull || nnz_b >= 0xffffffffull)
+            throw Error(OSP_ERR_ARG, "dimension or nnz exceeds the u32 index type");
+        const osp_config_t cfg = config_or_default(cfg_);
+        return new_result(ctx, dtype, result, [&](auto tag, Result *res) {
+            using T = decltype(tag);
+            spgemm_coo_impl<T>(ctx, res, M, K, N, nnz_a, a_rows, a_cols, (const T *)a_vals, nnz_b, b_rows, b_cols, (const T *)b_vals, space,
+                               cfg);
+        });
+    });
 }
 
 int osp_merge_csr_parts(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint64_t N, int nparts,
@@ -1047,30 +1001,13 @@ int osp_merge_csr_parts(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint6
     Context *ctx = (Context *)ctx_;
     if (!ctx || !result || !rowptrs || !colidxs || !valss) return fail(OSP_ERR_ARG, "null argument");
     if (nparts < 1) return fail(OSP_ERR_ARG, "nparts must be >= 1");
-    if (dtype != OSP_F32 && dtype != OSP_F64) return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
-    if (M >= 0xffffffffull || N > 0xffffffffull) return fail(OSP_ERR_ARG, "dimension exceeds the u32 index type");
-    osp_config_t cfg;
-    if (cfg_) cfg = *cfg_; else osp_config_default(&cfg);
-    Result *res = new Result;
-    res->ctx = ctx;
-    res->dtype = dtype;
-    res->info.M = M; res->info.N = N; res->info.dtype = dtype;
-    note_variants(ctx, res);
-    try {
-        OSP_HIP(hipSetDevice(ctx->device));
-        if (dtype == OSP_F32) merge_parts_impl<float>(ctx, res, M, N, nparts, rowptrs, colidxs, valss, space, cfg);
-        else merge_parts_impl<double>(ctx, res, M, N, nparts, rowptrs, colidxs, valss, space, cfg);
-    } catch (const Error &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(e.status, "%s", e.what());
-    } catch (const std::exception &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(OSP_ERR_ALLOC, "%s", e.what());
-    }
-    *result = (osp_result_t)res;
-    return OSP_OK;
+    return guard([&] {
+        check_dtype(dtype); check_space(space); check_dims(M, 0, N);
+        const osp_config_t cfg = config_or_default(cfg_);
+        return new_result(ctx, dtype, result, [&](auto tag, Result *res) {
+            merge_parts_impl<decltype(tag)>(ctx, res, M, N, nparts, rowptrs, colidxs, valss, space, cfg);
+        });
+    });
 }
 
 int osp_spgemm_partials(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint64_t K, uint64_t N, const int64_t *a_colptr,
@@ -1079,35 +1016,15 @@ int osp_spgemm_partials(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint6
     Context *ctx = (Context *)ctx_;
     if (!ctx || !result) return fail(OSP_ERR_ARG, "null context or result pointer");
     if (!a_colptr || !b_rowptr) return fail(OSP_ERR_ARG, "null pointer array");
-    if (dtype != OSP_F32 && dtype != OSP_F64) return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
-    if (space != OSP_HOST && space != OSP_DEVICE) return fail(OSP_ERR_ARG, "bad memory space");
-    if (M >= 0xffffffffull || N > 0xffffffffull || K >= 0xffffffffull) return fail(OSP_ERR_ARG, "dimension exceeds the u32 index type");
-    osp_config_t cfg;
-    if (cfg_) cfg = *cfg_; else osp_config_default(&cfg);
-    Result *res = new Result;
-    res->ctx = ctx;
-    res->dtype = dtype;
-    res->info.M = M; res->info.K = K; res->info.N = N; res->info.dtype = dtype;
-    note_variants(ctx, res);
-    try {
-        OSP_HIP(hipSetDevice(ctx->device));
-        if (dtype == OSP_F32)
-            spgemm_impl<float>(ctx, res, M, K, N, a_colptr, a_rowidx, (const float *)a_vals, b_rowptr, b_colidx, (const float *)b_vals,
-                               space, cfg, nullptr, true);
-        else
-            spgemm_impl<double>(ctx, res, M, K, N, a_colptr, a_rowidx, (const double *)a_vals, b_rowptr, b_colidx,
-                                (const double *)b_vals, space, cfg, nullptr, true);
-    } catch (const Error &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(e.status, "%s", e.what());
-    } catch (const std::exception &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(OSP_ERR_ALLOC, "%s", e.what());
-    }
-    *result = (osp_result_t)res;
-    return OSP_OK;
+    return guard([&] {
+        check_dtype(dtype); check_space(space); check_dims(M, K, N);
+        const osp_config_t cfg = config_or_default(cfg_);
+        return new_result(ctx, dtype, result, [&](auto tag, Result *res) {
+            using T = decltype(tag);
+            spgemm_impl<T>(ctx, res, M, K, N, a_colptr, a_rowidx, (const T *)a_vals, b_rowptr, b_colidx, (const T *)b_vals, space, cfg,
+                           nullptr, true);
+        });
+    });
 }
 
 int osp_result_partials(osp_result_t r_, const int64_t **rowptr, const void **records) {
@@ -1124,72 +1041,41 @@ int osp_merge_record_parts(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, ui
     Context *ctx = (Context *)ctx_;
     if (!ctx || !result || !rowptrs || !records) return fail(OSP_ERR_ARG, "null argument");
     if (nparts < 1) return fail(OSP_ERR_ARG, "nparts must be >= 1");
-    if (dtype != OSP_F32 && dtype != OSP_F64) return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
-    if (space != OSP_HOST && space != OSP_DEVICE) return fail(OSP_ERR_ARG, "bad memory space");
-    if (M >= 0xffffffffull || N > 0xffffffffull) return fail(OSP_ERR_ARG, "dimension exceeds the u32 index type");
-    osp_config_t cfg;
-    if (cfg_) cfg = *cfg_; else osp_config_default(&cfg);
-    Result *res = new Result;
-    res->ctx = ctx;
-    res->dtype = dtype;
-    res->info.M = M; res->info.N = N; res->info.dtype = dtype;
-    note_variants(ctx, res);
-    try {
-        OSP_HIP(hipSetDevice(ctx->device));
-        if (dtype == OSP_F32) merge_record_parts_impl<float>(ctx, res, M, N, nparts, rowptrs, records, space, cfg);
-        else merge_record_parts_impl<double>(ctx, res, M, N, nparts, rowptrs, records, space, cfg);
-    } catch (const Error &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(e.status, "%s", e.what());
-    } catch (const std::exception &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(OSP_ERR_ALLOC, "%s", e.what());
-    }
-    *result = (osp_result_t)res;
-    return OSP_OK;
+    return guard([&] {
+        check_dtype(dtype); check_space(space); check_dims(M, 0, N);
+        const osp_config_t cfg = config_or_default(cfg_);
+        return new_result(ctx, dtype, result, [&](auto tag, Result *res) {
+            merge_record_parts_impl<decltype(tag)>(ctx, res, M, N, nparts, rowptrs, records, space, cfg);
+        });
+    });
 }
 
 int osp_csr_bias_relu(osp_result_t in_, const void *bias, osp_memspace_t bias_space, int relu, osp_result_t *out) {
     Result *in = (Result *)in_;
     if (!in || !out) return fail(OSP_ERR_ARG, "null argument");
     if (in->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
-    if (bias_space != OSP_HOST && bias_space != OSP_DEVICE) return fail(OSP_ERR_ARG, "bad memory space");
-    Context *ctx = in->ctx;
-    Result *res = new Result;
-    res->ctx = ctx;
-    res->dtype = in->dtype;
-    try {
-        OSP_HIP(hipSetDevice(ctx->device));
-        if (in->dtype == OSP_F32) bias_relu_impl<float>(ctx, in, res, (const float *)bias, bias_space, relu);
-        else bias_relu_impl<double>(ctx, in, res, (const double *)bias, bias_space, relu);
-    } catch (const Error &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(e.status, "%s", e.what());
-    } catch (const std::exception &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(OSP_ERR_ALLOC, "%s", e.what());
-    }
-    *out = (osp_result_t)res;
-    return OSP_OK;
+    return guard([&] {
+        check_space(bias_space);
+        return new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {
+            using T = decltype(tag);
+            bias_relu_impl<T>(in->ctx, in, res, (const T *)bias, bias_space, relu);   // (res->info: in's, variants included)
+        });
+    });
 }
 
 int osp_result_coo_rows(osp_result_t r_, uint32_t *rows_device) {
     Result *r = (Result *)r_;
     if (!r || !rows_device) return fail(OSP_ERR_ARG, "null argument");
     if (r->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
-    OSP_GUARD_BEGIN
-    OSP_HIP(hipSetDevice(r->ctx->device));
-    const uint64_t M = r->info.M;
-    if (M && r->info.nnz_c)
-        csr_expand_rows_kernel<<<grid_for(M * kWave, 256), 256, 0, r->ctx->stream>>>(r->rowptr, M, rows_device);
-    OSP_HIP(hipStreamSynchronize(r->ctx->stream));
-    OSP_HIP(hipGetLastError());
-    return OSP_OK;
-    OSP_GUARD_END
+    return guard([&] {
+        OSP_HIP(hipSetDevice(r->ctx->device));
+        const uint64_t M = r->info.M;
+        if (M && r->info.nnz_c)
+            csr_expand_rows_kernel<<<grid_for(M * kWave, 256), 256, 0, r->ctx->stream>>>(r->rowptr, M, rows_device);
+        OSP_HIP(hipStreamSynchronize(r->ctx->stream));
+        OSP_HIP(hipGetLastError());
+        return OSP_OK;
+    });
 }
 
 int osp_im2col_csc(osp_context_t ctx_, osp_dtype_t dtype, uint64_t N, uint64_t C, uint64_t H, uint64_t W, uint64_t nnz_x,
@@ -1200,34 +1086,26 @@ int osp_im2col_csc(osp_context_t ctx_, osp_dtype_t dtype, uint64_t N, uint64_t C
     (void)validate;   // the channel grouping checks x's ranges and duplicates in every case
     if (!ctx || !nnz_a) return fail(OSP_ERR_ARG, "null context or nnz_a pointer");
     if (nnz_x && (!x_rows || !x_cols || !x_vals)) return fail(OSP_ERR_ARG, "null operand array");
-    if (dtype != OSP_F32 && dtype != OSP_F64) return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
-    if (space != OSP_HOST && space != OSP_DEVICE) return fail(OSP_ERR_ARG, "bad memory space");
-    if (nnz_x >= 0xffffffffull) return fail(OSP_ERR_ARG, "nnz exceeds the u32 index type");
-    const bool fill = a_colptr || a_rowidx || a_vals;
-    if (fill && !a_colptr) return fail(OSP_ERR_ARG, "a_colptr is null but other output arrays are not");
-    try {
-        OSP_HIP(hipSetDevice(ctx->device));
-        const ConvGeom g = conv_geometry(N, C, H, W, geom);
-        hipStream_t s = ctx->stream;
-        Scratch sc(ctx);
-        // (a_rowidx / a_vals are checked once the count is known: an A without entries needs only its colptr)
-        auto run = [&](auto tag) {
-            using T = decltype(tag);
-            const uint32_t *xr = to_device(sc, x_rows, nnz_x, space, s), *xc = to_device(sc, x_cols, nnz_x, space, s);
-            const T *xv = to_device(sc, (const T *)x_vals, nnz_x, space, s);
-            T *va = (T *)a_vals;
-            *nnz_a = im2col_impl<T>(ctx, sc, N, C, g, nnz_x, xr, xc, xv, fill, a_colptr, a_rowidx, va);
-        };
-        if (dtype == OSP_F32) run(float{});
-        else run(double{});
-    } catch (const Error &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return fail(e.status, "%s", e.what());
-    } catch (const std::exception &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return fail(OSP_ERR_ALLOC, "%s", e.what());
-    }
-    return OSP_OK;
+    return guard([&] {
+        check_dtype(dtype); check_space(space);
+        if (nnz_x >= 0xffffffffull) throw Error(OSP_ERR_ARG, "nnz exceeds the u32 index type");
+        const bool fill = a_colptr || a_rowidx || a_vals;
+        if (fill && !a_colptr) throw Error(OSP_ERR_ARG, "a_colptr is null but other output arrays are not");
+        on_device(ctx, [&] {
+            const ConvGeom g = conv_geometry(N, C, H, W, geom);
+            hipStream_t s = ctx->stream;
+            Scratch sc(ctx);
+            // (a_rowidx / a_vals are checked once the count is known: an A without entries needs only its colptr)
+            with_type(dtype, [&](auto tag) {
+                using T = decltype(tag);
+                const uint32_t *xr = to_device(sc, x_rows, nnz_x, space, s), *xc = to_device(sc, x_cols, nnz_x, space, s);
+                const T *xv = to_device(sc, (const T *)x_vals, nnz_x, space, s);
+                T *va = (T *)a_vals;
+                *nnz_a = im2col_impl<T>(ctx, sc, N, C, g, nnz_x, xr, xc, xv, fill, a_colptr, a_rowidx, va);
+            });
+        });
+        return OSP_OK;
+    });
 }
 
 int osp_spgemm_conv2d(osp_context_t ctx_, osp_dtype_t dtype, uint64_t N, uint64_t C, uint64_t H, uint64_t W, uint64_t nnz_x,
@@ -1237,37 +1115,18 @@ int osp_spgemm_conv2d(osp_context_t ctx_, osp_dtype_t dtype, uint64_t N, uint64_
     Context *ctx = (Context *)ctx_;
     if (!ctx || !result) return fail(OSP_ERR_ARG, "null context or result pointer");
     if ((nnz_x && (!x_rows || !x_cols || !x_vals)) || (nnz_w && (!w_rows || !w_cols || !w_vals))) return fail(OSP_ERR_ARG, "null operand array");
-    if (dtype != OSP_F32 && dtype != OSP_F64) return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
-    if (space != OSP_HOST && space != OSP_DEVICE) return fail(OSP_ERR_ARG, "bad memory space");
-    if (!OC || OC > 0xffffffffull || nnz_x >= 0xffffffffull || nnz_w >= 0xffffffffull)
-        return fail(OSP_ERR_ARG, "OC must be >= 1; OC or nnz exceeds the u32 index type");
-    osp_config_t cfg;
-    if (cfg_) cfg = *cfg_; else osp_config_default(&cfg);
-    Result *res = new Result;
-    res->ctx = ctx;
-    res->dtype = dtype;
-    res->info.dtype = dtype;
-    note_variants(ctx, res);
-    try {
-        OSP_HIP(hipSetDevice(ctx->device));
-        const ConvGeom g = conv_geometry(N, C, H, W, geom);
-        if (dtype == OSP_F32)
-            spgemm_conv2d_impl<float>(ctx, res, N, C, g, nnz_x, x_rows, x_cols, (const float *)x_vals, OC, nnz_w, w_rows, w_cols,
-                                      (const float *)w_vals, space, cfg);
-        else
-            spgemm_conv2d_impl<double>(ctx, res, N, C, g, nnz_x, x_rows, x_cols, (const double *)x_vals, OC, nnz_w, w_rows, w_cols,
-                                       (const double *)w_vals, space, cfg);
-    } catch (const Error &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(e.status, "%s", e.what());
-    } catch (const std::exception &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(OSP_ERR_ALLOC, "%s", e.what());
-    }
-    *result = (osp_result_t)res;
-    return OSP_OK;
+    return guard([&] {
+        check_dtype(dtype); check_space(space);
+        if (!OC || OC > 0xffffffffull || nnz_x >= 0xffffffffull || nnz_w >= 0xffffffffull)
+            throw Error(OSP_ERR_ARG, "OC must be >= 1; OC or nnz exceeds the u32 index type");
+        const osp_config_t cfg = config_or_default(cfg_);
+        return new_result(ctx, dtype, result, [&](auto tag, Result *res) {
+            using T = decltype(tag);
+            const ConvGeom g = conv_geometry(N, C, H, W, geom);
+            spgemm_conv2d_impl<T>(ctx, res, N, C, g, nnz_x, x_rows, x_cols, (const T *)x_vals, OC, nnz_w, w_rows, w_cols, (const T *)w_vals,
+                                  space, cfg);
+        });
+    });
 }
 
 int osp_csr_maxpool2d(osp_result_t in_, uint64_t N, uint64_t H, uint64_t W, uint32_t kh, uint32_t kw, uint32_t stride_h,
@@ -1279,25 +1138,11 @@ int osp_csr_maxpool2d(osp_result_t in_, uint64_t N, uint64_t H, uint64_t W, uint
     if (H < kh || W < kw) return fail(OSP_ERR_ARG, "the pooling window is larger than the input: empty output");
     if (H >= 0xffffffffull || W >= 0xffffffffull || (unsigned __int128)N * H * W != in->info.M)
         return fail(OSP_ERR_ARG, "N*H*W must equal the rows of the input");
-    Context *ctx = in->ctx;
-    Result *res = new Result;
-    res->ctx = ctx;
-    res->dtype = in->dtype;
-    try {
-        OSP_HIP(hipSetDevice(ctx->device));
-        if (in->dtype == OSP_F32) maxpool_impl<float>(ctx, in, res, N, (uint32_t)H, (uint32_t)W, kh, kw, stride_h, stride_w);
-        else maxpool_impl<double>(ctx, in, res, N, (uint32_t)H, (uint32_t)W, kh, kw, stride_h, stride_w);
-    } catch (const Error &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(e.status, "%s", e.what());
-    } catch (const std::exception &e) {
-        (void)hipStreamSynchronize(ctx->stream);
-        destroy_result(res);
-        return fail(OSP_ERR_ALLOC, "%s", e.what());
-    }
-    *out = (osp_result_t)res;
-    return OSP_OK;
+    return guard([&] {
+        return new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {   // (res->info: in's, variants included)
+            maxpool_impl<decltype(tag)>(in->ctx, in, res, N, (uint32_t)H, (uint32_t)W, kh, kw, stride_h, stride_w);
+        });
+    });
 }
 
 // ---- what a plain stream reaches on this device (bench.py: roofline.peak_measured) ----
@@ -1308,53 +1153,53 @@ int osp_stream_copy_probe(osp_context_t ctx_, uint64_t bytes, int reps, double *
     Context *ctx = (Context *)ctx_;
     if (!ctx || !gbps) return fail(OSP_ERR_ARG, "null argument");
     if (bytes < 4096 || reps < 1 || reps > 1000) return fail(OSP_ERR_ARG, "bytes >= 4096, 1 <= reps <= 1000");
-    OSP_GUARD_BEGIN
-    OSP_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    Scratch sc(ctx);
-    const uint64_t n = bytes / sizeof(u32x4);
-    u32x4 *src = sc.get<u32x4>(n), *dst = sc.get<u32x4>(n);
-    OSP_HIP(hipMemsetAsync(src, 0x5a, n * sizeof(u32x4), s));
-    if (n > 0xffffffffull * 256ull) return fail(OSP_ERR_ARG, "probe buffer too large");
-    const unsigned grid = (unsigned)((n + 255) / 256);
-    double best = 0;
-    for (int nt = 0; nt < 2; nt++) {   // plain and non-temporal accesses: the better of the two is the measured roof
-        for (int i = 0; i < 2; i++) {   // untimed: page tables, clocks
-            if (nt) stream_copy_kernel<true><<<grid, 256, 0, s>>>(src, dst, n); else stream_copy_kernel<false><<<grid, 256, 0, s>>>(src, dst, n);
+    return guard([&]() -> int {
+        OSP_HIP(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        Scratch sc(ctx);
+        const uint64_t n = bytes / sizeof(u32x4);
+        u32x4 *src = sc.get<u32x4>(n), *dst = sc.get<u32x4>(n);
+        OSP_HIP(hipMemsetAsync(src, 0x5a, n * sizeof(u32x4), s));
+        if (n > 0xffffffffull * 256ull) return fail(OSP_ERR_ARG, "probe buffer too large");
+        const unsigned grid = (unsigned)((n + 255) / 256);
+        double best = 0;
+        for (int nt = 0; nt < 2; nt++) {   // plain and non-temporal accesses: the better of the two is the measured roof
+            for (int i = 0; i < 2; i++) {   // untimed: page tables, clocks
+                if (nt) stream_copy_kernel<true><<<grid, 256, 0, s>>>(src, dst, n); else stream_copy_kernel<false><<<grid, 256, 0, s>>>(src, dst, n);
+            }
+            EventPair ev;
+            OSP_HIP(hipEventRecord(ev.a, s));
+            for (int i = 0; i < reps; i++) {
+                if (nt) stream_copy_kernel<true><<<grid, 256, 0, s>>>(src, dst, n); else stream_copy_kernel<false><<<grid, 256, 0, s>>>(src, dst, n);
+            }
+            OSP_HIP(hipEventRecord(ev.b, s));
+            OSP_HIP(hipStreamSynchronize(s));
+            OSP_HIP(hipGetLastError());
+            const double ms = ev.ms();
+            if (ms > 0) best = std::max(best, 2.0 * (double)(n * sizeof(u32x4)) * reps / (ms * 1e-3) / 1e9);
         }
-        EventPair ev;
-        OSP_HIP(hipEventRecord(ev.a, s));
-        for (int i = 0; i < reps; i++) {
-            if (nt) stream_copy_kernel<true><<<grid, 256, 0, s>>>(src, dst, n); else stream_copy_kernel<false><<<grid, 256, 0, s>>>(src, dst, n);
-        }
-        OSP_HIP(hipEventRecord(ev.b, s));
-        OSP_HIP(hipStreamSynchronize(s));
-        OSP_HIP(hipGetLastError());
-        const double ms = ev.ms();
-        if (ms > 0) best = std::max(best, 2.0 * (double)(n * sizeof(u32x4)) * reps / (ms * 1e-3) / 1e9);
-    }
-    *gbps = best;
-    return OSP_OK;
-    OSP_GUARD_END
+        *gbps = best;
+        return OSP_OK;
+    });
 }
 
 // ---- several GPUs of one node (osp_multi.h) ----
 int osp_multi_context_create(const int *devices, int ndev, osp_multi_context_t *out) {
     if (!devices || !out) return fail(OSP_ERR_ARG, "null argument");
     if (ndev < 1 || ndev > OSP_MULTI_MAX_RANKS) return fail(OSP_ERR_ARG, "between 1 and %d ranks", OSP_MULTI_MAX_RANKS);
-    MultiContext *mc = new MultiContext;
-    try {
+    return guard([&]() -> int {
+        std::unique_ptr<MultiContext> mc(new MultiContext);
         for (int g = 0; g < ndev; g++) {
             osp_context_t c = nullptr;
             const int st = osp_context_create(devices[g], &c);
-            if (st) { delete mc; return st; }   // (the message is already set)
+            if (st) return st;   // (the message is already set)
             mc->devices.push_back(devices[g]);
             mc->ctx.push_back((Context *)c);
             mc->copy.emplace_back((size_t)ndev, nullptr);
             mc->mctx.push_back(nullptr);
             osp_context_t c2 = nullptr;
             const int st2 = osp_context_create(devices[g], &c2);   // the merge of what arrives: a stream and a pool of its own
-            if (st2) { delete mc; return st2; }
+            if (st2) return st2;
             mc->mctx.back() = (Context *)c2;
             mc->ctx.back()->sibling = mc->mctx.back();
             mc->mctx.back()->sibling = mc->ctx.back();
@@ -1376,12 +1221,9 @@ int osp_multi_context_create(const int *devices, int ndev, osp_multi_context_t *
                     (void)hipGetLastError();   // "already enabled" is fine
                 }
             }
-    } catch (const Error &e) {
-        delete mc;
-        return fail(e.status, "%s", e.what());
-    }
-    *out = (osp_multi_context_t)mc;
-    return OSP_OK;
+        *out = (osp_multi_context_t)mc.release();
+        return OSP_OK;
+    });
 }
 int osp_multi_context_destroy(osp_multi_context_t mc) {
     delete (MultiContext *)mc;
@@ -1393,29 +1235,24 @@ int osp_multi_operands_create(osp_multi_context_t mc_, osp_dtype_t dtype, uint64
                               const void *b_vals, osp_multi_operands_t *out) {
     MultiContext *mc = (MultiContext *)mc_;
     if (!mc || !out || !a_colptr || !b_rowptr) return fail(OSP_ERR_ARG, "null argument");
-    if (dtype != OSP_F32 && dtype != OSP_F64) return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
-    if (M >= 0xffffffffull || N > 0xffffffffull || K >= 0xffffffffull) return fail(OSP_ERR_ARG, "dimension exceeds the u32 index type");
-    const int64_t nnz_a = a_colptr[K], nnz_b = b_rowptr[K];
-    if (nnz_a < 0 || nnz_b < 0 || (uint64_t)nnz_a >= 0xffffffffull || (uint64_t)nnz_b >= 0xffffffffull)
-        return fail(OSP_ERR_ARG, "operands with >= 2^32 non-zeros are not supported");
-    if ((nnz_a && (!a_rowidx || !a_vals)) || (nnz_b && (!b_colidx || !b_vals))) return fail(OSP_ERR_ARG, "null operand array");
-    for (uint64_t k = 0; k < K; k++)
-        if (a_colptr[k + 1] < a_colptr[k] || b_rowptr[k + 1] < b_rowptr[k] || a_colptr[0] != 0 || b_rowptr[0] != 0)
-            return fail(OSP_ERR_ARG, "pointer array is not a monotone 0..nnz sequence");
-    MultiOperands *ops = new MultiOperands;
-    ops->mc = mc; ops->dtype = dtype; ops->M = M; ops->K = K; ops->N = N;
-    try {
-        if (dtype == OSP_F32) multi_upload<float>(mc, ops, a_colptr, a_rowidx, (const float *)a_vals, b_rowptr, b_colidx, (const float *)b_vals);
-        else multi_upload<double>(mc, ops, a_colptr, a_rowidx, (const double *)a_vals, b_rowptr, b_colidx, (const double *)b_vals);
-    } catch (const Error &e) {
-        delete ops;
-        return fail(e.status, "%s", e.what());
-    } catch (const std::exception &e) {
-        delete ops;
-        return fail(OSP_ERR_ALLOC, "%s", e.what());
-    }
-    *out = (osp_multi_operands_t)ops;
-    return OSP_OK;
+    return guard([&]() -> int {
+        check_dtype(dtype); check_dims(M, K, N);
+        const int64_t nnz_a = a_colptr[K], nnz_b = b_rowptr[K];
+        if (nnz_a < 0 || nnz_b < 0 || (uint64_t)nnz_a >= 0xffffffffull || (uint64_t)nnz_b >= 0xffffffffull)
+            return fail(OSP_ERR_ARG, "operands with >= 2^32 non-zeros are not supported");
+        if ((nnz_a && (!a_rowidx || !a_vals)) || (nnz_b && (!b_colidx || !b_vals))) return fail(OSP_ERR_ARG, "null operand array");
+        for (uint64_t k = 0; k < K; k++)
+            if (a_colptr[k + 1] < a_colptr[k] || b_rowptr[k + 1] < b_rowptr[k] || a_colptr[0] != 0 || b_rowptr[0] != 0)
+                return fail(OSP_ERR_ARG, "pointer array is not a monotone 0..nnz sequence");
+        std::unique_ptr<MultiOperands> ops(new MultiOperands);
+        ops->mc = mc; ops->dtype = dtype; ops->M = M; ops->K = K; ops->N = N;
+        with_type(dtype, [&](auto tag) {
+            using T = decltype(tag);
+            multi_upload<T>(mc, ops.get(), a_colptr, a_rowidx, (const T *)a_vals, b_rowptr, b_colidx, (const T *)b_vals);
+        });
+        *out = (osp_multi_operands_t)ops.release();
+        return OSP_OK;
+    });
 }
 int osp_multi_operands_destroy(osp_multi_operands_t ops) {
     delete (MultiOperands *)ops;
@@ -1427,12 +1264,11 @@ int osp_spgemm_multi(osp_multi_context_t mc_, osp_multi_operands_t ops_, const o
     MultiOperands *ops = (MultiOperands *)ops_;
     if (!mc || !ops || !out) return fail(OSP_ERR_ARG, "null argument");
     if (ops->mc != mc) return fail(OSP_ERR_ARG, "operands belong to another multi-GPU context");
-    osp_config_t cfg;
-    if (cfg_) cfg = *cfg_; else osp_config_default(&cfg);
-    MultiResult *res = new MultiResult;
-    res->mc = mc;
-    res->dtype = ops->dtype;
-    try {
+    return guard([&] {
+        const osp_config_t cfg = config_or_default(cfg_);
+        std::unique_ptr<MultiResult> res(new MultiResult);
+        res->mc = mc;
+        res->dtype = ops->dtype;
         if (cfg.validate) {
             // per slab, as the single-GPU entry point does: ordering, ranges, duplicates (233)
             for (size_t g = 0; g < mc->ctx.size(); g++) {
@@ -1450,18 +1286,11 @@ int osp_spgemm_multi(osp_multi_context_t mc_, osp_multi_operands_t ops_, const o
                 check_flags(fb, "B (CSR)");
             }
         }
-        if (ops->dtype == OSP_F32) multi_product<float>(mc, ops, res, cfg);
-        else multi_product<double>(mc, ops, res, cfg);
+        with_type(ops->dtype, [&](auto tag) { multi_product<decltype(tag)>(mc, ops, res.get(), cfg); });
         res->info.ms_upload = ops->ms_upload;
-    } catch (const Error &e) {
-        delete res;
-        return fail(e.status, "%s", e.what());
-    } catch (const std::exception &e) {
-        delete res;
-        return fail(OSP_ERR_ALLOC, "%s", e.what());
-    }
-    *out = (osp_multi_result_t)res;
-    return OSP_OK;
+        *out = (osp_multi_result_t)res.release();
+        return OSP_OK;
+    });
 }
 
 int osp_spgemm_csc_csr_multi(const int *devices, int ndev, osp_dtype_t dtype, uint64_t M, uint64_t K, uint64_t N, const int64_t *a_colptr,
@@ -1526,20 +1355,20 @@ int osp_result_copy_csr(osp_result_t r_, int64_t *rowptr, uint32_t *colidx, void
     Result *r = (Result *)r_;
     if (!r) return fail(OSP_ERR_ARG, "null result");
     if (r->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR: use osp_result_partials");
-    OSP_GUARD_BEGIN
-    OSP_HIP(hipSetDevice(r->ctx->device));
-    hipStream_t s = r->ctx->stream;
-    const size_t vs = r->dtype == OSP_F32 ? 4 : 8;
-    auto out = [&](void *dst, const void *src, size_t bytes) {
-        if (space == OSP_HOST) copy_d2h(dst, src, bytes, s);
-        else OSP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
-    };
-    if (rowptr) out(rowptr, r->rowptr, (r->info.M + 1) * sizeof(int64_t));
-    if (colidx && r->info.nnz_c) out(colidx, r->colidx, r->info.nnz_c * sizeof(uint32_t));
-    if (vals && r->info.nnz_c) out(vals, r->vals, r->info.nnz_c * vs);
-    OSP_HIP(hipStreamSynchronize(s));
-    return OSP_OK;
-    OSP_GUARD_END
+    return guard([&] {
+        OSP_HIP(hipSetDevice(r->ctx->device));
+        hipStream_t s = r->ctx->stream;
+        const size_t vs = r->dtype == OSP_F32 ? 4 : 8;
+        auto out = [&](void *dst, const void *src, size_t bytes) {
+            if (space == OSP_HOST) copy_d2h(dst, src, bytes, s);
+            else OSP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
+        };
+        if (rowptr) out(rowptr, r->rowptr, (r->info.M + 1) * sizeof(int64_t));
+        if (colidx && r->info.nnz_c) out(colidx, r->colidx, r->info.nnz_c * sizeof(uint32_t));
+        if (vals && r->info.nnz_c) out(vals, r->vals, r->info.nnz_c * vs);
+        OSP_HIP(hipStreamSynchronize(s));
+        return OSP_OK;
+    });
 }
 
 int osp_result_device_ptrs(osp_result_t r_, const int64_t **rowptr, const uint32_t **colidx, const void **vals) {

@@ -38,6 +38,7 @@ int fail(int status, const char *fmt, ...) {
 }  // namespace osp
 
 using osp::fail;
+using osp::guard;
 
 extern "C" {
 
@@ -276,32 +277,30 @@ extern "C" {
 
 int osp_coo_to_compressed_f32(int by_col, uint64_t nseg, uint64_t nnz, const uint32_t *rows, const uint32_t *cols,
                               const float *vals, int64_t *ptr, uint32_t *idx, float *out_vals) {
-    try { return coo_to_compressed<float>(by_col, nseg, nnz, rows, cols, vals, ptr, idx, out_vals); }
-    catch (const std::exception &e) { return fail(OSP_ERR_ALLOC, "%s", e.what()); }
+    return guard([&] { return coo_to_compressed<float>(by_col, nseg, nnz, rows, cols, vals, ptr, idx, out_vals); });
 }
 int osp_coo_to_compressed_f64(int by_col, uint64_t nseg, uint64_t nnz, const uint32_t *rows, const uint32_t *cols,
                               const double *vals, int64_t *ptr, uint32_t *idx, double *out_vals) {
-    try { return coo_to_compressed<double>(by_col, nseg, nnz, rows, cols, vals, ptr, idx, out_vals); }
-    catch (const std::exception &e) { return fail(OSP_ERR_ALLOC, "%s", e.what()); }
+    return guard([&] { return coo_to_compressed<double>(by_col, nseg, nnz, rows, cols, vals, ptr, idx, out_vals); });
 }
 
 #ifndef OSP_HOST_ONLY
 int osp_spgemm_mtx(osp_context_t ctx, osp_dtype_t dtype, const char *path_a, const char *path_b, int transpose_b,
                    const osp_config_t *cfg, osp_result_t *result) {
     if (!ctx || !path_a || !path_b || !result) return fail(OSP_ERR_ARG, "null argument");
-    try {
+    return guard([&] {
         if (dtype == OSP_F32) return spgemm_mtx_t<float>(ctx, dtype, path_a, path_b, transpose_b, cfg, result);
         if (dtype == OSP_F64) return spgemm_mtx_t<double>(ctx, dtype, path_a, path_b, transpose_b, cfg, result);
-    } catch (const std::exception &e) { return fail(OSP_ERR_ALLOC, "%s", e.what()); }
-    return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
+        return fail(OSP_ERR_ARG, "dtype must be OSP_F32 or OSP_F64");
+    });
 }
 
 int osp_result_write_mtx(osp_result_t r, const char *path) {
     if (!r || !path) return fail(OSP_ERR_ARG, "null argument");
-    osp_result_info_t info;
-    int st = osp_result_info(r, &info);
-    if (st) return st;
-    try {
+    return guard([&]() -> int {
+        osp_result_info_t info;
+        int st = osp_result_info(r, &info);
+        if (st) return st;
         std::vector<int64_t> rp(info.M + 1);
         std::vector<uint32_t> ci(info.nnz_c ? info.nnz_c : 1);
         std::vector<double> vd;
@@ -320,8 +319,8 @@ int osp_result_write_mtx(osp_result_t r, const char *path) {
                 else fprintf(f, "%" PRIu64 " %u %.17g\n", row + 1, ci[i] + 1, vd[i]);
             }
         fclose(f);
-    } catch (const std::exception &e) { return fail(OSP_ERR_ALLOC, "%s", e.what()); }
-    return OSP_OK;
+        return OSP_OK;
+    });
 }
 
 #endif  // OSP_HOST_ONLY

@@ -198,3 +198,97 @@ def test_parallel_reader_gives_the_single_threaded_result(tmp_path, monkeypatch,
         assert got[:2] == want[:2]
         for x, y in zip(got[2:], want[2:]):
             assert np.array_equal(x, y)
+
+
+def _null_handle_calls(tmp_path, golden_dir):
+    """(entry point, arguments, expected status): every exported function that takes a context, result, multi-context or
+    operands handle, called with a null handle and otherwise valid host memory and a valid config."""
+    import ctypes as C
+    L = _lib.lib()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    ptr = np.array([0, 2, 3], np.int64)
+    pos = ptr.astype(np.uint64)
+    idx = np.array([0, 1, 1], np.uint32)
+    val = np.array([1.0, 2.0, 3.0])
+    rec = np.zeros(3, dtype=S.aos_dtype(np.float64))
+    cfg = _lib.Config()
+    L.osp_config_default(C.byref(cfg))
+    geom = S.conv2d_geometry(1)
+    out = C.c_void_p(0)
+    info = _lib.ResultInfo()
+    minfo = _lib.MultiInfo()
+    u64 = C.c_uint64(0)
+    rps = (C.c_void_p * 1)(p(ptr))
+    cis = (C.c_void_p * 1)(p(idx))
+    vas = (C.c_void_p * 1)(p(val))
+    recs = (C.c_void_p * 1)(p(rec))
+    fn = _lib.PANEL_FN(lambda panel, user: 0)
+    f64, host, ok, arg = _lib.OSP_F64, _lib.OSP_HOST, _lib.OSP_OK, _lib.ERR_ARG
+    mtx = os.path.join(golden_dir, "c1_A.mtx").encode()
+    csr = (p(ptr), p(idx), p(val), p(ptr), p(idx), p(val))
+    return [
+        ("osp_context_destroy", (None,), ok),
+        ("osp_context_trim", (None,), arg),
+        ("osp_context_alloc", (None, 64, C.byref(out)), arg),
+        ("osp_context_free", (None, None), arg),
+        ("osp_spgemm_csc_csr", (None, f64, 2, 2, 2, *csr, host, C.byref(cfg), C.byref(out)), arg),
+        ("osp_spgemm_csc_csr_aos", (None, f64, 2, 2, 2, p(pos), p(rec), p(pos), p(rec), host, C.byref(cfg), C.byref(out)), arg),
+        ("osp_spgemm_csc_csr_panels", (None, f64, 2, 2, 2, *csr, host, C.byref(cfg), fn, None, C.byref(info)), arg),
+        ("osp_spgemm_coo", (None, f64, 2, 2, 2, 3, p(idx), p(idx), p(val), 3, p(idx), p(idx), p(val), host, C.byref(cfg),
+                            C.byref(out)), arg),
+        ("osp_spgemm_partials", (None, f64, 2, 2, 2, *csr, host, C.byref(cfg), C.byref(out)), arg),
+        ("osp_merge_csr_parts", (None, f64, 2, 2, 1, rps, cis, vas, host, C.byref(cfg), C.byref(out)), arg),
+        ("osp_merge_record_parts", (None, f64, 2, 2, 1, rps, recs, host, C.byref(cfg), C.byref(out)), arg),
+        ("osp_stream_copy_probe", (None, 4096, 1, C.byref(C.c_double())), arg),
+        ("osp_im2col_csc", (None, f64, 1, 1, 2, 2, 3, p(idx), p(idx), p(val), host, C.byref(geom), 1, C.byref(u64), None, None,
+                            None), arg),
+        ("osp_spgemm_conv2d", (None, f64, 1, 1, 2, 2, 3, p(idx), p(idx), p(val), 2, 3, p(idx), p(idx), p(val), host,
+                               C.byref(geom), C.byref(cfg), C.byref(out)), arg),
+        ("osp_spgemm_mtx", (None, f64, mtx, mtx, 1, C.byref(cfg), C.byref(out)), arg),
+        ("osp_result_destroy", (None,), ok),
+        ("osp_result_info", (None, C.byref(info)), arg),
+        ("osp_result_partials", (None, C.byref(out), C.byref(out)), arg),
+        ("osp_result_copy_csr", (None, p(ptr), p(idx), p(val), host), arg),
+        ("osp_result_device_ptrs", (None, C.byref(out), C.byref(out), C.byref(out)), arg),
+        ("osp_result_write_mtx", (None, str(tmp_path / "c.mtx").encode()), arg),
+        ("osp_result_coo_rows", (None, p(idx)), arg),
+        ("osp_csr_bias_relu", (None, p(val), host, 1, C.byref(out)), arg),
+        ("osp_csr_maxpool2d", (None, 1, 2, 2, 1, 1, 1, 1, C.byref(out)), arg),
+        ("osp_multi_context_destroy", (None,), ok),
+        ("osp_multi_operands_create", (None, f64, 2, 2, 2, *csr, C.byref(out)), arg),
+        ("osp_multi_operands_destroy", (None,), ok),
+        ("osp_spgemm_multi", (None, None, C.byref(cfg), C.byref(out)), arg),
+        ("osp_multi_result_info", (None, C.byref(minfo)), arg),
+        ("osp_multi_result_shard", (None, 0, C.byref(u64), C.byref(u64), C.byref(out)), arg),
+        ("osp_multi_result_copy_csr", (None, p(ptr), p(idx), p(val)), arg),
+        ("osp_multi_result_destroy", (None,), ok),
+    ]
+
+
+def test_null_handles_are_argument_errors(tmp_path, golden_dir):
+    """A null context, result, multi-context or operands handle is OSP_ERR_ARG before anything else is looked at (no GPU
+    needed); the *_destroy functions accept null and return OSP_OK."""
+    calls = _null_handle_calls(tmp_path, golden_dir)
+    # every export that takes one of the four handles is in the table
+    no_handle = {"osp_context_create", "osp_context_create_on_stream", "osp_config_default", "osp_last_error_string",
+                 "osp_status_string", "osp_mtx_read", "osp_host_free", "osp_coo_to_compressed_f32", "osp_coo_to_compressed_f64",
+                 "osp_multi_context_create", "osp_spgemm_csc_csr_multi"}
+    assert sorted(name for name, _, _ in calls) == sorted(set(_lib.EXPORTS) - no_handle)
+    L = _lib.lib()
+    for name, args, want in calls:
+        st = getattr(L, name)(*args)
+        assert st == want, (name, st, L.osp_last_error_string())
+        if want != _lib.OSP_OK:
+            assert L.osp_last_error_string(), name
+
+
+def test_status_strings():
+    L = _lib.lib()
+    want = {_lib.OSP_OK: "ok", _lib.ERR_DIM: "inner dimensions differ", _lib.ERR_ARG: "bad argument",
+            _lib.ERR_ALLOC: "allocation failed", _lib.ERR_HIP: "HIP error", _lib.ERR_IO: "I/O error",
+            _lib.ERR_RANGE: "index out of range", _lib.ERR_CAPACITY: "staging capacity exceeded",
+            _lib.ERR_UNSORTED: "indices not ascending", _lib.ERR_DUPLICATE: "duplicate coordinate (233)"}
+    for st, s in want.items():
+        assert L.osp_status_string(st).decode() == s
+    for st in (-1, 9, 232, 234):
+        assert L.osp_status_string(st).decode() == "unknown status"

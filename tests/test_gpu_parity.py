@@ -232,6 +232,114 @@ def test_validation_errors(ctx):
     assert ei.value.status == 233
 
 
+def test_entry_point_argument_errors(_ctx_shared, port):
+    """Each entry point's argument checks, one bad argument at a time: the status, and the output handle left as it was.
+    Every operand is host memory or a valid device buffer, so a missing check shows as a failed assertion.  The context
+    then still computes a good product."""
+    import ctypes as C
+    from outerspace_amd import _lib
+    from outerspace_amd import spgemm as S
+    L = _lib.lib()
+    ctx = _ctx_shared
+    h = ctx._h
+    p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    ptr = np.array([0, 2, 3], np.int64)
+    pos = ptr.astype(np.uint64)
+    idx = np.array([0, 1, 1], np.uint32)
+    val = np.array([1.0, 2.0, 3.0])
+    rec = np.zeros(3, dtype=S.aos_dtype(np.float64))
+    rec["idx"] = idx
+    rec["val"] = val
+    rps = (C.c_void_p * 1)(p(ptr))
+    cis = (C.c_void_p * 1)(p(idx))
+    vas = (C.c_void_p * 1)(p(val))
+    recs = (C.c_void_p * 1)(p(rec))
+    geom = S.conv2d_geometry(1)
+    fn = _lib.PANEL_FN(lambda panel, user: 0)
+    big = 1 << 32
+    f64, host, arg = _lib.OSP_F64, _lib.OSP_HOST, _lib.ERR_ARG
+    csr = (p(ptr), p(idx), p(val), p(ptr), p(idx), p(val))
+    sentinel = 0x5EA1ED
+
+    def cfg():
+        c = _lib.Config()
+        L.osp_config_default(C.byref(c))
+        return c
+
+    # entry point -> function of (dtype, space, M, K, N, nparts, out) giving its arguments
+    product = {
+        "osp_spgemm_csc_csr": lambda dt, sp, M, K, N, n, o: (h, dt, M, K, N, *csr, sp, C.byref(cfg()), o),
+        "osp_spgemm_csc_csr_aos": lambda dt, sp, M, K, N, n, o: (h, dt, M, K, N, p(pos), p(rec), p(pos), p(rec), sp, C.byref(cfg()), o),
+        "osp_spgemm_coo": lambda dt, sp, M, K, N, n, o: (h, dt, M, K, N, 3, p(idx), p(idx), p(val), 3, p(idx), p(idx), p(val), sp,
+                                                         C.byref(cfg()), o),
+        "osp_spgemm_partials": lambda dt, sp, M, K, N, n, o: (h, dt, M, K, N, *csr, sp, C.byref(cfg()), o),
+        "osp_merge_csr_parts": lambda dt, sp, M, K, N, n, o: (h, dt, M, N, n, rps, cis, vas, sp, C.byref(cfg()), o),
+        "osp_merge_record_parts": lambda dt, sp, M, K, N, n, o: (h, dt, M, N, n, rps, recs, sp, C.byref(cfg()), o),
+    }
+    good = dict(dt=f64, sp=host, M=2, K=2, N=2, n=1)
+    cases = []
+    for name, make in product.items():
+        bad = [dict(dt=5), dict(sp=9), dict(M=big), dict(N=big)]
+        if name.startswith("osp_merge"):
+            bad.append(dict(n=0))
+        else:
+            bad.append(dict(K=big))
+        for b in bad:
+            a = dict(good, **b)
+            cases.append((name, b, lambda o, make=make, a=a: make(a["dt"], a["sp"], a["M"], a["K"], a["N"], a["n"], o)))
+    conv = lambda dt, sp: lambda o: (h, dt, 1, 1, 2, 2, 3, p(idx), p(idx), p(val), 2, 3, p(idx), p(idx), p(val), sp,   # noqa: E731
+                                     C.byref(geom), C.byref(cfg()), o)
+    im2col = lambda dt, sp: lambda o: (h, dt, 1, 1, 2, 2, 3, p(idx), p(idx), p(val), sp, C.byref(geom), 1, o, None, None,   # noqa: E731
+                                       None)
+    for dt, sp, what in ((5, host, "dtype"), (f64, 9, "space")):
+        cases.append(("osp_spgemm_conv2d", what, conv(dt, sp)))
+        cases.append(("osp_im2col_csc", what, im2col(dt, sp)))
+
+    # a partials result and a CSR result of the same product
+    part, res = C.c_void_p(), C.c_void_p()
+    _lib.check(L.osp_spgemm_partials(h, f64, 2, 2, 2, *csr, host, C.byref(cfg()), C.byref(part)))
+    _lib.check(L.osp_spgemm_csc_csr(h, f64, 2, 2, 2, *csr, host, C.byref(cfg()), C.byref(res)))
+    dev = ctx.alloc(64)
+    rowptr, colidx, vals = np.zeros(3, np.int64), np.zeros(8, np.uint32), np.zeros(8)
+    try:
+        cases += [
+            ("osp_csr_bias_relu", "partials", lambda o: (part, p(val), host, 1, o)),
+            ("osp_csr_bias_relu", "space", lambda o: (res, p(val), 9, 1, o)),
+            ("osp_csr_maxpool2d", "partials", lambda o: (part, 1, 2, 1, 1, 1, 1, 1, o)),
+            ("osp_result_coo_rows", "partials", lambda o: (part, C.c_void_p(dev))),
+            ("osp_result_copy_csr", "partials", lambda o: (part, p(rowptr), p(colidx), p(vals), host)),
+            ("osp_result_device_ptrs", "partials", lambda o: (part, o, o, o)),
+            ("osp_result_partials", "csr", lambda o: (res, o, o)),
+        ]
+        failed = []
+        for name, what, args in cases:
+            out = (C.c_uint64 if name == "osp_im2col_csc" else C.c_void_p)(sentinel)   # (*nnz_a, or a handle)
+            st = getattr(L, name)(*args(C.byref(out)))
+            if st != arg or out.value != sentinel:
+                failed.append((name, what, st, out.value, L.osp_last_error_string()))
+                if st == _lib.OSP_OK and out.value != sentinel and "result" not in name:
+                    L.osp_result_destroy(C.c_void_p(out.value))
+        # the panels entry reports through its info struct instead
+        for b in (dict(dt=5), dict(sp=9), dict(M=big), dict(K=big), dict(N=big)):
+            a = dict(good, **b)
+            info = _lib.ResultInfo()
+            info.M = sentinel
+            st = L.osp_spgemm_csc_csr_panels(h, a["dt"], a["M"], a["K"], a["N"], *csr, a["sp"], C.byref(cfg()), fn, None,
+                                             C.byref(info))
+            if st != arg or info.M != sentinel:
+                failed.append(("osp_spgemm_csc_csr_panels", b, st, info.M, L.osp_last_error_string()))
+        assert not failed, failed
+    finally:
+        L.osp_result_destroy(part)
+        L.osp_result_destroy(res)
+        ctx.free(dev)
+    # the context is as good as before
+    n, rows, cols, vals = gen.rmat_coo(8, 8, "g500", seed=3)
+    got, want = run_both(ctx, port, n, n, n, (rows, cols, vals), (rows, cols, vals), np.float64)
+    assert_same(got, want)
+    got.close()
+
+
 def test_mlp_layer_f32(ctx, golden_dir):
     """BASELINE configs[4] shape: act * W^T in f32 within 1e-5 of the reference."""
     from outerspace_amd import spgemm as S
