@@ -44,13 +44,14 @@
 extern "C" {
 #endif
 
-#define OSP_VERSION 6   /* round of the build: 3 = osp_multi_*, osp_csr_bias_relu, osp_result_coo_rows, direct-row counters;
+#define OSP_VERSION 7   /* round of the build: 3 = osp_multi_*, osp_csr_bias_relu, osp_result_coo_rows, direct-row counters;
                             4 = per-destination exchange streams (osp_multi_rank_info_t grew);
                             5 = osp_result_info_t grew (gathered_*, expand_*): since this version the two reference functions
                                 of osp_spgemm_csc_csr are ONE kernel for most rows -- the merge forms the partial products
                                 cscMulcsr would stage (same products, same order, same bits);
                             6 = osp_conv2d_geometry_t, osp_im2col_csc, osp_spgemm_conv2d, osp_csr_maxpool2d (no existing
-                                struct changed) */
+                                struct changed);
+                            7 = include/outerspace_spgemm_masked.h: osp_spgemm_masked (no existing struct changed) */
 
 typedef enum osp_status {
     OSP_OK = 0,

@@ -112,6 +112,9 @@ EXPORTS = [
     "osp_spgemm_csc_csr_multi", "osp_multi_result_info", "osp_multi_result_shard", "osp_multi_result_copy_csr", "osp_multi_result_destroy",
 ]
 
+# every symbol include/outerspace_spgemm_masked.h declares (kept apart from EXPORTS: that list pins outerspace_spgemm.h)
+MASKED_EXPORTS = ["osp_spgemm_masked"]
+
 _lib = None
 
 
@@ -188,6 +191,7 @@ def lib():
                                     C.POINTER(Config), C.POINTER(vp)]
     u32 = C.c_uint32
     L.osp_csr_maxpool2d.argtypes = [vp, u64, u64, u64, u32, u32, u32, u32, C.POINTER(vp)]
+    L.osp_spgemm_masked.argtypes = [vp, i32, u64, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(Config), C.POINTER(vp)]
     _lib = L
     return L
 

@@ -19,12 +19,14 @@
 #include <vector>
 
 #include "../../include/outerspace_spgemm.h"
+#include "../../include/outerspace_spgemm_masked.h"
 #include "osp_internal.h"
 #include "osp_kernels.h"
 #include "osp_split.h"
 #include "osp_sort.h"
 #include "osp_epilogue.h"
 #include "osp_conv.h"
+#include "osp_masked.h"
 
 namespace osp {
 
@@ -730,6 +732,172 @@ static void maxpool_impl(Context *ctx, const Result *in, Result *res, uint64_t N
     res->info.ms_total = ev.ms();
 }
 
+// ---- the masked product (osp_masked.h) ----
+// One operand in the other major order: (ptr, idx, vals) with nseg_minor segments -> (ptr_out over nseg_major segments,
+// the old segment index in ascending order inside each, vals).  One stable sort by the new major index: entries of one new
+// segment keep their input order, which is ascending in the old segment index.
+template <class T>
+static void masked_view(Context *ctx, Scratch &sc, uint64_t nseg_minor, uint64_t nseg_major, uint64_t nnz, const int64_t *ptr,
+                        const uint32_t *idx, const T *vals, int64_t **ptr_out, uint32_t **idx_out, T **vals_out) {
+    hipStream_t s = ctx->stream;
+    int64_t *optr = sc.get<int64_t>(nseg_major + 1);
+    uint32_t *oidx = sc.get<uint32_t>(nnz);
+    T *ovals = sc.get<T>(nnz);
+    *ptr_out = optr; *idx_out = oidx; *vals_out = ovals;
+    if (nnz == 0) {
+        OSP_HIP(hipMemsetAsync(optr, 0, (nseg_major + 1) * sizeof(int64_t), s));
+        return;
+    }
+    Scratch ss(ctx);
+    uint32_t *minor = ss.get<uint32_t>(nnz), *major = ss.get<uint32_t>(nnz);
+    uint32_t *ka = ss.get<uint32_t>(nnz), *pa = ss.get<uint32_t>(nnz), *kb = ss.get<uint32_t>(nnz), *pb = ss.get<uint32_t>(nnz);
+    uint32_t *hist = ss.get<uint32_t>(rs_hist_entries(nnz));
+    uint32_t *hist_tmp = ss.get<uint32_t>(scan_scratch_entries(rs_hist_entries(nnz)));
+    if (nseg_minor) csr_expand_rows_kernel<<<grid_for(nseg_minor * kWave, 256), 256, 0, s>>>(ptr, nseg_minor, minor);
+    device_sort_rows<MaskedViewEpilogue<T>>(idx, nnz, std::max(1, bits_for(nseg_major)), ka, pa, kb, pb, hist, hist_tmp,
+                                            MaskedViewEpilogue<T>{minor, vals, major, oidx, ovals}, s, ctx->rank_atomic);
+    ingest_ptr_kernel<<<grid_for(nseg_major + 1, 256), 256, 0, s>>>(major, nnz, nseg_major, optr);
+    OSP_HIP(hipStreamSynchronize(s));   // (ss goes back to the pool)
+}
+
+// unsigned setting from the environment, or `dflt`
+static uint64_t env_u64(const char *name, uint64_t dflt) {
+    const char *v = getenv(name);
+    return v && *v ? strtoull(v, nullptr, 10) : dflt;
+}
+
+template <class T>
+static void masked_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint64_t N, const int64_t *a_colptr_in, const uint32_t *a_rowidx_in,
+                        const T *a_vals_in, const int64_t *b_rowptr_in, const uint32_t *b_colidx_in, const T *b_vals_in,
+                        const int64_t *m_rowptr_in, const uint32_t *m_colidx_in, osp_memspace_t space, const osp_config_t &cfg) {
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev, ev_in, ev_k;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    res->info = osp_result_info_t{};   // every field the masked product does not name stays 0 (rank_atomic included)
+    res->info.dtype = res->dtype;
+    res->info.M = M; res->info.K = K; res->info.N = N;
+    res->info.row_begin = 0; res->info.row_end = M;
+
+    const int64_t *a_colptr = to_device(sc, a_colptr_in, K + 1, space, s);
+    const int64_t *b_rowptr = to_device(sc, b_rowptr_in, K + 1, space, s);
+    const int64_t *m_rowptr = to_device(sc, m_rowptr_in, M + 1, space, s);
+    int64_t nnz_a, nnz_b, nnz_m;
+    if (space == OSP_HOST) {
+        nnz_a = a_colptr_in[K]; nnz_b = b_rowptr_in[K]; nnz_m = m_rowptr_in[M];
+    } else {
+        Gather g(s);
+        g.add(&nnz_a, a_colptr + K); g.add(&nnz_b, b_rowptr + K); g.add(&nnz_m, m_rowptr + M);
+        g.wait();
+    }
+    if (nnz_a < 0 || nnz_b < 0 || nnz_m < 0) throw Error(OSP_ERR_ARG, "negative nnz in pointer array");
+    if ((uint64_t)nnz_a >= 0xffffffffull || (uint64_t)nnz_b >= 0xffffffffull || (uint64_t)nnz_m >= 0xffffffffull)
+        throw Error(OSP_ERR_ARG, "operands or masks with >= 2^32 non-zeros are not supported");
+    if (nnz_m && !m_colidx_in) throw Error(OSP_ERR_ARG, "null mask column array with a non-empty mask");
+    const uint32_t *a_rowidx = to_device(sc, a_rowidx_in, nnz_a, space, s);
+    const T *a_vals = to_device(sc, a_vals_in, nnz_a, space, s);
+    const uint32_t *b_colidx = to_device(sc, b_colidx_in, nnz_b, space, s);
+    const T *b_vals = to_device(sc, b_vals_in, nnz_b, space, s);
+    const uint32_t *m_colidx = to_device(sc, m_colidx_in, nnz_m, space, s);
+    res->info.nnz_a = nnz_a;
+    res->info.nnz_b = nnz_b;
+
+    if (cfg.validate) {
+        uint32_t *flags = sc.get<uint32_t>(3);
+        OSP_HIP(hipMemsetAsync(flags, 0, 3 * sizeof(uint32_t), s));
+        validate_ptr_kernel<<<grid_for(K + 1, 256), 256, 0, s>>>(a_colptr, K, nnz_a, flags);
+        validate_ptr_kernel<<<grid_for(K + 1, 256), 256, 0, s>>>(b_rowptr, K, nnz_b, flags + 1);
+        validate_ptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(m_rowptr, M, nnz_m, flags + 2);
+        uint32_t f[3] = {0, 0, 0};
+        { Gather g(s); for (int q = 0; q < 3; q++) g.add(&f[q], (const uint32_t *)flags + q); g.wait(); }
+        check_flags(f[0], "A (CSC)");
+        check_flags(f[1], "B (CSR)");
+        check_flags(f[2], "mask (CSR)");
+        if (nnz_a) validate_idx_kernel<<<grid_for(nnz_a, 256), 256, 0, s>>>(a_colptr, a_rowidx, K, nnz_a, M, flags);
+        if (nnz_b) validate_idx_kernel<<<grid_for(nnz_b, 256), 256, 0, s>>>(b_rowptr, b_colidx, K, nnz_b, N, flags + 1);
+        if (nnz_m) validate_idx_kernel<<<grid_for(nnz_m, 256), 256, 0, s>>>(m_rowptr, m_colidx, M, nnz_m, N, flags + 2);
+        { Gather g(s); for (int q = 0; q < 3; q++) g.add(&f[q], (const uint32_t *)flags + q); g.wait(); }
+        check_flags(f[0], "A (CSC)");
+        check_flags(f[1], "B (CSR)");
+        check_flags(f[2], "mask (CSR)");
+    }
+
+    // ---- views: A by rows, B by columns ----
+    OSP_HIP(hipEventRecord(ev_in.a, s));
+    int64_t *arow_ptr, *bcol_ptr;
+    uint32_t *arow_k, *bcol_k;
+    T *arow_v, *bcol_v;
+    masked_view<T>(ctx, sc, K, M, nnz_a, a_colptr, a_rowidx, a_vals, &arow_ptr, &arow_k, &arow_v);
+    masked_view<T>(ctx, sc, K, N, nnz_b, b_rowptr, b_colidx, b_vals, &bcol_ptr, &bcol_k, &bcol_v);
+    OSP_HIP(hipEventRecord(ev_in.b, s));
+
+    // ---- slots: classify, order light slots by cost bucket, intersect ----
+    const uint64_t nm = (uint64_t)nnz_m;
+    uint32_t *m_row = sc.get<uint32_t>(nm), *hit = sc.get<uint32_t>(nm);
+    T *val = sc.get<T>(nm);
+    unsigned long long *products = (unsigned long long *)sc.get<uint64_t>(1);
+    uint32_t *count = sc.get<uint32_t>(kMaskedBuckets);
+    zero_async(s, {{products, sizeof(uint64_t)}, {count, kMaskedBuckets * sizeof(uint32_t)}});
+    uint32_t launches = 0;
+    if (nm) {
+        const uint32_t heavy_min = (uint32_t)std::min<uint64_t>(env_u64("OSP_MASKED_HEAVY_MIN", kMaskedHeavyMin), 0xffffffffull);
+        const int bucketed = env_u64("OSP_MASKED_BUCKET", 1) ? 1 : 0;
+        Scratch ss(ctx);
+        uint32_t *key = ss.get<uint32_t>(nm), *order = ss.get<uint32_t>(nm);
+        csr_expand_rows_kernel<<<grid_for(M * kWave, 256), 256, 0, s>>>(m_rowptr, M, m_row);
+        masked_classify_kernel<<<grid_for(nm, 256), 256, 0, s>>>(m_row, m_colidx, arow_ptr, bcol_ptr, nm, heavy_min, bucketed, key, hit, count);
+        uint32_t hc[kMaskedBuckets];
+        copy_d2h(hc, count, sizeof(hc), s);
+        const uint64_t n_empty = hc[kMaskedEmpty], n_heavy = hc[kMaskedHeavy], n_light = nm - n_empty - n_heavy;
+        if (n_light || n_heavy) {
+            uint32_t *ka = ss.get<uint32_t>(nm), *pa = ss.get<uint32_t>(nm), *kb = ss.get<uint32_t>(nm), *pb = ss.get<uint32_t>(nm);
+            uint32_t *hist = ss.get<uint32_t>(rs_hist_entries(nm));
+            uint32_t *hist_tmp = ss.get<uint32_t>(scan_scratch_entries(rs_hist_entries(nm)));
+            device_sort_rows<MaskedOrderEpilogue>(key, nm, 5, ka, pa, kb, pb, hist, hist_tmp, MaskedOrderEpilogue{order}, s, ctx->rank_atomic);
+        }
+        const MaskedOperands op{m_row, m_colidx, arow_ptr, arow_k, bcol_ptr, bcol_k};
+        OSP_HIP(hipEventRecord(ev_k.a, s));
+        if (n_light) {
+            masked_light_kernel<T><<<grid_for(n_light, 256), 256, 0, s>>>(op, arow_v, bcol_v, order + n_empty, n_light, hit, val, products);
+            launches++;
+        }
+        if (n_heavy) {
+            masked_heavy_kernel<T><<<(unsigned)n_heavy, kWave, 0, s>>>(op, arow_v, bcol_v, order + n_empty + n_light, n_heavy, hit, val, products);
+            launches++;
+        }
+        OSP_HIP(hipEventRecord(ev_k.b, s));
+        OSP_HIP(hipStreamSynchronize(s));   // (ss goes back to the pool)
+    } else {
+        OSP_HIP(hipEventRecord(ev_k.a, s));
+        OSP_HIP(hipEventRecord(ev_k.b, s));
+    }
+
+    // ---- compaction: C at its exact size ----
+    uint64_t *pos = sc.get<uint64_t>(nm + 1);
+    uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(nm + 1));
+    device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{hit}, nm, pos, tmp, s);
+    uint64_t nnz_c = 0, P = 0;
+    { Gather g(s); g.add(&nnz_c, (const uint64_t *)pos + nm); g.add(&P, (const uint64_t *)products); g.wait(); }
+    res->rowptr = (int64_t *)ctx->alloc((M + 1) * sizeof(int64_t));
+    res->colidx = (uint32_t *)ctx->alloc(std::max<uint64_t>(nnz_c, 1) * sizeof(uint32_t));
+    res->vals = ctx->alloc(std::max<uint64_t>(nnz_c, 1) * sizeof(T));
+    masked_rowptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(m_rowptr, pos, M, res->rowptr);
+    if (nnz_c) masked_scatter_kernel<T><<<grid_for(nm, 256), 256, 0, s>>>(hit, val, m_colidx, pos, nm, res->colidx, (T *)res->vals);
+    OSP_HIP(hipEventRecord(ev.b, s));
+    OSP_HIP(hipStreamSynchronize(s));
+    OSP_HIP(hipGetLastError());
+    res->info.nnz_c = nnz_c;
+    res->info.partials = P;
+    res->info.ms_total = ev.ms();
+    res->info.ms_ingest = ev_in.ms();
+    res->info.ms_multiply_kernel = ev_k.ms();
+    res->info.multiply_launches = launches;
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] masked M=%llu K=%llu N=%llu nnzA=%lld nnzB=%lld nnzM=%lld nnzC=%llu products=%llu launches=%u %.3f ms\n",
+                (unsigned long long)M, (unsigned long long)K, (unsigned long long)N, (long long)nnz_a, (long long)nnz_b, (long long)nnz_m,
+                (unsigned long long)nnz_c, (unsigned long long)P, launches, res->info.ms_total);
+}
+
 static void destroy_result(Result *r) {
     if (!r) return;
     if (r->ctx) {
@@ -935,7 +1103,27 @@ int osp_spgemm_csc_csr(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint64
     });
 }
 
-int osp_spgemm_csc_csr_aos(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint64_t K, uint64_t N, const uint64_t *a_pos,
+int osp_spgemm_masked(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint64_t K, uint64_t N, const int64_t *a_colptr,
+                      const uint32_t *a_rowidx, const void *a_vals, const int64_t *b_rowptr, const uint32_t *b_colidx, const void *b_vals,
+                      const int64_t *m_rowptr, const uint32_t *m_colidx, osp_memspace_t space, const osp_config_t *cfg_,
+                      osp_result_t *result) {
+    Context *ctx = (Context *)ctx_;
+    if (!ctx || !result) return fail(OSP_ERR_ARG, "null context or result pointer");
+    if (!a_colptr || !b_rowptr || !m_rowptr) return fail(OSP_ERR_ARG, "null pointer array");
+    return guard([&] {
+        check_dtype(dtype); check_space(space); check_dims(M, K, N);
+        const osp_config_t cfg = config_or_default(cfg_);
+        if (cfg.k_begin != 0 || cfg.k_end != 0) throw Error(OSP_ERR_ARG, "masked product: k_begin / k_end must be 0 / 0");
+        if (cfg.row_shard_count > 1) throw Error(OSP_ERR_ARG, "masked product: row shards are not supported");
+        return new_result(ctx, dtype, result, [&](auto tag, Result *res) {
+            using T = decltype(tag);
+            masked_impl<T>(ctx, res, M, K, N, a_colptr, a_rowidx, (const T *)a_vals, b_rowptr, b_colidx, (const T *)b_vals, m_rowptr,
+                           m_colidx, space, cfg);
+        });
+    });
+}
+
+int osp_spgemm_csc_csr_aos(osp_context_t ctx_,osp_dtype_t dtype, uint64_t M, uint64_t K, uint64_t N, const uint64_t *a_pos,
                            const void *a_data, const uint64_t *b_pos, const void *b_data, osp_memspace_t space,
                            const osp_config_t *cfg_, osp_result_t *result) {
     Context *ctx = (Context *)ctx_;

@@ -307,6 +307,37 @@ class Context:
                                                  C.byref(cfg), C.byref(h)))
         return CsrResult(self, h)
 
+    def spgemm_masked(self, M, K, N, a_colptr, a_rowidx, a_vals, b_rowptr, b_colidx, b_vals, m_rowptr, m_colidx, *, validate=True):
+        """C<mask> = A(CSC) * B(CSR) with numpy (host) operands (``osp_spgemm_masked``): the entries of the product at the
+        mask's pattern (M x N, CSR, no values) where at least one product exists, the same bits as the unmasked product
+        there.  ``result.info['partials']`` is the number of products formed."""
+        dt = np.dtype(a_vals.dtype)
+        if dt not in _DT or np.dtype(b_vals.dtype) != dt:
+            raise TypeError("values must both be float32 or both float64")
+        arrs = [np.ascontiguousarray(a_colptr, np.int64), np.ascontiguousarray(a_rowidx, np.uint32),
+                np.ascontiguousarray(a_vals, dt), np.ascontiguousarray(b_rowptr, np.int64),
+                np.ascontiguousarray(b_colidx, np.uint32), np.ascontiguousarray(b_vals, dt),
+                np.ascontiguousarray(m_rowptr, np.int64), np.ascontiguousarray(m_colidx, np.uint32)]
+        if len(arrs[0]) != K + 1 or len(arrs[3]) != K + 1:
+            raise OspError(_lib.ERR_DIM, f"pointer arrays must have K+1={K + 1} entries "
+                                         f"(got {len(arrs[0])} and {len(arrs[3])})")
+        if len(arrs[6]) != M + 1:
+            raise OspError(_lib.ERR_ARG, f"the mask's row pointers must have M+1={M + 1} entries (got {len(arrs[6])})")
+        cfg = self._config(validate, 0, None)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_spgemm_masked(self._h, _DT[dt], M, K, N, *[_ptr(a) for a in arrs[:6]],
+                                                C.c_void_p(arrs[6].ctypes.data), _ptr(arrs[7]), _lib.OSP_HOST, C.byref(cfg), C.byref(h)))
+        return CsrResult(self, h)
+
+    def spgemm_masked_device(self, dtype, M, K, N, ptrs, mask_ptrs, *, validate=False):
+        """Same with DEVICE addresses (ints): ``ptrs`` as in ``spgemm_csc_csr_device``, ``mask_ptrs`` = (m_rowptr, m_colidx).
+        The arrays must be complete when this is called (see ``spgemm_csc_csr_device``)."""
+        cfg = self._config(validate, 0, None)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_spgemm_masked(self._h, _DT[np.dtype(dtype)], M, K, N, *[C.c_void_p(int(p)) for p in ptrs],
+                                                *[C.c_void_p(int(p)) for p in mask_ptrs], _lib.OSP_DEVICE, C.byref(cfg), C.byref(h)))
+        return CsrResult(self, h)
+
     def spgemm_partials_device(self, dtype, M, K, N, ptrs, *, k_range=None):
         """The multiply phase alone (``osp_spgemm_partials``): the product's partial products, unmerged, as packed records
         grouped by output row.  ``ptrs`` = six DEVICE addresses as in ``spgemm_csc_csr_device``.  ``result.nnz`` = P;
@@ -573,4 +604,30 @@ def spgemm(A, B, transpose_b=True, ctx=None, dtype=None):
     with_res = ctx.spgemm_csc_csr(M, K, bc_n, *a, *b)
     out = with_res.to_scipy()
     with_res.close()
+    return out
+
+
+def spgemm_masked(A, B, mask, transpose_b=True, ctx=None, dtype=None):
+    """``(A @ B.T)`` (default, as ``spgemm``) or ``A @ B``, computed only at the pattern of ``mask`` (its values are not
+    read), as scipy CSR.  An entry of the mask where no product exists is absent from the result; an entry whose products
+    cancel is kept as an explicit 0."""
+    ctx = ctx or default_context()
+    M, K, ar, ac, av = _as_coo(A)
+    br_n, bc_n, br, bc, bv = _as_coo(B)
+    if transpose_b:
+        br_n, bc_n, br, bc = bc_n, br_n, bc, br
+    if br_n != K:
+        raise OspError(_lib.ERR_DIM, f"inner dimensions differ: A is {M}x{K}, B is {br_n}x{bc_n}")
+    mm, mn, mr, mc, _ = _as_coo(mask)
+    if (mm, mn) != (M, bc_n):
+        raise OspError(_lib.ERR_ARG, f"the mask is {mm}x{mn}, the product {M}x{bc_n}")
+    dt = np.dtype(dtype or np.result_type(av.dtype, bv.dtype))
+    if dt not in _DT:
+        dt = np.dtype(np.float64)
+    a = coo_to_csc(K, ar, ac, av.astype(dt))
+    b = coo_to_csr(K, br, bc, bv.astype(dt))
+    m_rowptr, m_colidx, _ = coo_to_csr(M, mr, mc, np.zeros(len(mr), np.float32))
+    res = ctx.spgemm_masked(M, K, bc_n, *a, *b, m_rowptr, m_colidx)
+    out = res.to_scipy()
+    res.close()
     return out
