@@ -71,6 +71,21 @@ class Conv2dGeometry(C.Structure):
                 ("reserved", C.c_uint32 * 8)]
 
 
+class MclStep(C.Structure):
+    """osp_mcl_step_t"""
+    _fields_ = [("power", C.c_double), ("threshold", C.c_double), ("max_per_row", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class MclStats(C.Structure):
+    """osp_mcl_stats_t"""
+    _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("rows_capped", C.c_uint64), ("rows_rescued", C.c_uint64),
+                ("rows_long", C.c_uint64), ("chaos", C.c_double), ("ms_total", C.c_float), ("ms_select_kernel", C.c_float),
+                ("launches", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -114,6 +129,9 @@ EXPORTS = [
 
 # every symbol include/outerspace_spgemm_masked.h declares (kept apart from EXPORTS: that list pins outerspace_spgemm.h)
 MASKED_EXPORTS = ["osp_spgemm_masked"]
+
+# every symbol include/outerspace_spgemm_mcl.h declares
+MCL_EXPORTS = ["osp_csr_inflate_prune"]
 
 _lib = None
 
@@ -192,6 +210,7 @@ def lib():
     u32 = C.c_uint32
     L.osp_csr_maxpool2d.argtypes = [vp, u64, u64, u64, u32, u32, u32, u32, C.POINTER(vp)]
     L.osp_spgemm_masked.argtypes = [vp, i32, u64, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(Config), C.POINTER(vp)]
+    L.osp_csr_inflate_prune.argtypes = [vp, C.POINTER(MclStep), i32, C.POINTER(vp), C.POINTER(MclStats)]
     _lib = L
     return L
 

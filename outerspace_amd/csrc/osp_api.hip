@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +21,7 @@
 
 #include "../../include/outerspace_spgemm.h"
 #include "../../include/outerspace_spgemm_masked.h"
+#include "../../include/outerspace_spgemm_mcl.h"
 #include "osp_internal.h"
 #include "osp_kernels.h"
 #include "osp_split.h"
@@ -27,6 +29,7 @@
 #include "osp_epilogue.h"
 #include "osp_conv.h"
 #include "osp_masked.h"
+#include "osp_mcl.h"
 
 namespace osp {
 
@@ -898,6 +901,109 @@ static void masked_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
                 (unsigned long long)nnz_c, (unsigned long long)P, launches, res->info.ms_total);
 }
 
+// ---- the step between two expansions of Markov clustering (osp_mcl.h) ----
+template <class T>
+static void inflate_prune_impl(Context *ctx, const Result *in, Result *res, const osp_mcl_step_t &step, int validate, osp_mcl_stats_t *st) {
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev, ev_k;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint64_t M = in->info.M, nnz_in = in->info.nnz_c;
+    const T *val = (const T *)in->vals;
+    const T thr = (T)step.threshold, power = (T)step.power;
+    const int mode = step.power == 1.0 ? MCL_POW_ONE : step.power == 2.0 ? MCL_POW_SQUARE : MCL_POW_GENERAL;
+    const uint32_t long_min = (uint32_t)std::min<uint64_t>(env_u64("OSP_MCL_LONG_MIN", kMclLongMin), 0xffffffffull);
+    uint32_t launches = 0;
+
+    unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MCL_COUNTERS);
+    zero_async(s, {{counters, MCL_COUNTERS * sizeof(uint64_t)}});
+    if (validate && nnz_in) {
+        mcl_validate_kernel<T><<<grid_for(nnz_in, 256), 256, 0, s>>>(val, nnz_in, counters);
+        launches++;
+        if (d2h((const uint64_t *)counters + MCL_INVALID, s)) throw Error(OSP_ERR_ARG, "inflate_prune: a value is negative, NaN or infinite");
+    }
+
+    // ---- classes: rows longer than long_min get a workgroup each ----
+    uint32_t *long_rows = sc.get<uint32_t>(nnz_in / ((uint64_t)long_min + 1) + 1);
+    if (M) {
+        mcl_classify_kernel<<<grid_for(M, 256), 256, 0, s>>>(in->rowptr, M, long_min, long_rows, counters);
+        launches++;
+    }
+    const uint64_t n_long = d2h((const uint64_t *)counters + MCL_NLONG, s);
+
+    // ---- pass 1: kept entries per row, then the output's row pointers ----
+    res->info = in->info;
+    res->rowptr = (int64_t *)ctx->alloc((M + 1) * sizeof(int64_t));
+    uint32_t *cnt = sc.get<uint32_t>(M + 1), *nsurv = sc.get<uint32_t>(M + 1);
+    uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(M + 1));
+    constexpr uint64_t kSlice = 1ull << 30;   // rows per launch of the one-wave-per-row kernels (grid limit)
+    for (uint64_t r0 = 0; r0 < M; r0 += kSlice) {
+        mcl_count_kernel<T, kWave><<<(unsigned)std::min(kSlice, M - r0), kWave, 0, s>>>(in->rowptr, val, r0, M, nullptr, long_min, thr, step.max_per_row,
+                                                                                      nsurv, cnt, counters);
+        launches++;
+    }
+    if (n_long) {
+        mcl_count_kernel<T, kMclLongThreads><<<(unsigned)n_long, kMclLongThreads, 0, s>>>(in->rowptr, val, 0, M, long_rows, long_min, thr,
+                                                                                          step.max_per_row, nsurv, cnt, counters);
+        launches++;
+    }
+    device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{cnt}, M, (uint64_t *)res->rowptr, tmp, s);
+    const uint64_t nnz = (uint64_t)d2h(res->rowptr + M, s);
+    res->colidx = (uint32_t *)ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(uint32_t));
+    res->vals = ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(T));
+
+    // ---- pass 2: select, compact, inflate, normalise ----
+    OSP_HIP(hipEventRecord(ev_k.a, s));
+    if (nnz) {
+        for (uint64_t r0 = 0; r0 < M; r0 += kSlice) {
+            mcl_write_kernel<T, kWave><<<(unsigned)std::min(kSlice, M - r0), kWave, 0, s>>>(in->rowptr, in->colidx, val, r0, M, nullptr, long_min, thr, mode,
+                                                                                          power, nsurv, res->rowptr, res->colidx, (T *)res->vals, counters);
+            launches++;
+        }
+        if (n_long) {
+            mcl_write_kernel<T, kMclLongThreads><<<(unsigned)n_long, kMclLongThreads, 0, s>>>(in->rowptr, in->colidx, val, 0, M, long_rows, long_min, thr,
+                                                                                              mode, power, nsurv, res->rowptr, res->colidx,
+                                                                                              (T *)res->vals, counters);
+            launches++;
+        }
+    }
+    OSP_HIP(hipEventRecord(ev_k.b, s));
+    uint64_t capped = 0, rescued = 0, chaos_bits = 0;
+    {
+        Gather g(s);
+        g.add(&capped, (const uint64_t *)counters + MCL_CAPPED);
+        g.add(&rescued, (const uint64_t *)counters + MCL_RESCUED);
+        g.add(&chaos_bits, (const uint64_t *)counters + MCL_CHAOS);
+        g.wait();
+    }
+    OSP_HIP(hipEventRecord(ev.b, s));
+    OSP_HIP(hipStreamSynchronize(s));
+    OSP_HIP(hipGetLastError());
+    res->info.nnz_c = nnz;
+    res->info.ms_total = ev.ms();
+    *st = osp_mcl_stats_t{};
+    st->nnz_in = nnz_in;
+    st->nnz_out = nnz;
+    st->rows_capped = capped;
+    st->rows_rescued = rescued;
+    st->rows_long = n_long;
+    if (sizeof(T) == 8) {
+        memcpy(&st->chaos, &chaos_bits, 8);
+    } else {
+        const uint32_t b32 = (uint32_t)chaos_bits;
+        float f;
+        memcpy(&f, &b32, 4);
+        st->chaos = (double)f;
+    }
+    st->ms_total = res->info.ms_total;
+    st->ms_select_kernel = ev_k.ms();
+    st->launches = launches + 1;   // (the counters' zeroing)
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] inflate_prune M=%llu nnz %llu -> %llu capped=%llu rescued=%llu long=%llu chaos=%.3e %.3f ms (select %.3f)\n",
+                (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)nnz, (unsigned long long)capped, (unsigned long long)rescued,
+                (unsigned long long)n_long, st->chaos, st->ms_total, st->ms_select_kernel);
+}
+
 static void destroy_result(Result *r) {
     if (!r) return;
     if (r->ctx) {
@@ -1120,6 +1226,24 @@ int osp_spgemm_masked(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint64_
             masked_impl<T>(ctx, res, M, K, N, a_colptr, a_rowidx, (const T *)a_vals, b_rowptr, b_colidx, (const T *)b_vals, m_rowptr,
                            m_colidx, space, cfg);
         });
+    });
+}
+
+int osp_csr_inflate_prune(osp_result_t in_, const osp_mcl_step_t *step, int validate, osp_result_t *out, osp_mcl_stats_t *stats) {
+    Result *in = (Result *)in_;
+    if (!in || !step || !out) return fail(OSP_ERR_ARG, "null argument");
+    if (in->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
+    return guard([&] {
+        if (!(step->power >= 1.0) || !(step->power < HUGE_VAL)) throw Error(OSP_ERR_ARG, "inflate_prune: power must be a finite number >= 1");
+        if (!(step->threshold >= 0.0) || !(step->threshold < HUGE_VAL)) throw Error(OSP_ERR_ARG, "inflate_prune: threshold must be a finite number >= 0");
+        for (uint32_t w : step->reserved)
+            if (w) throw Error(OSP_ERR_ARG, "inflate_prune: reserved words must be 0");
+        osp_mcl_stats_t st{};
+        const int rc = new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {
+            inflate_prune_impl<decltype(tag)>(in->ctx, in, res, *step, validate, &st);
+        });
+        if (stats) *stats = st;
+        return rc;
     });
 }
 

@@ -110,6 +110,19 @@ class CsrResult:
         _lib.check(_lib.lib().osp_csr_maxpool2d(self._h, int(N), int(H), int(W), kh, kw, sh, sw, C.byref(h)))
         return CsrResult(self._ctx, h)
 
+    def inflate_prune(self, power=2.0, threshold=0.0, max_per_row=0, validate=False):
+        """One Markov-clustering step on this CSR, row by row, as a new CSR result on the device
+        (``osp_csr_inflate_prune``): keep the entries ``>= threshold`` (a row that keeps nothing keeps its largest), of
+        those at most the ``max_per_row`` largest (0: no cap; ties to the lower column), raise them to ``power`` and
+        divide by the row's sum.  Returns (result, stats dict): nnz_in, nnz_out, rows_capped, rows_rescued, rows_long,
+        chaos, ms_total, ms_select_kernel, launches.  validate=True refuses negative, NaN and infinite values."""
+        step = _lib.MclStep()
+        step.power, step.threshold, step.max_per_row = float(power), float(threshold), int(max_per_row)
+        stats = _lib.MclStats()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_csr_inflate_prune(self._h, C.byref(step), int(bool(validate)), C.byref(h), C.byref(stats)))
+        return CsrResult(self._ctx, h), stats.as_dict()
+
     def coo_rows_into(self, rows_device_ptr):
         """Row index of every entry into caller-owned DEVICE memory (nnz u32 values): with ``device_ptrs()[1:]`` the COO
         form ``Context.spgemm_coo_device`` takes (``osp_result_coo_rows``)."""
