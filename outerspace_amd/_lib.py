@@ -86,6 +86,15 @@ class MclStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class ApplyMaskStats(C.Structure):
+    """osp_apply_mask_stats_t"""
+    _fields_ = [("nnz_in", C.c_uint64), ("nnz_mask", C.c_uint64), ("nnz_out", C.c_uint64), ("ms_total", C.c_float),
+                ("launches", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -132,6 +141,9 @@ MASKED_EXPORTS = ["osp_spgemm_masked"]
 
 # every symbol include/outerspace_spgemm_mcl.h declares
 MCL_EXPORTS = ["osp_csr_inflate_prune"]
+
+# every symbol include/outerspace_spgemm_apply_mask.h declares
+APPLY_MASK_EXPORTS = ["osp_csr_apply_mask"]
 
 _lib = None
 
@@ -211,6 +223,7 @@ def lib():
     L.osp_csr_maxpool2d.argtypes = [vp, u64, u64, u64, u32, u32, u32, u32, C.POINTER(vp)]
     L.osp_spgemm_masked.argtypes = [vp, i32, u64, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(Config), C.POINTER(vp)]
     L.osp_csr_inflate_prune.argtypes = [vp, C.POINTER(MclStep), i32, C.POINTER(vp), C.POINTER(MclStats)]
+    L.osp_csr_apply_mask.argtypes = [vp, u64, u64, vp, vp, i32, i32, i32, C.POINTER(vp), C.POINTER(ApplyMaskStats)]
     _lib = L
     return L
 

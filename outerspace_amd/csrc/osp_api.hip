@@ -22,6 +22,7 @@
 #include "../../include/outerspace_spgemm.h"
 #include "../../include/outerspace_spgemm_masked.h"
 #include "../../include/outerspace_spgemm_mcl.h"
+#include "../../include/outerspace_spgemm_apply_mask.h"
 #include "osp_internal.h"
 #include "osp_kernels.h"
 #include "osp_split.h"
@@ -30,6 +31,7 @@
 #include "osp_conv.h"
 #include "osp_masked.h"
 #include "osp_mcl.h"
+#include "osp_apply_mask.h"
 
 namespace osp {
 
@@ -1004,6 +1006,106 @@ static void inflate_prune_impl(Context *ctx, const Result *in, Result *res, cons
                 (unsigned long long)n_long, st->chaos, st->ms_total, st->ms_select_kernel);
 }
 
+// ---- the mask filter C<M> / C<¬M> of a CSR result (osp_apply_mask.h) ----
+template <class T>
+static void apply_mask_impl(Context *ctx, const Result *in, Result *res, const int64_t *m_rowptr_in, const uint32_t *m_colidx_in,
+                            osp_memspace_t space, int complement, int validate, osp_apply_mask_stats_t *st) {
+    typedef typename std::conditional<sizeof(T) == 8, uint64_t, uint32_t>::type V;
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint64_t M = in->info.M, N = in->info.N, nnz_in = in->info.nnz_c;
+    uint32_t launches = 0;
+
+    // ---- the mask; a device mask's nnz comes back with nnz_out unless something needs it earlier ----
+    const int64_t *m_rowptr = to_device(sc, m_rowptr_in, M + 1, space, s);
+    int64_t nnz_m = 0;
+    bool have_nnz_m = space == OSP_HOST;
+    if (have_nnz_m) nnz_m = m_rowptr_in[M];
+    const auto check_nnz_m = [&] {
+        if (nnz_m < 0) throw Error(OSP_ERR_ARG, "apply_mask: negative nnz in the mask's pointer array");
+        if ((uint64_t)nnz_m >= 0xffffffffull) throw Error(OSP_ERR_ARG, "apply_mask: masks with >= 2^32 non-zeros are not supported");
+        if (nnz_m && !m_colidx_in) throw Error(OSP_ERR_ARG, "apply_mask: null mask column array with a non-empty mask");
+    };
+    if (!have_nnz_m && (!m_colidx_in || validate || nnz_in == 0)) {
+        nnz_m = d2h(m_rowptr + M, s);
+        have_nnz_m = true;
+    }
+    if (have_nnz_m) check_nnz_m();
+    const uint32_t *m_colidx = space == OSP_HOST ? to_device(sc, m_colidx_in, (uint64_t)nnz_m, space, s) : m_colidx_in;
+
+    if (validate) {
+        uint32_t *flags = sc.get<uint32_t>(1);
+        zero_async(s, {{flags, sizeof(uint32_t)}});
+        validate_ptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(m_rowptr, M, (uint64_t)nnz_m, flags);
+        launches += 2;
+        check_flags(d2h((const uint32_t *)flags, s), "mask (CSR)");
+        if (nnz_m) {
+            validate_idx_kernel<<<grid_for((uint64_t)nnz_m, 256), 256, 0, s>>>(m_rowptr, m_colidx, M, (uint64_t)nnz_m, N, flags);
+            launches++;
+            check_flags(d2h((const uint32_t *)flags, s), "mask (CSR)");
+        }
+    }
+
+    res->info = in->info;
+    res->rowptr = (int64_t *)ctx->alloc((M + 1) * sizeof(int64_t));
+    uint64_t nnz = 0;
+    if (nnz_in == 0 || (have_nnz_m && nnz_m == 0)) {
+        // nothing to search: the result is empty, or (nothing is masked out) `in` itself
+        if (nnz_in && complement) {
+            nnz = nnz_in;
+            OSP_HIP(hipMemcpyAsync(res->rowptr, in->rowptr, (M + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        } else {
+            OSP_HIP(hipMemsetAsync(res->rowptr, 0, (M + 1) * sizeof(int64_t), s));
+        }
+        res->colidx = (uint32_t *)ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(uint32_t));
+        res->vals = ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(T));
+        if (nnz) {
+            OSP_HIP(hipMemcpyAsync(res->colidx, in->colidx, nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+            OSP_HIP(hipMemcpyAsync(res->vals, in->vals, nnz * sizeof(T), hipMemcpyDeviceToDevice, s));
+        }
+    } else {
+        const uint64_t nwords = (nnz_in + 63) / 64;
+        uint64_t *bits = sc.get<uint64_t>(nwords), *pos = sc.get<uint64_t>(nwords + 1);
+        uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(nwords));
+        const unsigned nchunks = grid_for(nnz_in, (unsigned)kAmChunk);
+        apply_mask_flag_kernel<<<nchunks, kAmThreads, 0, s>>>(in->rowptr, in->colidx, M, nnz_in, m_rowptr, m_colidx, complement, bits);
+        device_exclusive_scan<LoadPopc64, uint64_t>(LoadPopc64{bits}, nwords, pos, tmp, s);
+        launches += 1 + ((nwords + kScanTile - 1) / kScanTile <= kScanSmallTiles ? 1 : 3);
+        {   // the call's one read-back
+            Gather g(s);
+            g.add(&nnz, (const uint64_t *)pos + nwords);
+            if (!have_nnz_m) g.add(&nnz_m, m_rowptr + M);
+            g.wait();
+        }
+        if (!have_nnz_m) check_nnz_m();
+        res->colidx = (uint32_t *)ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(uint32_t));
+        res->vals = ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(T));
+        apply_mask_rowptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(in->rowptr, M, bits, pos, res->rowptr);
+        launches++;
+        if (nnz) {
+            apply_mask_write_kernel<V><<<grid_for(nnz_in, 256), 256, 0, s>>>(in->colidx, (const V *)in->vals, nnz_in, bits, pos, res->colidx,
+                                                                               (V *)res->vals);
+            launches++;
+        }
+    }
+    OSP_HIP(hipEventRecord(ev.b, s));
+    OSP_HIP(hipStreamSynchronize(s));
+    OSP_HIP(hipGetLastError());
+    res->info.nnz_c = nnz;
+    res->info.ms_total = ev.ms();
+    *st = osp_apply_mask_stats_t{};
+    st->nnz_in = nnz_in;
+    st->nnz_mask = (uint64_t)nnz_m;
+    st->nnz_out = nnz;
+    st->ms_total = res->info.ms_total;
+    st->launches = launches;
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] apply_mask%s M=%llu nnz %llu -> %llu (mask %llu) launches=%u %.3f ms\n", complement ? " (complement)" : "",
+                (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)nnz, (unsigned long long)nnz_m, launches, st->ms_total);
+}
+
 static void destroy_result(Result *r) {
     if (!r) return;
     if (r->ctx) {
@@ -1241,6 +1343,23 @@ int osp_csr_inflate_prune(osp_result_t in_, const osp_mcl_step_t *step, int vali
         osp_mcl_stats_t st{};
         const int rc = new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {
             inflate_prune_impl<decltype(tag)>(in->ctx, in, res, *step, validate, &st);
+        });
+        if (stats) *stats = st;
+        return rc;
+    });
+}
+
+int osp_csr_apply_mask(osp_result_t in_, uint64_t M, uint64_t N, const int64_t *m_rowptr, const uint32_t *m_colidx, osp_memspace_t space,
+                       int complement, int validate, osp_result_t *out, osp_apply_mask_stats_t *stats) {
+    Result *in = (Result *)in_;
+    if (!in || !out || !m_rowptr) return fail(OSP_ERR_ARG, "null argument");
+    if (in->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
+    return guard([&] {
+        check_space(space);
+        if (M != in->info.M || N != in->info.N) throw Error(OSP_ERR_ARG, "apply_mask: the mask's shape differs from the result's");
+        osp_apply_mask_stats_t st{};
+        const int rc = new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {
+            apply_mask_impl<decltype(tag)>(in->ctx, in, res, m_rowptr, m_colidx, space, complement, validate, &st);
         });
         if (stats) *stats = st;
         return rc;

@@ -1,5 +1,7 @@
-"""Graph analytics on the library's products: triangle counting on the masked product (``osp_spgemm_masked``) and Markov
-clustering on the plain one with ``osp_csr_inflate_prune`` between two expansions (``markov_cluster``, at the end).
+"""Graph analytics on the library's products: triangle counting on the masked product (``osp_spgemm_masked``), Markov
+clustering on the plain one with ``osp_csr_inflate_prune`` between two expansions (``markov_cluster``), and traversals
+that use both with the mask filter ``osp_csr_apply_mask`` between two levels (``bfs_levels``, ``betweenness_centrality``,
+at the end).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -79,12 +81,10 @@ def triangle_count(rows, cols, n=None, ctx=None):
     return int(total)
 
 
-def walk_pattern(rows, cols, n=None, weights=None, device=None):
-    """A + I of ``markov_cluster`` from an edge list (any direction, duplicates and self loops allowed): the graph is made
-    symmetric, self loops are dropped, duplicate edges become one (weighted: the MAXIMUM of their weights, whichever
-    direction they were given in), and every vertex gets a self loop of weight 1 (weighted: of the largest weight in its
-    row, 1 for an isolated vertex).  Returns (n, rowptr int64, colidx int64, vals float64) as tensors on `device`
-    (default: the edges'), CSR with ascending columns.  Runs on the CPU as well."""
+def _undirected_keys(rows, cols, n, device):
+    """What ``walk_pattern`` and ``symmetric_adjacency`` share: the edge list checked, self loops dropped, every remaining
+    edge in both directions.  Returns (device, n, keep, both): ``keep`` marks the input edges that are no self loops, ``both``
+    holds the keys u * n + v of the kept edges followed by those of their reversals (duplicates still in)."""
     device = torch.device(device) if device is not None else (rows.device if torch.is_tensor(rows) else torch.device("cpu"))
     r, c = _as_index(rows, device), _as_index(cols, device)
     if r.shape != c.shape:
@@ -96,7 +96,16 @@ def walk_pattern(rows, cols, n=None, weights=None, device=None):
         raise ValueError(f"vertex ids must lie in [0, {n})")
     keep = r != c
     r, c = r[keep], c[keep]
-    both = torch.cat([r * n + c, c * n + r])
+    return device, n, keep, torch.cat([r * n + c, c * n + r])
+
+
+def walk_pattern(rows, cols, n=None, weights=None, device=None):
+    """A + I of ``markov_cluster`` from an edge list (any direction, duplicates and self loops allowed): the graph is made
+    symmetric, self loops are dropped, duplicate edges become one (weighted: the MAXIMUM of their weights, whichever
+    direction they were given in), and every vertex gets a self loop of weight 1 (weighted: of the largest weight in its
+    row, 1 for an isolated vertex).  Returns (n, rowptr int64, colidx int64, vals float64) as tensors on `device`
+    (default: the edges'), CSR with ascending columns.  Runs on the CPU as well."""
+    device, n, keep, both = _undirected_keys(rows, cols, n, device)
     if weights is None:
         key = torch.unique(both)
         w = torch.ones(key.numel(), dtype=torch.float64, device=device)
@@ -197,3 +206,205 @@ def markov_cluster(rows, cols, n=None, *, inflation=2.0, threshold=1e-4, max_per
         T.close()
     info["n_clusters"] = int(labels.max()) + 1
     return labels, info
+
+
+def symmetric_adjacency(rows, cols, n=None, device=None):
+    """The adjacency matrix of the undirected simple graph of an edge list (any direction, duplicates and self loops
+    allowed): symmetric, every edge once per direction, no self loops, unit values -- ``walk_pattern`` without the loops.
+    Returns (n, rowptr int64, colidx int64, vals float64) as tensors on `device` (default: the edges'), CSR with ascending
+    columns.  Runs on the CPU as well."""
+    device, n, _, both = _undirected_keys(rows, cols, n, device)
+    key = torch.unique(both)
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    if n:
+        rowptr[1:] = torch.cumsum(torch.bincount(key // n, minlength=n), 0)
+    return n, rowptr, key % n, torch.ones(key.numel(), dtype=torch.float64, device=device)
+
+
+class _Adjacency:
+    """``symmetric_adjacency`` on the device in the two forms the traversals hand to the library: COO (the B operand of
+    ``spgemm_coo_device``) and CSR (the B operand of ``spgemm_masked_device``)."""
+
+    def __init__(self, rows, cols, n, device):
+        self.n, self.rowptr, colidx, self.vals = symmetric_adjacency(rows, cols, n, device)
+        self.nnz = int(colidx.numel())
+        self.cols = colidx.to(torch.int32)
+        self.rows = torch.repeat_interleave(torch.arange(self.n, dtype=torch.int32, device=device), self.rowptr[1:] - self.rowptr[:-1])
+
+    def coo_ptrs(self):
+        return tuple(t.data_ptr() if self.nnz else 0 for t in (self.rows, self.cols, self.vals))
+
+    def csr_ptrs(self):
+        return (self.rowptr.data_ptr(),) + tuple(t.data_ptr() if self.nnz else 0 for t in (self.cols, self.vals))
+
+
+def _check_sources(sources, n):
+    src = np.atleast_1d(np.asarray(sources.cpu() if torch.is_tensor(sources) else sources)).astype(np.int64).ravel()
+    if src.size and (src.min() < 0 or src.max() >= n):
+        raise ValueError(f"sources must lie in [0, {n})")
+    return src
+
+
+def _device_mask_filter(product, visited):
+    return product.apply_mask(visited, complement=True)
+
+
+def _bfs_forward(ctx, device, adj, src, max_levels=None, keep_levels=False, mask_filter=_device_mask_filter):
+    """The forward sweep both traversals share.  Returns (level, sigma, info, levels): the dense int32 / float64
+    [len(src), n] tensors on `device`, the per-level lists, and -- with keep_levels -- per level d = 0..D the pair
+    (N_d as a CsrResult, its entries' positions row * n + col in the dense arrays); the caller closes those results.
+    ``mask_filter(product, visited) -> (CsrResult, stats)`` is the step between the product and the union
+    (tools/time_bfs.py --host-mask passes the host round trip)."""
+    from .sparse_util import _result_as_input
+    S, n = int(src.size), adj.n
+    level = torch.full((S, n), -1, dtype=torch.int32, device=device)
+    sigma = torch.zeros((S, n), dtype=torch.float64, device=device)
+    info = {"levels": 0, "frontier_nnz": [], "nnz_visited": [], "nnz_product": [], "nnz_new": [], "ms_product": [], "ms_mask": [],
+            "ms_union": []}
+    levels = []
+    if S == 0 or n == 0:
+        return level, sigma, info, levels
+    s_dev = torch.as_tensor(src, device=device)
+    lin0 = torch.arange(S, dtype=torch.int64, device=device) * n + s_dev
+    level.view(-1)[lin0] = 0
+    sigma.view(-1)[lin0] = 1.0
+    rp0 = torch.arange(S + 1, dtype=torch.int64, device=device)
+    c0, v0 = s_dev.to(torch.int32), torch.ones(S, dtype=torch.float64, device=device)
+    torch.cuda.synchronize(device)   # the library works on its own stream
+    # the sources as library CSR results: the merge of ONE part is the part itself.  F = the frontier, V = the visited set
+    part = [(rp0.data_ptr(), c0.data_ptr(), v0.data_ptr())]
+    F = V = None
+    try:
+        F = ctx.merge_csr_parts_device(np.float64, S, n, part)
+        V = ctx.merge_csr_parts_device(np.float64, S, n, part)
+        if keep_levels:
+            levels.append((F, lin0))
+        a = _result_as_input(F, device)
+        d = 0
+        while max_levels is None or d < max_levels:
+            d += 1
+            P = ctx.spgemm_coo_device(np.float64, S, n, n, a.nnz, (a.rows.data_ptr(), a.cols.data_ptr(), a.vals.data_ptr()), adj.nnz,
+                                      adj.coo_ptrs())
+            try:
+                Nx, st = mask_filter(P, V)
+            finally:
+                info["frontier_nnz"].append(a.nnz)
+                info["nnz_visited"].append(V.nnz)
+                info["nnz_product"].append(P.nnz)
+                info["ms_product"].append(P.info["ms_total"])
+                P.close()
+            info["nnz_new"].append(Nx.nnz)
+            info["ms_mask"].append(st["ms_total"])
+            if Nx.nnz == 0:
+                Nx.close()
+                info["ms_union"].append(0.0)
+                break
+            try:
+                U = ctx.merge_csr_parts_device(np.float64, S, n, [V.device_ptrs(), Nx.device_ptrs()])
+            except Exception:
+                Nx.close()
+                raise
+            info["ms_union"].append(U.info["ms_total"])
+            info["levels"] = d
+            torch.cuda.synchronize(device)   # torch holds views of F's arrays: nothing of it is in flight when they go back to the pool
+            del a
+            if not keep_levels:
+                F.close()
+            V.close()
+            F, V = Nx, U
+            a = _result_as_input(F, device)
+            lin = a.rows.to(torch.int64)[:a.nnz] * n + a.cols.to(torch.int64)
+            level.view(-1)[lin] = d
+            sigma.view(-1)[lin] = a.vals
+            if keep_levels:
+                levels.append((F, lin))
+        torch.cuda.synchronize(device)
+        del a
+    except Exception:
+        torch.cuda.synchronize(device)
+        for res, _ in levels:
+            res.close()
+        levels = []
+        raise
+    finally:
+        if F is not None and not keep_levels:
+            F.close()
+        if V is not None:
+            V.close()
+    return level, sigma, info, levels
+
+
+def bfs_levels(rows, cols, n=None, sources=(0,), *, max_levels=None, ctx=None):
+    """Breadth-first search from every vertex of ``sources`` at once on the undirected graph with edges (rows[e], cols[e])
+    on vertices [0, n), every level on the GPU: with the frontier F (one row per source) and the visited set V as CSR
+    results, a level is  P = F @ Adj  (the library's product, F handed over in HBM),  Nx = P<¬V>
+    (``CsrResult.apply_mask(V, complement=True)``),  V += Nx  (``merge_csr_parts_device``),  F = Nx,  until Nx is empty or
+    ``max_levels`` levels were taken.  With (+, x) and unit edge weights the frontier's values ARE the numbers of shortest
+    paths, so they come for free.
+
+    Returns (level, sigma, info): ``level`` int32 [len(sources), n], the distance from the source, -1 where unreached;
+    ``sigma`` float64 of the same shape, the number of shortest paths from the source (0 where unreached, exact below
+    2^53); ``info`` = levels (the deepest level reached) and per product the lists frontier_nnz, nnz_visited, nnz_product,
+    nnz_new, ms_product, ms_mask, ms_union (device times).  Duplicate sources are independent rows; a source out of
+    range is a ValueError; an isolated source ends after one product.  float64 only.  rows / cols: torch tensors (any
+    device; the plumbing runs on cuda:ctx.device) or array-likes."""
+    ctx = ctx or _S.default_context()
+    device = torch.device("cuda", ctx.device)
+    adj = _Adjacency(rows, cols, n, device)
+    src = _check_sources(sources, adj.n)
+    level, sigma, info, _ = _bfs_forward(ctx, device, adj, src, max_levels)
+    return level.cpu().numpy(), sigma.cpu().numpy(), info
+
+
+def betweenness_centrality(rows, cols, n=None, sources=None, *, batch=64, ctx=None):
+    """Betweenness centrality (Brandes) of the undirected graph with edges (rows[e], cols[e]) on vertices [0, n), ``batch``
+    sources at a time, every product on the GPU.  Returns float64 [n]:  bc[v] = sum over s in ``sources``, s != v, of the
+    dependency delta_s(v) -- unnormalised and NOT halved: with all vertices as sources (``sources=None``) an undirected
+    graph gives TWICE networkx's ``betweenness_centrality(normalized=False)``, every pair being counted from both ends.
+
+    Forward: the sweep of ``bfs_levels``, keeping every level's pattern N_d and the path counts sigma.  Backward, for
+    d = D .. 1:  W_d = (1 + delta) / sigma on N_d's pattern,  T = W_d @ Adj wanted only at N_{d-1}'s pattern -- the masked
+    product as it stands (``spgemm_masked_device``, W_d in CSC by a sort on the device) --,  delta += sigma * T there."""
+    from .sparse_util import _result_as_input
+    ctx = ctx or _S.default_context()
+    device = torch.device("cuda", ctx.device)
+    adj = _Adjacency(rows, cols, n, device)
+    n = adj.n
+    src_all = np.arange(n, dtype=np.int64) if sources is None else _check_sources(sources, n)
+    if int(batch) < 1:
+        raise ValueError("batch must be at least 1")
+    bc = torch.zeros(n, dtype=torch.float64, device=device)
+    for b0 in range(0, src_all.size, int(batch)):
+        src = src_all[b0:b0 + int(batch)]
+        S = int(src.size)
+        _, sigma, _, levels = _bfs_forward(ctx, device, adj, src, keep_levels=True)
+        try:
+            delta = torch.zeros((S, n), dtype=torch.float64, device=device)
+            sg, dl = sigma.view(-1), delta.view(-1)
+            for d in range(len(levels) - 1, 0, -1):
+                lin = levels[d][1]
+                w = (1.0 + dl[lin]) / sg[lin]
+                # W_d (S x n) in CSC: entries ordered by (column, row)
+                r, c = lin // n, lin % n
+                order = torch.argsort(c * S + r)
+                wv, ri = w[order].contiguous(), r[order].to(torch.int32)
+                colptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
+                colptr[1:] = torch.cumsum(torch.bincount(c, minlength=n), 0)
+                torch.cuda.synchronize(device)   # the library works on its own stream
+                T = ctx.spgemm_masked_device(np.float64, S, n, n, (colptr.data_ptr(), ri.data_ptr(), wv.data_ptr()) + adj.csr_ptrs(),
+                                             levels[d - 1][0].device_ptrs()[:2])
+                try:
+                    t = _result_as_input(T, device)
+                    tl = t.rows.to(torch.int64)[:t.nnz] * n + t.cols.to(torch.int64)
+                    dl[tl] += sg[tl] * t.vals
+                    torch.cuda.synchronize(device)   # torch holds views of T's arrays
+                    del t
+                finally:
+                    T.close()
+            dl[levels[0][1]] = 0.0   # delta_s(s) is not part of the sum
+            bc += delta.sum(0)
+        finally:
+            torch.cuda.synchronize(device)
+            for res, _ in levels:
+                res.close()
+    return bc.cpu().numpy()

@@ -123,6 +123,34 @@ class CsrResult:
         _lib.check(_lib.lib().osp_csr_inflate_prune(self._h, C.byref(step), int(bool(validate)), C.byref(h), C.byref(stats)))
         return CsrResult(self._ctx, h), stats.as_dict()
 
+    def apply_mask(self, mask, *, complement=False, validate=False, space="device"):
+        """The entries of this CSR that are in ``mask`` (``complement=True``: that are NOT in it) as a new CSR result on the
+        device (``osp_csr_apply_mask``); values keep their bits.  ``mask`` is a CSR pattern of this result's shape:
+        ``(rowptr, colidx)`` as device addresses (``space="device"``) or numpy arrays (``space="host"``), or another
+        ``CsrResult`` (its pattern, on the device).  Returns (result, stats dict): nnz_in, nnz_mask, nnz_out, ms_total,
+        launches.  validate=True checks the mask as ``spgemm_masked`` does."""
+        M, N = self.shape
+        if isinstance(mask, CsrResult):
+            if mask.shape != self.shape:
+                raise OspError(_lib.ERR_ARG, f"the mask's shape {mask.shape} differs from the result's {self.shape}")
+            rp, ci = (C.c_void_p(p) for p in mask.device_ptrs()[:2])
+            sp_, keep = _lib.OSP_DEVICE, None
+        elif space == "host":
+            r, c = np.ascontiguousarray(mask[0], np.int64), np.ascontiguousarray(mask[1], np.uint32)
+            if len(r) != M + 1:
+                raise OspError(_lib.ERR_ARG, f"the mask's row pointers must have M+1={M + 1} entries (got {len(r)})")
+            rp, ci, sp_, keep = C.c_void_p(r.ctypes.data), _ptr(c), _lib.OSP_HOST, (r, c)
+        elif space == "device":
+            rp, ci, sp_, keep = C.c_void_p(int(mask[0])), C.c_void_p(int(mask[1])), _lib.OSP_DEVICE, None
+        else:
+            raise ValueError('space must be "device" or "host"')
+        stats = _lib.ApplyMaskStats()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_csr_apply_mask(self._h, M, N, rp, ci, sp_, int(bool(complement)), int(bool(validate)), C.byref(h),
+                                                 C.byref(stats)))
+        del keep
+        return CsrResult(self._ctx, h), stats.as_dict()
+
     def coo_rows_into(self, rows_device_ptr):
         """Row index of every entry into caller-owned DEVICE memory (nnz u32 values): with ``device_ptrs()[1:]`` the COO
         form ``Context.spgemm_coo_device`` takes (``osp_result_coo_rows``)."""
