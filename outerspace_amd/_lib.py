@@ -95,6 +95,27 @@ class ApplyMaskStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+SELECT_OPS = {"lt": 0, "le": 1, "gt": 2, "ge": 3, "eq": 4, "ne": 5, "tril": 6, "triu": 7, "diag": 8, "offdiag": 9}  # osp_select_op_t
+
+
+class Select(C.Structure):
+    """osp_select_t"""
+    _fields_ = [("op", C.c_int32), ("fill", C.c_int32), ("threshold", C.c_double), ("diag", C.c_int64), ("fill_value", C.c_double),
+                ("reserved", C.c_uint32 * 8)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+class SelectStats(C.Structure):
+    """osp_select_stats_t"""
+    _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("ms_total", C.c_float), ("launches", C.c_uint32),
+                ("reserved", C.c_uint32 * 6)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -144,6 +165,9 @@ MCL_EXPORTS = ["osp_csr_inflate_prune"]
 
 # every symbol include/outerspace_spgemm_apply_mask.h declares
 APPLY_MASK_EXPORTS = ["osp_csr_apply_mask"]
+
+# every symbol include/outerspace_spgemm_select.h declares
+SELECT_EXPORTS = ["osp_csr_select"]
 
 _lib = None
 
@@ -224,6 +248,7 @@ def lib():
     L.osp_spgemm_masked.argtypes = [vp, i32, u64, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(Config), C.POINTER(vp)]
     L.osp_csr_inflate_prune.argtypes = [vp, C.POINTER(MclStep), i32, C.POINTER(vp), C.POINTER(MclStats)]
     L.osp_csr_apply_mask.argtypes = [vp, u64, u64, vp, vp, i32, i32, i32, C.POINTER(vp), C.POINTER(ApplyMaskStats)]
+    L.osp_csr_select.argtypes = [vp, C.POINTER(Select), C.POINTER(vp), C.POINTER(SelectStats)]
     _lib = L
     return L
 

@@ -14,6 +14,7 @@
 #include <chrono>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <string>
@@ -23,6 +24,7 @@
 #include "../../include/outerspace_spgemm_masked.h"
 #include "../../include/outerspace_spgemm_mcl.h"
 #include "../../include/outerspace_spgemm_apply_mask.h"
+#include "../../include/outerspace_spgemm_select.h"
 #include "osp_internal.h"
 #include "osp_kernels.h"
 #include "osp_split.h"
@@ -32,6 +34,7 @@
 #include "osp_masked.h"
 #include "osp_mcl.h"
 #include "osp_apply_mask.h"
+#include "osp_select.h"
 
 namespace osp {
 
@@ -1106,6 +1109,89 @@ static void apply_mask_impl(Context *ctx, const Result *in, Result *res, const i
                 (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)nnz, (unsigned long long)nnz_m, launches, st->ms_total);
 }
 
+// ---- the entry filter of a CSR result (osp_select.h) ----
+template <class T, int OP = 0>
+static void launch_select_value(int op, unsigned grid, hipStream_t s, const T *val, uint64_t nnz, double threshold, uint64_t *bits) {
+    if constexpr (OP <= SEL_NE) {
+        if (op == OP) select_flag_value_kernel<T, OP><<<grid, kAmThreads, 0, s>>>(val, nnz, threshold, bits);
+        else launch_select_value<T, OP + 1>(op, grid, s, val, nnz, threshold, bits);
+    }
+}
+template <int OP = SEL_TRIL>
+static void launch_select_position(int op, unsigned grid, hipStream_t s, const int64_t *rowptr, const uint32_t *col, uint64_t M, uint64_t nnz,
+                                   int64_t diag, uint64_t *bits) {
+    if constexpr (OP < SEL_OPS) {
+        if (op == OP) select_flag_position_kernel<OP><<<grid, kAmThreads, 0, s>>>(rowptr, col, M, nnz, diag, bits);
+        else launch_select_position<OP + 1>(op, grid, s, rowptr, col, M, nnz, diag, bits);
+    }
+}
+
+template <class T>
+static void select_impl(Context *ctx, const Result *in, Result *res, const osp_select_t &sel, osp_select_stats_t *st) {
+    typedef typename std::conditional<sizeof(T) == 8, uint64_t, uint32_t>::type V;
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint64_t M = in->info.M, nnz_in = in->info.nnz_c;
+    uint32_t launches = 0;
+    res->info = in->info;
+    res->rowptr = (int64_t *)ctx->alloc((M + 1) * sizeof(int64_t));
+    uint64_t nnz = 0;
+    if (nnz_in == 0) {
+        OSP_HIP(hipMemsetAsync(res->rowptr, 0, (M + 1) * sizeof(int64_t), s));
+        res->colidx = (uint32_t *)ctx->alloc(sizeof(uint32_t));
+        res->vals = ctx->alloc(sizeof(T));
+    } else {
+        const uint64_t nwords = (nnz_in + 63) / 64;
+        uint64_t *bits = sc.get<uint64_t>(nwords), *pos = sc.get<uint64_t>(nwords + 1);
+        uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(nwords));
+        const unsigned nchunks = grid_for(nnz_in, (unsigned)kAmChunk);
+        if (sel.op <= OSP_SELECT_NE) {
+            launch_select_value<T>(sel.op, nchunks, s, (const T *)in->vals, nnz_in, sel.threshold, bits);
+        } else {
+            // |col - row| < 2^32: a diagonal beyond +-2^33 selects what +-2^33 selects, and row + diag cannot overflow
+            const int64_t lim = (int64_t)1 << 33;
+            launch_select_position(sel.op, nchunks, s, in->rowptr, in->colidx, M, nnz_in, std::min(std::max(sel.diag, -lim), lim), bits);
+        }
+        device_exclusive_scan<LoadPopc64, uint64_t>(LoadPopc64{bits}, nwords, pos, tmp, s);
+        launches += 1 + ((nwords + kScanTile - 1) / kScanTile <= kScanSmallTiles ? 1 : 3);
+        nnz = d2h((const uint64_t *)pos + nwords, s);   // the call's one read-back
+        res->colidx = (uint32_t *)ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(uint32_t));
+        res->vals = ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(T));
+        apply_mask_rowptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(in->rowptr, M, bits, pos, res->rowptr);
+        launches++;
+        if (nnz) {
+            if (sel.fill) {
+                // (a double beyond T's range has no defined conversion: it becomes the infinity of its sign)
+                const double fv = sel.fill_value;
+                const T fill = std::isfinite(fv) && std::fabs(fv) > (double)std::numeric_limits<T>::max()
+                                   ? (T)std::copysign((double)std::numeric_limits<T>::infinity(), fv) : (T)fv;
+                V fill_bits;
+                memcpy(&fill_bits, &fill, sizeof fill);
+                select_fill_kernel<V><<<grid_for(nnz_in, 256), 256, 0, s>>>(in->colidx, nnz_in, bits, pos, fill_bits, res->colidx, (V *)res->vals);
+            } else {
+                apply_mask_write_kernel<V><<<grid_for(nnz_in, 256), 256, 0, s>>>(in->colidx, (const V *)in->vals, nnz_in, bits, pos, res->colidx,
+                                                                                   (V *)res->vals);
+            }
+            launches++;
+        }
+    }
+    OSP_HIP(hipEventRecord(ev.b, s));
+    OSP_HIP(hipStreamSynchronize(s));
+    OSP_HIP(hipGetLastError());
+    res->info.nnz_c = nnz;
+    res->info.ms_total = ev.ms();
+    *st = osp_select_stats_t{};
+    st->nnz_in = nnz_in;
+    st->nnz_out = nnz;
+    st->ms_total = res->info.ms_total;
+    st->launches = launches;
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] select op=%d%s M=%llu nnz %llu -> %llu launches=%u %.3f ms\n", sel.op, sel.fill ? " (fill)" : "",
+                (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)nnz, launches, st->ms_total);
+}
+
 static void destroy_result(Result *r) {
     if (!r) return;
     if (r->ctx) {
@@ -1360,6 +1446,23 @@ int osp_csr_apply_mask(osp_result_t in_, uint64_t M, uint64_t N, const int64_t *
         osp_apply_mask_stats_t st{};
         const int rc = new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {
             apply_mask_impl<decltype(tag)>(in->ctx, in, res, m_rowptr, m_colidx, space, complement, validate, &st);
+        });
+        if (stats) *stats = st;
+        return rc;
+    });
+}
+
+int osp_csr_select(osp_result_t in_, const osp_select_t *sel, osp_result_t *out, osp_select_stats_t *stats) {
+    Result *in = (Result *)in_;
+    if (!in || !sel || !out) return fail(OSP_ERR_ARG, "null argument");
+    if (in->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
+    return guard([&] {
+        if (sel->op < OSP_SELECT_LT || sel->op > OSP_SELECT_OFFDIAG) throw Error(OSP_ERR_ARG, "select: op is not one of osp_select_op_t");
+        for (uint32_t w : sel->reserved)
+            if (w) throw Error(OSP_ERR_ARG, "select: reserved words must be 0");
+        osp_select_stats_t st{};
+        const int rc = new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {
+            select_impl<decltype(tag)>(in->ctx, in, res, *sel, &st);
         });
         if (stats) *stats = st;
         return rc;

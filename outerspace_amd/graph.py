@@ -1,7 +1,8 @@
 """Graph analytics on the library's products: triangle counting on the masked product (``osp_spgemm_masked``), Markov
 clustering on the plain one with ``osp_csr_inflate_prune`` between two expansions (``markov_cluster``), and traversals
-that use both with the mask filter ``osp_csr_apply_mask`` between two levels (``bfs_levels``, ``betweenness_centrality``,
-at the end).
+that use both with the mask filter ``osp_csr_apply_mask`` between two levels (``bfs_levels``, ``betweenness_centrality``),
+and edge support and k-truss on the masked product with the entry filter ``osp_csr_select`` between two rounds
+(``edge_support``, ``k_truss``, ``truss_decomposition``, at the end).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -408,3 +409,174 @@ def betweenness_centrality(rows, cols, n=None, sources=None, *, batch=64, ctx=No
             for res, _ in levels:
                 res.close()
     return bc.cpu().numpy()
+
+
+# ---- edge support, k-truss -------------------------------------------------------------------------------
+def _truss_info():
+    return {"rounds": 0, "nnz_graph": [], "nnz_support": [], "nnz_kept": [], "ms_product": [], "ms_select": []}
+
+
+def _truss_setup(rows, cols, n, dtype, ctx):
+    """What the three truss functions share: the context first (without a GPU this is where they fail), the adjacency on
+    its device, and the guard of float32's exact range.  Returns (ctx, device, dtype, adj)."""
+    ctx = ctx or _S.default_context()
+    device = torch.device("cuda", ctx.device)
+    dtype = np.dtype(dtype).type
+    if dtype not in (np.float32, np.float64):
+        raise TypeError("dtype must be float32 or float64")
+    adj = _Adjacency(rows, cols, n, device)
+    # a support is below the smaller degree of the edge's ends
+    if dtype == np.float32 and adj.nnz and int((adj.rowptr[1:] - adj.rowptr[:-1]).max().item()) >= 1 << 24:
+        raise ValueError("float32 holds supports exactly only while the maximum degree is below 2^24: use float64")
+    return ctx, device, dtype, adj
+
+
+def _adjacency_result(ctx, adj, dtype, device):
+    """A non-empty ``_Adjacency`` as a library CSR result with unit values of ``dtype``: the merge of ONE part is the part
+    itself."""
+    vals = adj.vals.to(torch.float32 if dtype == np.float32 else torch.float64)
+    torch.cuda.synchronize(device)   # the library works on its own stream
+    return ctx.merge_csr_parts_device(dtype, adj.n, adj.n, [(adj.rowptr.data_ptr(), adj.cols.data_ptr(), vals.data_ptr())])
+
+
+def _support_product(ctx, A):
+    """S = (A @ A)<A> for a SYMMETRIC CSR result A with unit values: S[i, j] = the number of triangles through the edge
+    {i, j}; an edge in no triangle has no entry.  A's CSR arrays are also its CSC arrays, so it is A, B and the mask of the
+    masked product by its device pointers."""
+    n = A.shape[0]
+    p = A.device_ptrs()
+    return ctx.spgemm_masked_device(A.dtype, n, n, n, p + p, p[:2])
+
+
+def _upper_entries(A):
+    """The entries above the diagonal of the CSR result A -- every undirected edge once --, taken on the device
+    (``select("triu", diag=1)``).  Returns (u, v, values) on the host, u < v, ascending by (u, v)."""
+    U, _ = A.select("triu", diag=1)
+    try:
+        rowptr, colidx, vals = U.to_host()
+        return np.repeat(np.arange(U.shape[0], dtype=np.int64), np.diff(rowptr)), colidx.astype(np.int64), vals
+    finally:
+        U.close()
+
+
+def _truss_level(ctx, A, S, k, info, select_step=None):
+    """Rounds of level k on the graph A (a symmetric CSR result with unit values) until a filter removes nothing or leaves
+    nothing.  S: A's supports where they are known (``truss_decomposition``: the converged supports of level k - 1; the
+    first filter then needs no product and is no round), else None.  A and S are closed here.  Returns (A', S'): the k-truss
+    and -- unless it is empty -- its supports, on the same pattern.
+    ``select_step(result, op, threshold, fill=...) -> (CsrResult, stats)`` is the step between two products, by default
+    ``CsrResult.select`` (tools/time_truss.py --host-select passes the host round trip)."""
+    select_step = select_step or _S.CsrResult.select
+    while True:
+        try:
+            fresh = S is None
+            if fresh:
+                S = _support_product(ctx, A)
+            new, st = select_step(S, "ge", float(k - 2), fill=1.0)
+        except Exception:
+            A.close()
+            if S is not None:
+                S.close()
+            raise
+        if fresh:
+            info["rounds"] += 1
+            info["nnz_graph"].append(A.nnz)
+            info["nnz_support"].append(S.nnz)
+            info["nnz_kept"].append(new.nnz)
+            info["ms_product"].append(S.info["ms_total"])
+            info["ms_select"].append(st["ms_total"])
+        A.close()
+        A = new
+        # (the edges the product itself dropped lay in no triangle: no survivor's support changed with them)
+        if st["nnz_out"] == st["nnz_in"] or st["nnz_out"] == 0:
+            return A, S
+        S.close()
+        S = None
+
+
+def edge_support(rows, cols, n=None, *, dtype=np.float64, ctx=None):
+    """The number of triangles through every edge of the undirected graph with edges (rows[e], cols[e]) on vertices
+    [0, n) (any direction, duplicates and self loops allowed): S = (A @ A)<A>, the masked product as it stands, with A the
+    symmetric adjacency, and of A and S the halves above the diagonal by ``select("triu", diag=1)``.  Returns
+    (u, v, support): every edge once, u < v, ascending by (u, v), int64; an edge in no triangle has support 0."""
+    ctx, device, dtype, adj = _truss_setup(rows, cols, n, dtype, ctx)
+    if adj.nnz == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64)
+    A = _adjacency_result(ctx, adj, dtype, device)
+    try:
+        u, v, _ = _upper_entries(A)
+        S = _support_product(ctx, A)
+        try:
+            su, sv, sval = _upper_entries(S)
+        finally:
+            S.close()
+    finally:
+        A.close()
+    support = np.zeros(len(u), np.int64)
+    support[np.searchsorted(u * adj.n + v, su * adj.n + sv)] = sval.astype(np.int64)   # (the product has no entry where it is 0)
+    return u, v, support
+
+
+def k_truss(rows, cols, n=None, k=3, *, dtype=np.float64, ctx=None):
+    """The k-truss of the undirected graph with edges (rows[e], cols[e]) on vertices [0, n): the largest subgraph in which
+    every edge lies in at least k - 2 triangles of the subgraph (``networkx.k_truss``'s definition).  k >= 2; the 2-truss
+    is every edge and takes no round.  A ROUND is one support product S = (A @ A)<A> and one
+    ``S.select("ge", k - 2, fill=1.0)``, whose result is the next round's A, B and mask by its device pointers; the loop
+    ends after the first round whose filter removes nothing or leaves nothing.
+
+    Returns (u, v, info): the truss's edges once each, u < v, ascending by (u, v), int64; info = rounds, and per round the
+    lists nnz_graph, nnz_support, nnz_kept (directed entries: twice the edges), ms_product, ms_select (device times).
+    float32 is allowed while every support is exact (maximum degree below 2^24, else ValueError)."""
+    return _k_truss(rows, cols, n, k, dtype, ctx)
+
+
+def _k_truss(rows, cols, n, k, dtype, ctx, select_step=None):
+    k = int(k)
+    if k < 2:
+        raise ValueError("k must be at least 2")
+    ctx, device, dtype, adj = _truss_setup(rows, cols, n, dtype, ctx)
+    info = _truss_info()
+    if adj.nnz == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), info
+    A = _adjacency_result(ctx, adj, dtype, device)
+    if k > 2:
+        A, S = _truss_level(ctx, A, None, k, info, select_step)
+        S.close()
+    try:
+        u, v, _ = _upper_entries(A)
+    finally:
+        A.close()
+    return u, v, info
+
+
+def truss_decomposition(rows, cols, n=None, *, dtype=np.float64, ctx=None):
+    """The trussness of every edge of the undirected graph with edges (rows[e], cols[e]) on vertices [0, n): the largest k
+    whose k-truss contains the edge (2 for an edge in no triangle).  Levels k = 3, 4, ... run on the shrinking graph; the
+    converged supports of level k are the first filter input of level k + 1, so no product is repeated.
+
+    Returns (u, v, trussness, info): every edge once, u < v, ascending by (u, v), int64; info = k_max (the largest
+    trussness; 2 without edges), products (support products in all) and the per-product lists of ``k_truss``."""
+    ctx, device, dtype, adj = _truss_setup(rows, cols, n, dtype, ctx)
+    info = dict(_truss_info(), k_max=2, products=0)
+    if adj.nnz == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64), info
+    A = _adjacency_result(ctx, adj, dtype, device)
+    S = None
+    try:
+        u, v, _ = _upper_entries(A)
+        trussness = np.full(len(u), 2, np.int64)
+        k = 3
+        while True:
+            A, S = _truss_level(ctx, A, S, k, info)
+            if A.nnz == 0:
+                break
+            tu, tv, _ = _upper_entries(A)
+            trussness[np.searchsorted(u * adj.n + v, tu * adj.n + tv)] = k
+            info["k_max"] = k
+            k += 1
+    finally:
+        A.close()
+        if S is not None:
+            S.close()
+    info["products"] = info["rounds"]
+    return u, v, trussness, info

@@ -151,6 +151,23 @@ class CsrResult:
         del keep
         return CsrResult(self._ctx, h), stats.as_dict()
 
+    def select(self, op, threshold=0.0, *, diag=0, fill=None):
+        """The entries of this CSR that pass a predicate as a new CSR result on the device (``osp_csr_select``).  ``op`` is
+        ``"lt" "le" "gt" "ge" "eq" "ne"`` -- value ``op`` ``threshold``, compared as doubles under IEEE rules (a NaN passes
+        ``"ne"`` only) -- or ``"tril" "triu" "diag" "offdiag"`` -- column ``<=``, ``>=``, ``==``, ``!=`` row + ``diag``.
+        ``fill=None``: kept entries keep their value bits; otherwise every kept entry's value is ``fill``.  Returns
+        (result, stats dict): nnz_in, nnz_out, ms_total, launches."""
+        if op not in _lib.SELECT_OPS:
+            raise ValueError(f"op must be one of {' '.join(_lib.SELECT_OPS)} (got {op!r})")
+        sel = _lib.Select()
+        sel.op, sel.threshold, sel.diag = _lib.SELECT_OPS[op], float(threshold), int(diag)
+        if fill is not None:
+            sel.fill, sel.fill_value = 1, float(fill)
+        stats = _lib.SelectStats()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_csr_select(self._h, C.byref(sel), C.byref(h), C.byref(stats)))
+        return CsrResult(self._ctx, h), stats.as_dict()
+
     def coo_rows_into(self, rows_device_ptr):
         """Row index of every entry into caller-owned DEVICE memory (nnz u32 values): with ``device_ptrs()[1:]`` the COO
         form ``Context.spgemm_coo_device`` takes (``osp_result_coo_rows``)."""
