@@ -1375,6 +1375,22 @@ __device__ unsigned long long osp_merge_prof[16];
 // round trip instead of a chain of five.
 // workgroups of NT threads that fit one CU's 160 KiB of LDS -> waves per SIMD the register budget must allow
 constexpr int kMergeMaxWgs = 5;  // per CU (measured: five workgroups at <= 102 registers, a few spilled, beat four at 120)
+// Rounds per tile.  Every per-entry loop of the tile kernel is unrolled over the slots a thread (or a wave, in the sort)
+// holds: LPT = ceil(capacity / threads) rounds, each a few dozen instructions issued whether or not a lane has an entry.
+// A tile of n entries needs ceil(n / threads) of them.  With OSP_TILE_ROUNDS = K > 1 the tile's body is compiled K times,
+// for ceil(LPT * c / K) rounds (c = 1..K, the last one the full LPT), and a tile runs the smallest that holds it: the
+// round count stays a compile-time constant inside each body (register arrays keep static indices, loads of one phase
+// still go out together and are waited for one by one), and a full tile runs the code it ran before.  In a body of Q
+// rounds a wave's span of a gathered tile is 64 * Q positions and a thread's block of sorted entries is Q long, so the
+// waves and threads share a small tile evenly instead of the first ones taking capacity-sized pieces of it.
+// 0 or 1: one body of LPT rounds, capacity-sized spans (the kernel as it was through round 5).
+#ifndef OSP_TILE_ROUNDS
+#define OSP_TILE_ROUNDS 3
+#endif
+constexpr int kTileRoundClasses = OSP_TILE_ROUNDS > 1 ? OSP_TILE_ROUNDS : 1;
+static_assert(kTileRoundClasses <= 3, "OSP_TILE_ROUNDS: at most three bodies");
+// rounds of class c (1-based) of K for a kernel of `lpt` slots per thread
+constexpr int tile_class_rounds(int lpt, int c, int K) { return (lpt * c + K - 1) / K; }
 template <class T, int NT, int CAP, int MAXWG = kMergeMaxWgs, int ABL = 0>
 constexpr int merge_wgs_per_cu() {
     // (mode 64, row-wise tiles, keeps the values of a tile in LDS: one more array)
@@ -1407,7 +1423,6 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
     constexpr int NW = NT / kWave;
     constexpr int LPT = (kTileCap + NT - 1) / NT;
     constexpr int ITERS = (kTileCap / NW + kWave - 1) / kWave;  // wave iterations per sort pass
-    constexpr int IPT = LPT;
     constexpr int DPT = (kDigits + NT - 1) / NT;  // digits per thread in the scan step
     static_assert(kTileMaxRows + 1 <= NT, "row offsets are fetched one per thread");
     unsigned tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
@@ -1437,15 +1452,23 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
     uint64_t ro = 0;
     PartWords<T> lrec[LPT];  // raw: unpacked at staging time, so the loads stay in flight together
     // a thread's q-th entry of a tile is ix0 + q * ixs: tid + q * NT, or -- in the instantiation that knows gathered tiles --
-    // w * kSpan + q * 64 + lane: a wave owns a contiguous span of the tile (as in the sort passes), so that the records a wave
+    // w * 64 * Q + q * 64 + lane: a wave owns a contiguous span of the tile (as in the sort passes), so that the records a wave
     // gathers in one load are consecutive.  (For a staged tile the two are the same to the memory system: 64 consecutive
-    // records per wave and load either way.)
-    constexpr uint32_t kSpan = (uint32_t)kTileCap / NW;
-    static_assert(!GA || (kTileCap % (NW * kWave) == 0 && (int)kSpan == LPT * kWave), "gathered tiles: a wave's span is LPT wave-loads");
-    uint32_t ix0 = GA ? w * kSpan + lane : tid;
+    // records per wave and load either way.)  Q: the rounds of the body the tile runs (OSP_TILE_ROUNDS) -- n <= NW * 64 * Q.
+    static_assert(!GA || kTileCap % (NW * kWave) == 0, "gathered tiles: a wave's span is a whole number of wave-loads");
+    static_assert(ITERS <= LPT, "sort passes: a wave's share of a full tile in LPT wave-loads");
+    constexpr int K = kTileRoundClasses;
+    constexpr int Q1 = tile_class_rounds(LPT, 1, K), Q2 = tile_class_rounds(LPT, K > 1 ? 2 : 1, K);   // (the last class: LPT)
+    auto tile_rounds = [&](uint32_t n_) -> uint32_t {   // (tile-uniform: n comes through LDS, the compiler cannot know)
+        const uint32_t qn = (uint32_t)__builtin_amdgcn_readfirstlane((int)((n_ + NT - 1) / NT));
+        return K > 1 && qn <= (uint32_t)Q1 ? (uint32_t)Q1 : K > 2 && qn <= (uint32_t)Q2 ? (uint32_t)Q2 : (uint32_t)LPT;
+    };
+    uint32_t ix0 = tid;
     constexpr uint32_t ixs = GA ? (uint32_t)kWave : (uint32_t)NT;
     auto request = [&](const TileDesc &dd, bool ok) {
         bool fetch = ok && dd.n <= (uint32_t)kTileCap;
+        const uint32_t qr = tile_rounds(dd.n);                       // the rounds and the spans of the body that will consume them
+        const uint32_t rx0 = GA ? w * (uint32_t)kWave * qr + lane : tid;
         ro = 0;
 #ifndef OSP_TEST_NO_LATE_GUARD
         const uint32_t lv_i = dd.lvl & 1u;  // two levels; never index the argument arrays with anything else
@@ -1472,7 +1495,10 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
         }
 #pragma unroll
         for (int q = 0; q < LPT; q++) {
-            const uint32_t i = ix0 + q * ixs;
+            // the rounds beyond the tile's body are left out class by class (tile-uniform; the loads are only issued here, so
+            // nothing waits at these branches)
+            if ((K > 1 && q >= Q1 && qr <= (uint32_t)Q1) || (K > 2 && q >= Q2 && qr <= (uint32_t)Q2)) continue;
+            const uint32_t i = rx0 + q * ixs;
             // unconditional load from a clamped address (lanes past the end read the descriptor array and
             // ignore it): a branch here makes the compiler wait for every load inside its own block
             const Part<T> *src = (fetch && i < dd.n) ? &stage[dd.s + i] : reinterpret_cast<const Part<T> *>(desc);
@@ -1487,7 +1513,8 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
         // counters ... some thirty values -- out of the loop and, short of registers, SPILLS them: 21 of them with the gathered
         // path compiled in, reloaded sixty times per tile.  Hiding the thread index behind an empty asm once per tile makes
         // them the few integer instructions they are: no spills at the same 96 registers.)
-        if constexpr (GA) { asm volatile("" : "+v"(tid)); lane = tid & 63u; w = tid >> 6; ix0 = w * kSpan + lane; }
+        // (With several bodies there is that much more to hoist: every instantiation hides it now.)
+        if constexpr (GA || K > 1) { asm volatile("" : "+v"(tid)); lane = tid & 63u; w = tid >> 6; }
         OSP_DESC_CHECK(t, d);
         OSP_CRUMB(1, ntiles, d.lvl, d.nr);
         const uint64_t ra = d.ra, s = d.s, base = lvl.base[d.lvl];
@@ -1519,6 +1546,12 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
             __syncthreads();
             continue;
         }
+        // the tile's body, for Q rounds (see OSP_TILE_ROUNDS; not indented: it was the loop's body)
+        auto tile_body = [&](auto rounds_tag) __attribute__((always_inline)) {
+        constexpr int Q = decltype(rounds_tag)::value;
+        static_assert(Q >= 1 && Q <= LPT, "rounds of a tile body");
+        constexpr int SQ = K > 1 ? Q : ITERS;                        // wave iterations per sort pass
+        ix0 = GA ? w * (uint32_t)(kWave * Q) + lane : tid;          // (as request() placed the tile's records)
         int rowbits = 0;
         while ((1u << rowbits) < nr) rowbits++;
         const bool relkey = d.kbits != 0;  // level-1 tile: key = col - cbase
@@ -1612,17 +1645,17 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
                 // run starts before the wave's span (wave-uniform), then window by window
                 uint32_t cnt0 = 0;
                 {
-                    const uint32_t nwords = w * (kSpan / 32u);   // <= 3 * 14 words: one per lane
-                    static_assert((NW - 1) * (kSpan / 32u) <= (uint32_t)kWave, "gathered tiles: the bits before a wave's span, one word per lane");
+                    const uint32_t nwords = w * (2u * Q);   // <= 3 * 14 words: one per lane
+                    static_assert((NW - 1) * 2 * LPT <= kWave, "gathered tiles: the bits before a wave's span, one word per lane");
                     cnt0 = wave_reduce_sum<uint32_t>(lane < nwords ? (uint32_t)__popc(sm.gbits[lane]) : 0u);
                     cnt0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)cnt0);
                 }
 #pragma unroll
                 for (int q = 0; q < (LPT + 1) / 2; q++) rq[q] = 0;
 #pragma unroll
-                for (int q = 0; q < LPT; q++) {
+                for (int q = 0; q < Q; q++) {
                     const uint32_t i = ix0 + q * ixs;
-                    const uint32_t wi = w * (kSpan / 32u) + 2u * (uint32_t)q;   // the window's two words (wave-uniform address)
+                    const uint32_t wi = w * (2u * Q) + 2u * (uint32_t)q;   // the window's two words (wave-uniform address)
                     const uint32_t mlo = sm.gbits[wi], mhi = sm.gbits[wi + 1];
                     // starts at or before my position inside the window: those below my lane, and mine
                     const uint32_t below = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
@@ -1634,9 +1667,9 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
                 }
                 uint32_t bc[LPT];
 #pragma unroll
-                for (int q = 0; q < LPT; q++) bc[q] = ga.b_colidx[bpos[q]];
+                for (int q = 0; q < Q; q++) bc[q] = ga.b_colidx[bpos[q]];
 #pragma unroll
-                for (int q = 0; q < LPT; q++) {
+                for (int q = 0; q < Q; q++) {
                     const uint32_t i = ix0 + q * ixs;
                     if (relkey) {
                         kq[q] = bc[q] - cbase;
@@ -1651,13 +1684,13 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
                 if (early) {
                     uint32_t hq[LPT], oq[LPT];
 #pragma unroll
-                    for (int q = 0; q < LPT; q++) {
+                    for (int q = 0; q < Q; q++) {
                         hq[q] = (uint32_t)(((uint64_t)(kq[q] * 2654435761u) * HSG) >> 32);
                         oq[q] = kq[q];
                         if (ix0 + q * ixs < n) oq[q] = atomicCAS(&htab_g[hq[q]], 0xffffffffu, kq[q]);
                     }
 #pragma unroll
-                    for (int q = 0; q < LPT; q++) {
+                    for (int q = 0; q < Q; q++) {
                         if (ix0 + q * ixs < n) {
                             uint32_t old = oq[q], h = hq[q];
                             while (old != 0xffffffffu && old != kq[q]) {
@@ -1743,7 +1776,7 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
             }
         } else {
 #pragma unroll
-            for (int q = 0; q < LPT; q++) {
+            for (int q = 0; q < Q; q++) {
                 const uint32_t i = ix0 + q * ixs;
                 kq[q] = 0;
                 if (i < n) {
@@ -1761,13 +1794,13 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
                 // first probes of all the thread's keys go out together; only collisions with a different key walk on
                 uint32_t hq[LPT], oq[LPT];
 #pragma unroll
-                for (int q = 0; q < LPT; q++) {
+                for (int q = 0; q < Q; q++) {
                     hq[q] = (uint32_t)(((uint64_t)(kq[q] * 2654435761u) * HS) >> 32);
                     oq[q] = kq[q];
                     if (ix0 + q * ixs < n) oq[q] = atomicCAS(&htab[hq[q]], 0xffffffffu, kq[q]);
                 }
 #pragma unroll
-                for (int q = 0; q < LPT; q++) {
+                for (int q = 0; q < Q; q++) {
                     if (ix0 + q * ixs < n) {
                         uint32_t old = oq[q], h = hq[q];
                         while (old != 0xffffffffu && old != kq[q]) {
@@ -1784,7 +1817,8 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
             if (lane == kWave - 1 && wsum) atomicAdd(&sm.hcount, wsum);
         }
         // each wave ranks a contiguous span, so earlier waves = earlier positions (stable)
-        const uint32_t per = (n + NW - 1) / NW;
+        // (spans of 64 * Q like the staging spans; with one body for all tiles: of ceil(n / NW), as it was)
+        const uint32_t per = K > 1 ? (uint32_t)(kWave * Q) : (n + NW - 1) / NW;
         const uint32_t wbeg = min(w * per, n), wend = min(wbeg + per, n);
         int cur = 0;
         __syncthreads();   // keys staged, hash count complete
@@ -1793,7 +1827,7 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
                 if (tid < (uint32_t)kTileCap / 32u) sm.gbits[tid] = 0;   // (every thread has read them: the barrier above)
                 if constexpr (kRunInPad) {
 #pragma unroll
-                    for (int q = 0; q < LPT; q++) {
+                    for (int q = 0; q < Q; q++) {
                         const uint32_t i = ix0 + q * ixs;
                         if (i < n) sm.pad[i] = (uint16_t)(rq[q >> 1] >> (16 * (q & 1)));
                     }
@@ -1819,11 +1853,11 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
                 for (int dd = lane; dd < (ndig + 3) / 4; dd += kWave) c64[dd] = 0ull;
             }
             // (a) rank inside the wave's span; keys and ranks stay in registers for (c)
-            uint32_t kreg[ITERS], rreg[ITERS];
+            uint32_t kreg[SQ], rreg[SQ];
             auto rank_span = [&](auto bits_tag) {
                 constexpr int BITS = decltype(bits_tag)::value;
 #pragma unroll
-                for (int it = 0; it < ITERS; it++) {
+                for (int it = 0; it < SQ; it++) {
                     const uint32_t i = wbeg + it * kWave + lane;
                     const bool valid = i < wend;
                     kreg[it] = valid ? ksrc[i] : 0u;
@@ -1847,7 +1881,7 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
             {
                 uint32_t(*cnt32)[kDigits / 2] = reinterpret_cast<uint32_t(*)[kDigits / 2]>(sm.cnt);
 #pragma unroll
-                for (int it = 0; it < ITERS; it++) {
+                for (int it = 0; it < SQ; it++) {
                     const uint32_t i = wbeg + it * kWave + lane;
                     const bool valid = i < wend;
                     kreg[it] = valid ? ksrc[i] : 0u;
@@ -1920,7 +1954,7 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
             OSP_PROF_MARK(4);
             // (c) scatter
 #pragma unroll
-            for (int it = 0; it < ITERS; it++) {
+            for (int it = 0; it < SQ; it++) {
                 const uint32_t i = wbeg + it * kWave + lane;
                 if (i < wend) {
                     const uint32_t k = kreg[it];
@@ -1946,7 +1980,7 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
         if (!rw_tile && !gath) {
             const Part<T> *__restrict__ stg = lvl.stage[d.lvl];
 #pragma unroll
-            for (int q = 0; q < LPT; q++) {
+            for (int q = 0; q < Q; q++) {
                 const uint32_t i = ix0 + q * ixs;
                 vq[q] = load_part_words(i < n ? &stg[s + i] : reinterpret_cast<const Part<T> *>(desc)).val();  // clamped, branch-free
             }
@@ -1961,18 +1995,18 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
                 if constexpr (kKeepPos) {
                     T av[LPT];
 #pragma unroll
-                    for (int q = 0; q < LPT; q++) {
+                    for (int q = 0; q < Q; q++) {
                         const uint32_t i = ix0 + q * ixs;
                         bv[q] = ga.b_vals[bpos[q]];
                         av[q] = gruns[d.rbeg + (i < n ? (uint32_t)sm.pad[i] : 0u)].av;
                     }
 #pragma unroll
-                    for (int q = 0; q < LPT; q++) vq[q] = av[q] * bv[q];
+                    for (int q = 0; q < Q; q++) vq[q] = av[q] * bv[q];
                     (void)tile0;
                 } else {
                 RunDesc<T> rdq[LPT];
 #pragma unroll
-                for (int q = 0; q < LPT; q++) {
+                for (int q = 0; q < Q; q++) {
                     const uint32_t i = ix0 + q * ixs;
                     uint32_t r;
                     if constexpr (kRunInPad) r = i < n ? (uint32_t)sm.pad[i] : 0u;
@@ -1980,22 +2014,23 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
                     rdq[q] = gruns[d.rbeg + r];
                 }
 #pragma unroll
-                for (int q = 0; q < LPT; q++) {
+                for (int q = 0; q < Q; q++) {
                     const uint32_t i = ix0 + q * ixs;
                     bv[q] = ga.b_vals[i < n ? rdq[q].src - (rdq[q].dst - tile0) + i : 0u];   // clamped, branch-free
                 }
 #pragma unroll
-                for (int q = 0; q < LPT; q++) vq[q] = rdq[q].av * bv[q];
+                for (int q = 0; q < Q; q++) vq[q] = rdq[q].av * bv[q];
                 }
             }
         }
         if (npass == 0) __syncthreads();
-        // head flags + exclusive scan (blocked: thread owns IPT consecutive sorted entries) -- while the values are on
+        // head flags + exclusive scan (blocked: thread owns IPT = Q consecutive sorted entries) -- while the values are on
         // their way
+        constexpr int IPT = Q;
         const uint32_t ib = tid * IPT;
         uint32_t heads = 0, hmask = 0;
 #pragma unroll
-        for (int q = 0; q < IPT; q++) {
+        for (int q = 0; q < Q; q++) {
             const uint32_t i = ib + q;
             if (i < n) {
                 const bool h = (i == 0) || (skey[i] != skey[i - 1]);
@@ -2008,7 +2043,7 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
         }
         if (!rw_tile) {
 #pragma unroll
-            for (int q = 0; q < LPT; q++) {
+            for (int q = 0; q < Q; q++) {
                 const uint32_t i = ix0 + q * ixs;
                 if (i < n) sval[i] = vq[q];
             }
@@ -2032,7 +2067,7 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
         OSP_PROF_MARK(7);
         const uint32_t oslot0 = ex;   // output slot of the first run that starts among the thread's entries
 #pragma unroll
-        for (int q = 0; q < IPT; q++) {
+        for (int q = 0; q < Q; q++) {
             const uint32_t i = ib + q;
             if (i < n) {
                 sm.rank[i] = (uint16_t)ex;  // output slot of the run that starts at/behind i (the counters are dead)
@@ -2056,13 +2091,13 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
         {
             T v[IPT];
 #pragma unroll
-            for (int q = 0; q < IPT; q++) {
+            for (int q = 0; q < Q; q++) {
                 const uint32_t i = ib + q;
                 v[q] = i < n ? sval[spos[i]] : T(0);
             }
             T cur = T(0);
 #pragma unroll
-            for (int q = 0; q < IPT; q++) {
+            for (int q = 0; q < Q; q++) {
                 const uint32_t i = ib + q;
                 const bool hd = (hmask >> q) & 1u;
                 cur = hd ? v[q] : cur + v[q];   // (the sum STARTS as the head's value: keeps a lone -0.0)
@@ -2093,7 +2128,7 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
                 acc[IPT - 1] = a;
             }
 #pragma unroll
-            for (int q = 0; q < IPT; q++) {
+            for (int q = 0; q < Q; q++) {
                 if ((tmask >> q) & 1u) {
                     const uint32_t k = skey[ib + q];
                     ocol[q] = relkey ? k + cbase : (k & colmask);
@@ -2127,7 +2162,7 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
         // compact in LDS (columns over the sorted keys, sums over the values), then stream out with consecutive
         // lanes on consecutive addresses
 #pragma unroll
-        for (int q = 0; q < IPT; q++) {
+        for (int q = 0; q < Q; q++) {
             if ((tmask >> q) & 1u) {   // the run that ends at the thread's entry q: its slot is its head's
                 const uint32_t slot = oslot0 + (uint32_t)__popc(hmask & ((2u << q) - 1u)) - 1u;
                 skey[slot] = ocol[q];
@@ -2162,6 +2197,10 @@ __global__ __launch_bounds__(NT, (merge_waves_per_simd<T, NT, CAP, MAXWG, ABL>()
         d = dn;
         __syncthreads();  // LDS is reused by the next tile
         OSP_PROF_MARK(10);
+        };
+        if (const uint32_t rounds = tile_rounds(n); K > 1 && rounds == (uint32_t)Q1) tile_body(std::integral_constant<int, Q1>{});
+        else if (K > 2 && rounds == (uint32_t)Q2) tile_body(std::integral_constant<int, Q2>{});
+        else tile_body(std::integral_constant<int, LPT>{});
     }
     OSP_CRUMB(7, ntiles, 0, 0);
     OSP_PROF_FLUSH;

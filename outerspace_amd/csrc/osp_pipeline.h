@@ -626,6 +626,20 @@ static void merge_panel(Context *ctx, Result *res, PhaseTimer &tm, const MergeIO
         for (int k = 0; k < 5; k++) if (byp[k]) fprintf(stderr, " %d passes: %llu tiles, %.0f entries each;", k, (unsigned long long)byp[k], (double)ent[k] / byp[k]);
         fprintf(stderr, " gathered: %llu tiles, %.0f entries and %.1f runs each\n[osp]   tiles by key bits:", (unsigned long long)gt, gt ? (double)ge / gt : 0.0, gt ? (double)gr / gt : 0.0);
         for (int k = 0; k <= 32; k++) if (bits[k]) fprintf(stderr, " %d: %llu;", k, (unsigned long long)bits[k]);
+        // ... and by the rounds they need, Q = ceil(entries / threads); the body a tile runs (OSP_TILE_ROUNDS) is the smallest that holds it
+        constexpr int lpt = ((int)kCap + kMergeThreads - 1) / kMergeThreads;
+        uint64_t byq[lpt + 1] = {0}, slots = 0, need = 0, run = 0;
+        for (const TileDesc &t : hd) {
+            if (t.n > kCap) continue;
+            const int q = std::max(1, (int)((t.n + kMergeThreads - 1) / kMergeThreads));
+            int body = lpt;
+            for (int c = kTileRoundClasses; c >= 1; c--) if (q <= tile_class_rounds(lpt, c, kTileRoundClasses)) body = tile_class_rounds(lpt, c, kTileRoundClasses);
+            byq[q]++; slots += lpt; need += q; run += body;
+        }
+        fprintf(stderr, "\n[osp]   tiles by rounds (Q = ceil(n / %d)):", kMergeThreads);
+        for (int q = 1; q <= lpt; q++) fprintf(stderr, " Q=%d: %llu;", q, (unsigned long long)byq[q]);
+        fprintf(stderr, " slot-rounds needed %.1f %%, run %.1f %% of %d per tile (%d bodies)", slots ? 100.0 * need / slots : 0.0,
+                slots ? 100.0 * run / slots : 0.0, lpt, kTileRoundClasses);
         fprintf(stderr, "\n");
     }
     if (getenv("OSP_VERBOSE")) {   // (`make prof`: cycles of thread 0 of every workgroup between the kernel's marks)
