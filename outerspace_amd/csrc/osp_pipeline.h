@@ -143,15 +143,16 @@ template <class T> struct PanelPlan {
     explicit PanelPlan(Context *c) : sc(c) {}
 };
 
-// totals[mode] += rows, totals[3 + mode] += partial products, per mode of the long rows
+// totals[mode] += rows, totals[3 + mode] += partial products, per mode of the long rows; totals[6] += the one-wave planner's rows
 __global__ void mode_totals_kernel(const uint32_t *rows, uint32_t nlong, const uint64_t *row_off, const uint8_t *hmode,
-                                   unsigned long long *totals) {
+                                   const uint8_t *hsmall, unsigned long long *totals) {
     // (grid-stride, few workgroups: every wave ends in up to six atomics on six hot words -- one wave per 64 rows made them
     // 0.18 ms per panel on R-MAT-22)
-    uint64_t part[3] = {0, 0, 0}, cnt[3] = {0, 0, 0};
+    uint64_t part[3] = {0, 0, 0}, cnt[3] = {0, 0, 0}, nsmall = 0;
     for (uint32_t h = blockIdx.x * blockDim.x + threadIdx.x; h < nlong; h += gridDim.x * blockDim.x) {
         const uint64_t U = row_off[rows[h] + 1] - row_off[rows[h]];
         const uint8_t m = hmode[h];
+        nsmall += hsmall[h] ? 1ull : 0ull;
 #pragma unroll
         for (int mode = 0; mode < 3; mode++) { part[mode] += m == mode ? U : 0ull; cnt[mode] += m == mode ? 1ull : 0ull; }
     }
@@ -159,6 +160,8 @@ __global__ void mode_totals_kernel(const uint32_t *rows, uint32_t nlong, const u
         const uint64_t p = wave_reduce_sum<uint64_t>(part[mode]), c = wave_reduce_sum<uint64_t>(cnt[mode]);
         if (lane_id() == 0 && c) { atomicAdd(&totals[mode], (unsigned long long)c); atomicAdd(&totals[3 + mode], (unsigned long long)p); }
     }
+    nsmall = wave_reduce_sum<uint64_t>(nsmall);
+    if (lane_id() == 0 && nsmall) atomicAdd(&totals[6], (unsigned long long)nsmall);
 }
 
 // Before the multiply: level-0 tiles, the long rows and how each of them will reach the tile kernel, the second buffer
@@ -187,7 +190,20 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
     uint64_t nrd = 0;
     pl.blkbase = sc.get<uint64_t>((uint64_t)nlong + 1); pl.hbase = sc.get<uint64_t>((uint64_t)nlong + 1);
     pl.vbase = sc.get<uint64_t>((uint64_t)nlong + 1); pl.cellbase = sc.get<uint64_t>((uint64_t)nlong + 1);
-    unsigned long long *totals = (unsigned long long *)sc.get<uint64_t>(6);
+    unsigned long long *totals = (unsigned long long *)sc.get<uint64_t>(7);
+    // Small direct rows go to the one-wave planner (osp_split.h, direct_plan_small_kernel) where the panel gathers all its direct
+    // rows; OSP_PLAN_SMALL=0 leaves every row to direct_plan_kernel (A/B timing, debugging).  OSP_PLAN_SMALL_CELLS /
+    // OSP_PLAN_SMALL_CHUNKS move the limits (measurements; tests reach both sides of them).
+    uint8_t *hsmall = sc.get<uint8_t>(nlong);
+    SmallLimits small_lim{};
+    if (want_gather && !(getenv("OSP_PLAN_SMALL") && atoi(getenv("OSP_PLAN_SMALL")) == 0) &&
+        !(getenv("OSP_GATHER_OVER") && atoi(getenv("OSP_GATHER_OVER")) == 0)) {
+        small_lim.cells = (uint32_t)std::clamp<long>(getenv("OSP_PLAN_SMALL_CELLS") ? atol(getenv("OSP_PLAN_SMALL_CELLS")) : (long)kSmallCells,
+                                                     (long)kSmallCellsMin, (long)kSmallCellsMax);
+        small_lim.chunks = (uint32_t)std::clamp<long>(getenv("OSP_PLAN_SMALL_CHUNKS") ? atol(getenv("OSP_PLAN_SMALL_CHUNKS")) : (long)kSmallChunks,
+                                                      1L, (long)kSmallChunks);
+    }
+    uint64_t nsmall = 0;
     // debugging aid: OSP_SPLIT_ROW_MAX moves the boundary between the two split kernels (tests run both on small inputs)
     const uint64_t row_max = getenv("OSP_SPLIT_ROW_MAX") ? strtoull(getenv("OSP_SPLIT_ROW_MAX"), nullptr, 10) : kSplitRowMax;
     // no more ranges than make a range as narrow as the dense accumulators take (osp_split.h, kDenseBits): beyond that
@@ -217,9 +233,9 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
         if (!hub_possible) hub_b = 0;
         split_params_kernel<<<grid_for(nlong, 256), 256, 0, s>>>(pl.p0.long_rows, nlong, row_off, colbits, row_max, bits_cap, ds ? ds->rowfirst : nullptr,
                                                                  ds ? ds->direct_max : 0ull, kCap, pl.hbits, pl.hmode, pl.nstretch, nseg, nhist, ncellh,
-                                                                 hub_b, direct_fine, ds ? nrund : nullptr);
-        zero_async(s, {{totals, 6 * sizeof(uint64_t)}});
-        mode_totals_kernel<<<std::min(grid_for(nlong, 256), 64u), 256, 0, s>>>(pl.p0.long_rows, nlong, row_off, pl.hmode, totals);
+                                                                 hub_b, direct_fine, ds ? nrund : nullptr, hsmall, ds ? small_lim : SmallLimits{});
+        zero_async(s, {{totals, 7 * sizeof(uint64_t)}});
+        mode_totals_kernel<<<std::min(grid_for(nlong, 256), 64u), 256, 0, s>>>(pl.p0.long_rows, nlong, row_off, pl.hmode, hsmall, totals);
         device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{pl.nstretch}, nlong, pl.blkbase, pl.hscan_tmp, s);
         device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{nseg}, nlong, pl.vbase, pl.hscan_tmp, s);
         device_exclusive_scan<LoadU64, uint64_t>(LoadU64{nhist}, nlong, pl.hbase, pl.hscan_tmp, s);
@@ -234,6 +250,7 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
             if (ds) g.add(&ndcell, (const uint64_t *)pl.cellbase + nlong);
             if (ds && nrund) g.add(&nrd, (const uint64_t *)rdbase + nlong);
             for (int i = 0; i < 6; i++) g.add(&tot[i], (const uint64_t *)totals + i);
+            g.add(&nsmall, (const uint64_t *)totals + 6);
             g.wait();
         }
         // the cells of a panel are addressed with 32 bits (and are device memory beside the staging buffers): a panel whose
@@ -292,8 +309,20 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
         // the gathered rows beside them their skip marks: the offsets must exist first
         if (!(runs && gp.over) || (hub_b && pl.nblocks)) ds->ensure_chunk_off(s);
         gp.mark_skipped = ds->chunk_off_ready ? 1u : 0u;
+        // the one-wave planner's rows: only where every direct row of the panel is gathered (it leaves no cells)
+        const bool plan_small = runs != nullptr && gp.over && nsmall != 0;
+        const bool plan_big = !plan_small || nsmall < pl.mode_rows[kModeDirect];
+        if (plan_small) gp.small = hsmall;
+        if (getenv("OSP_VERBOSE"))
+            fprintf(stderr, "[osp]   small planner: %llu of %llu direct rows (at most %u chunks, %u cells)\n", (unsigned long long)(plan_small ? nsmall : 0),
+                    (unsigned long long)pl.mode_rows[kModeDirect], small_lim.chunks, small_lim.cells);
         tm.begin(PH_PLAN_K, s);
-        if (nlong <= 4u * ctx->cus)   // few rows: the launch lasts as long as its longest row (osp_split.h, kDirectCellsBig)
+        if (plan_small)
+            direct_plan_small_kernel<T><<<nlong, kWave, direct_plan_small_lds(small_lim.cells), s>>>(
+                pl.p0.long_rows, nlong, pl.hbits, nseg, pl.vbase, pl.hoff, colbits, kCap, ds->rowfirst, ds->off, ds->bs, ds->perm, ds->b_colidx,
+                pl.vrow_off, pl.vcol0, pl.vcol1, ds->chunk_off, gp, (const T *)ds->a_vals, runs);
+        if (!plan_big) { /* every direct row of the panel is a small one */ }
+        else if (nlong <= 4u * ctx->cus)   // few rows: the launch lasts as long as its longest row (osp_split.h, kDirectCellsBig)
             direct_plan_kernel<T, kDirectCellsBig><<<nlong, kDirectThreads, 0, s>>>(pl.p0.long_rows, nlong, pl.hmode, pl.hbits, nseg, pl.vbase, pl.hoff,
                                                                                  pl.cellbase, row_off, colbits, kCap, ds->rowfirst, ds->off, ds->bs, ds->perm,
                                                                                  ds->b_colidx, pl.vrow_off, pl.vcol0, pl.vcol1, pl.cells, ds->chunk_off, gp,
@@ -315,6 +344,14 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
             fprintf(stderr, "[osp]   planner cycles: header %.1f %%, chunk descriptors %.1f %%, histogram pass %.1f %%, grouping %.1f %%, cell pass %.1f %%, "
                             "prefixes + output %.1f %%; %.0f cycles per row, %u rows\n", 100 * hp[0] / tot, 100 * hp[1] / tot, 100 * hp[2] / tot, 100 * hp[3] / tot,
                     100 * hp[4] / tot, 100 * hp[5] / tot, tot / std::max(1u, nlong), nlong);
+            (void)hipMemcpyFromSymbol(hp, HIP_SYMBOL(osp_plan_small_prof), sizeof(hp));
+            (void)hipMemcpyToSymbol(HIP_SYMBOL(osp_plan_small_prof), z, sizeof(z));
+            tot = 0;
+            for (int k = 0; k < 5; k++) tot += (double)hp[k];
+            if (plan_small && tot > 0)
+                fprintf(stderr, "[osp]   small planner cycles: header + chunk descriptors %.1f %%, histogram pass %.1f %%, grouping %.1f %%, counts %.1f %%, "
+                                "prefixes + output %.1f %%; %.0f cycles per row, %llu rows\n", 100 * hp[0] / tot, 100 * hp[1] / tot, 100 * hp[2] / tot,
+                        100 * hp[3] / tot, 100 * hp[4] / tot, tot / (double)nsmall, (unsigned long long)nsmall);
         }
 #endif
         res->info.direct_plan_launches++;

@@ -76,6 +76,20 @@ constexpr int kDirectCells = 4096;     // LDS words of direct_plan_kernel's (chu
 constexpr uint64_t kDirectDenseMax = 1ull << 20;   // longest dense row (ranges capped at the accumulators' width) written directly
 constexpr int kDirectMaxRanges = 255;  // ranges per direct row (a byte per fine bin names the range)
 constexpr uint64_t kDirectRowCells = 1ull << 19;  // (chunk, range) cells of ONE direct row at most
+// SMALL direct rows: few chunks, a handful of ranges -- two thirds of the planned rows of R-MAT-22 "mild".  One WAVE plans such a
+// row (direct_plan_small_kernel below) instead of a workgroup of four whose scans, barriers and blocks of 512 chunks are sized for
+// rows a hundred times longer.  The limits: a lane per chunk, the slim histogram of 2^kSmallFineBits bins, kSmallRanges
+// segments, and nc * nranges cells (LDS of the launch: OSP_PLAN_SMALL_CELLS lowers or raises it at run time, for measurements).
+constexpr int kSmallChunks = 64;
+constexpr int kSmallFineBits = 8;
+constexpr int kSmallRanges = 32;
+#ifndef OSP_SMALL_CELLS
+#define OSP_SMALL_CELLS 512
+#endif
+constexpr int kSmallCells = OSP_SMALL_CELLS, kSmallCellsMin = 1 << kSmallFineBits, kSmallCellsMax = 2048;
+struct SmallLimits {   // what split_params_kernel lets the one-wave planner take (cells == 0: nothing)
+    uint32_t cells = 0, chunks = kSmallChunks, ranges = kSmallRanges;
+};
 // per long row h: b = number of split bits, the mode, and the sizes that get scanned.
 // rowfirst != nullptr: the row's chunks are known (first chunk of every row in (row, k) order), so rows of at most
 // direct_max partial products that one workgroup could split are planned as direct rows instead: nseg = an upper bound
@@ -87,7 +101,8 @@ constexpr uint64_t kDirectRowCells = 1ull << 19;  // (chunk, range) cells of ONE
 __global__ void split_params_kernel(const uint32_t *rows, uint32_t nheavy, const uint64_t *row_off, int colbits,
                                     uint64_t row_max, int bits_cap, const uint32_t *rowfirst, uint64_t direct_max, uint32_t cap,
                                     uint8_t *hbits, uint8_t *hmode, uint32_t *nstretch, uint32_t *nseg, uint64_t *nhist, uint64_t *ncell,
-                                    int hub_b = 0, int direct_fine = 0, uint64_t *nrund = nullptr) {
+                                    int hub_b = 0, int direct_fine = 0, uint64_t *nrund = nullptr, uint8_t *hsmall = nullptr,
+                                    SmallLimits sl = SmallLimits{}) {
     const uint32_t h = blockIdx.x * blockDim.x + threadIdx.x;
     if (h >= nheavy) return;
     const uint64_t U = row_off[rows[h] + 1] - row_off[rows[h]];
@@ -121,6 +136,10 @@ __global__ void split_params_kernel(const uint32_t *rows, uint32_t nheavy, const
     ncell[h] = direct ? ((1ull << b) + 3) / 4 + nc * nranges : 0ull;
     // run descriptors of a gathered row: one per non-empty (chunk, range) cell, never more than the row has products
     if (nrund) nrund[h] = direct ? min(nc * nranges, U) : 0ull;
+    // a small direct row (see kSmallChunks): planned by one wave, if the panel turns out to gather its direct rows
+    if (hsmall)
+        hsmall[h] = direct && !capped && b <= kSmallFineBits && nc >= 1 && nc <= (uint64_t)sl.chunks && nranges <= (uint64_t)sl.ranges &&
+                    nc * nranges <= (uint64_t)sl.cells && U < (1ull << 20);
 }
 struct HeavyLenIf {   // partial products of long row h if it has mode `mode` (else 0): how much each path handles
     const uint32_t *rows;
@@ -655,8 +674,11 @@ __device__ __forceinline__ uint32_t direct_find_chunk(const uint32_t *cst, uint3
 __device__ unsigned long long osp_plan_prof[8];
 #define OSP_PLAN_MARK(k) do { if (threadIdx.x == 0) { const unsigned long long now_ = clock64(); atomicAdd(&osp_plan_prof[k], now_ - prof_t); prof_t = now_; } } while (0)
 #define OSP_PLAN_DECL unsigned long long prof_t = clock64();
+__device__ unsigned long long osp_plan_small_prof[8];   // the same for direct_plan_small_kernel (phases: see its marks)
+#define OSP_PLAN_SMALL_MARK(k) do { if (threadIdx.x == 0) { const unsigned long long now_ = clock64(); atomicAdd(&osp_plan_small_prof[k], now_ - prof_t); prof_t = now_; } } while (0)
 #else
 #define OSP_PLAN_MARK(k)
+#define OSP_PLAN_SMALL_MARK(k)
 #define OSP_PLAN_DECL
 #endif
 // GATHERED rows (round 5; osp_kernels.h, "gathered rows"): a direct row none of whose ranges exceeds a tile is not written by
@@ -675,6 +697,7 @@ struct GatherPlan {
     uint32_t over = 1;                  // rows with a range that exceeds a tile are gathered too
     uint32_t mark_skipped = 1;          // the chunk offsets exist (a column-major multiply may read them): gathered chunks get kChunkSkip
     uint32_t av_in_order = 0;           // a_vals holds the chunks' A values in (row, k) order (else: indexed through perm)
+    const uint8_t *small = nullptr;     // per long row: 1 = direct_plan_small_kernel plans it, direct_plan_kernel leaves it (null: no such rows)
 };
 // gstat[0..2] += gathered rows, their partial products, their runs (few workgroups: they end in atomics on three hot words --
 // one set per ROW inside the planner made it twice as slow)
@@ -717,6 +740,7 @@ __global__ __launch_bounds__(kDirectThreads, (CL > OSP_DIRECT_CELLS_LDS ? 2 : 8)
     __shared__ uint32_t s_T, s_over;
     const uint32_t h = blockIdx.x;
     if (h >= nlong || hmode[h] != kModeDirect) return;
+    if (gp.small != nullptr && gp.small[h]) return;   // (the one-wave planner's row)
     OSP_PLAN_DECL
     const unsigned tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
     const uint64_t above = lanes_above_mask();
@@ -1035,6 +1059,198 @@ __global__ __launch_bounds__(kDirectThreads, (CL > OSP_DIRECT_CELLS_LDS ? 2 : 8)
         __syncthreads();   // the block's cells and descriptors have been read
         OSP_PLAN_MARK(5);   // prefixes, cells and descriptors out
     }
+}
+// ---- small direct rows: one wave per row ----------------------------------------------------------------------------------
+// The plan of a SMALL row (split_params_kernel, kSmallChunks) -- at most 64 chunks, a few ranges, a gathering panel -- word for
+// word what direct_plan_kernel leaves for it (segment tables, run descriptors in (range, chunk) order, skip marks), made by ONE
+// wave: lane = chunk for the descriptors, wave scans instead of block scans, no barrier, and none of the steps of a few dozen
+// work items that four waves execute four times over.  Its LDS -- the slim histogram and ONE array of
+// (chunk, range) cells that holds where every range starts inside its chunk (a count is the difference of two neighbours) -- is
+// under 5 KB at 512 cells, so that as many waves stay resident per CU as the four-wave planner has.
+// (LDS traffic of one wave is in order; the fences keep the compiler from moving it across a step's end.)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ uint32_t wave_last(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, kWave - 1); }
+constexpr size_t direct_plan_small_lds(uint32_t cells) { return (size_t)cells * sizeof(uint32_t); }   // dynamic LDS of a launch
+template <class V>
+__global__ __launch_bounds__(kWave, 8) void direct_plan_small_kernel(
+    const uint32_t *__restrict__ rows, uint32_t nlong, const uint8_t *__restrict__ hbits, const uint32_t *__restrict__ nseg,
+    const uint64_t *__restrict__ vbase, const uint64_t *__restrict__ hoff, int colbits, uint32_t cap,
+    const uint32_t *__restrict__ rowfirst, const uint64_t *__restrict__ ct_off, const uint32_t *__restrict__ ct_bs,
+    const uint32_t *__restrict__ perm, const uint32_t *__restrict__ b_colidx, uint64_t *__restrict__ vrow_off,
+    uint32_t *__restrict__ vcol0, uint32_t *__restrict__ vcol1, uint64_t *__restrict__ chunk_off, const GatherPlan gp,
+    const V *__restrict__ a_vals, RunDesc<V> *__restrict__ runs) {
+    constexpr int NF = 1 << kSmallFineBits, UNR = OSP_DIRECT_UNR, RMAX = kSmallRanges;
+    extern __shared__ uint32_t cell[];                 // grouping: the chain of range starts; then cell[cl * (T + 1) + t] = first entry of range t inside chunk cl
+    __shared__ alignas(8) uint32_t hist[NF + 2];       // bin counts, then their exclusive prefix; descriptors: the chunks' A values
+    __shared__ uint32_t psum[kWave];                   // descriptors: products and runs per (group of chunks, range)
+    __shared__ uint32_t cbs[kWave], cst[kWave + 1];    // per chunk: (B position - first entry number), first entry number
+    __shared__ uint32_t rbin0[RMAX + 1], roff[RMAX + 1], bcol[RMAX + 1], nzc[RMAX + 1];
+    static_assert(sizeof(hist) >= kSmallChunks * sizeof(V), "the A values go where the histogram was");
+    static_assert(kSmallChunks <= kWave && kSmallRanges <= kWave && kSmallCellsMin >= NF, "a lane per chunk, a lane per segment, the chain in the cells");
+    const uint32_t h = blockIdx.x;
+    if (h >= nlong || !gp.small[h]) return;
+    OSP_PLAN_DECL
+    const unsigned lane = lane_id();
+    const uint64_t above = lanes_above_mask();
+    const uint32_t i = rows[h];
+    const uint32_t c0 = rowfirst[i], nc = rowfirst[i + 1] - c0;   // 1 .. 64
+    const uint32_t b = hbits[h], nfine = 1u << b, Ta = nseg[h];
+    const int sh = colbits - (int)b;
+    const uint32_t q0 = (uint32_t)hoff[h];
+    // chunk descriptors, lane = chunk (the lanes behind the last chunk: empty chunks at the row's end)
+    uint32_t bs = 0, len = 0, pa = 0;
+    if (lane < nc) {
+        const uint32_t c = c0 + lane;
+        bs = ct_bs[c];
+        len = (uint32_t)(ct_off[c + 1] - ct_off[c]);
+        pa = perm[c];
+    }
+    // (the A value: two dependent loads that arrive during the walk)
+    const V av = lane < nc ? (gp.av_in_order ? a_vals[c0 + lane] : a_vals[pa]) : V(0);
+    const uint32_t cincl = wave_incl_scan(len), E = wave_last(cincl);
+    cst[lane] = cincl - len;
+    cbs[lane] = bs - (cincl - len);
+    if (lane == kWave - 1) cst[kWave] = E;
+    for (uint32_t d = lane; d <= nfine; d += kWave) hist[d] = 0;
+    wave_lds_sync();
+    OSP_PLAN_SMALL_MARK(0);   // row header, chunk descriptors
+    // ---- 1. histogram over the fine bins: the row's entries in their flat numbering, UNR wave-loads of B's columns in flight.
+    // A lane's entries ascend from load to load, and so does its chunk.
+    {
+        uint32_t c = 0;
+        for (uint32_t base = 0; base < E; base += UNR * kWave) {
+            uint32_t col[UNR];
+#pragma unroll
+            for (int u = 0; u < UNR; u++) {
+                const uint32_t e = base + u * kWave + lane;
+                const bool valid = e < E;
+                while (valid && e >= cst[c + 1]) c++;
+                col[u] = b_colidx[valid ? cbs[c] + e : 0u];   // clamped: the loads go out together
+            }
+#pragma unroll
+            for (int u = 0; u < UNR; u++) {
+                if (base + u * kWave >= E) break;   // (wave-uniform)
+                const bool valid = base + u * kWave + lane < E;   // valid lanes are a prefix
+                const uint32_t bin = valid ? col[u] >> sh : 0xffffffffu;
+                uint32_t runlen;
+                if (wave_run_head(bin, valid, runlen, above)) atomicAdd(&hist[bin], runlen);
+            }
+        }
+    }
+    wave_lds_sync();
+    OSP_PLAN_SMALL_MARK(1);   // histogram pass
+    // ---- 2. greedy grouping into ranges of at most `cap` (direct_plan_kernel's rule): prefix sums, the bin every range that
+    // starts at d ends before, then one lane follows that chain
+    {
+        constexpr int PER = NF / kWave;   // bins per lane (blocked)
+        uint32_t v[PER], sum = 0;
+#pragma unroll
+        for (int q = 0; q < PER; q++) { const uint32_t d = lane * PER + q; v[q] = d < nfine ? hist[d] : 0u; sum += v[q]; }
+        const uint32_t incl = wave_incl_scan(sum), total = wave_last(incl);
+        uint32_t ex = incl - sum;
+#pragma unroll
+        for (int q = 0; q < PER; q++) { const uint32_t d = lane * PER + q; if (d < nfine) hist[d] = ex; ex += v[q]; }
+        if (lane == 0) hist[nfine] = total;
+    }
+    wave_lds_sync();
+    uint32_t *nxt = cell;
+    for (uint32_t d = lane; d < nfine; d += kWave) {
+        const uint32_t lim = hist[d] + cap;
+        uint32_t lo = d + 1, hi = nfine + 1;   // first e in (d, nfine] with hist[e] > lim, or nfine + 1
+        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (hist[mid] <= lim) lo = mid + 1; else hi = mid; }
+        nxt[d] = max(d + 1, lo - 1);
+    }
+    wave_lds_sync();
+    uint32_t T = 0;
+    if (lane == 0) {
+        uint32_t t = 0;
+        for (uint32_t d = 0; d < nfine; d = nxt[d]) { rbin0[t] = d; roff[t] = hist[d]; t++; }
+        rbin0[t] = nfine; roff[t] = hist[nfine];
+        T = t;
+    }
+    T = (uint32_t)__builtin_amdgcn_readfirstlane((int)T);   // 1 .. Ta - 1 (split_params_kernel's bound)
+    wave_lds_sync();
+    if (lane < Ta) {
+        const uint64_t v = vbase[h] + lane;
+        const uint32_t tt = min(lane, T);   // the unused segments at the end: empty
+        vrow_off[v] = (uint64_t)q0 + roff[tt];
+        vcol0[v] = (uint32_t)min((uint64_t)rbin0[tt] << sh, (uint64_t)0xffffffffu);
+        vcol1[v] = (uint32_t)min((uint64_t)rbin0[min(tt + 1, T)] << sh, (uint64_t)0xffffffffu);
+    }
+    if (lane <= T) bcol[lane] = (uint32_t)min((uint64_t)rbin0[lane] << sh, (uint64_t)0xffffffffu);   // first column of every range
+    V *avs = reinterpret_cast<V *>(hist);   // (the prefix has been read: roff holds what is needed of it)
+    if (lane < nc) avs[lane] = av;
+    OSP_PLAN_SMALL_MARK(2);   // grouping, segment tables
+    // ---- 3. where every range starts inside every chunk.  B's rows are sorted: a lower bound per (chunk, inner boundary).
+    // (direct_plan_kernel walks the entries again instead where the chunks are shorter than 8 entries per boundary -- the counts
+    // are the same either way, and a small row never is such a row: consecutive ranges together exceed a tile, so
+    // T - 1 < 2 U / cap, and 8 nc (T - 1) < 16 nc U / cap <= U with at most cap / 16 chunks.)
+    static_assert(16 * kSmallChunks <= TileCap<V>::value, "small rows never take the walk");
+    const uint32_t TS = T + 1;   // a chunk's cells: T starts and its length
+    wave_lds_sync();
+    for (uint32_t x = lane; x < nc * (T - 1); x += kWave) {
+        const uint32_t cl = x / (T - 1), t = x - cl * (T - 1) + 1;
+        const uint32_t col = bcol[t], b0 = cbs[cl] + cst[cl];
+        uint32_t lo = 0, hi = cst[cl + 1] - cst[cl];
+        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (b_colidx[b0 + mid] < col) lo = mid + 1; else hi = mid; }
+        cell[cl * TS + t] = lo;
+    }
+    if (lane < nc) { cell[lane * TS] = 0; cell[lane * TS + T] = len; }
+    wave_lds_sync();
+    OSP_PLAN_SMALL_MARK(3);   // (chunk, range) counts
+    // ---- 4. run descriptors in (range, chunk) order: G groups of S chunks per range, a lane per (group, range)
+    const uint32_t G = max(1u, min((uint32_t)kWave / T, 16u)), S = (nc + G - 1) / G;
+    const uint32_t g = lane / T, t = lane - g * T;
+    const bool on = g < G;
+    const uint32_t cl0 = min(nc, g * S), cl1 = min(nc, (g + 1) * S);
+    {
+        uint32_t sum = 0, nz = 0;   // (a small row holds less than 2^20 products and 64 chunks: 21 + 7 bits)
+        if (on)
+            for (uint32_t cl = cl0; cl < cl1; cl++) { const uint32_t c = cell[cl * TS + t + 1] - cell[cl * TS + t]; sum += c; nz += c != 0; }
+        psum[lane] = sum | (nz << 21);
+    }
+    wave_lds_sync();
+    uint32_t run = 0, nrun = 0, nzt = 0;   // products and runs of the range in the groups before this one; runs of the range
+    if (on)
+        for (uint32_t gg = 0; gg < G; gg++) {
+            const uint32_t p = psum[gg * T + t];
+            if (gg < g) { run += p & 0x1fffffu; nrun += p >> 21; }
+            nzt += p >> 21;
+        }
+    {
+        const uint32_t mine = lane < T ? nzt : 0u;
+        const uint32_t incl = wave_incl_scan(mine), total = wave_last(incl);
+        if (lane < T) nzc[lane] = incl - mine;
+        if (lane == 0) { nzc[T] = total; gp.rowruns[h] = total; }
+    }
+    wave_lds_sync();
+    const uint32_t rowbase = (uint32_t)gp.rdbase[h];
+    if (lane < Ta) {
+        const uint64_t v = vbase[h] + lane;
+        gp.vrun_off[v] = rowbase + nzc[min(lane, T)];
+        gp.vrun_end[v] = rowbase + nzc[min(lane + 1, T)];
+    }
+    if (on) {
+        const uint32_t rbase = q0 + roff[t];
+        RunDesc<V> *__restrict__ out = runs + rowbase + nzc[t];
+        for (uint32_t cl = cl0; cl < cl1; cl++) {
+            const uint32_t s0 = cell[cl * TS + t], c = cell[cl * TS + t + 1] - s0;
+            if (c) {
+                RunDesc<V> rd;
+                rd.dst = rbase + run;
+                rd.src = cbs[cl] + cst[cl] + s0;
+                rd.av = avs[cl];
+                out[nrun++] = rd;
+            }
+            run += c;
+        }
+    }
+    if (gp.mark_skipped && lane < nc) chunk_off[pa] = kChunkSkip;
+    OSP_PLAN_SMALL_MARK(4);   // prefixes and descriptors out
 }
 // ---- hub rows: the plan the multiply phase writes them by -----------------------------------------------------------------
 // (what a hub row is and what the multiply does with the cells: osp_kernels.h, "HUB rows")
