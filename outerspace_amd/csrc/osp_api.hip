@@ -584,6 +584,81 @@ static void note_variants(const Context *ctx, Result *res) {
     res->info.dense_atomic = ctx->dense_atomic[res->dtype == OSP_F64] ? 1u : 0u;
 }
 
+// ---- what the operations that make a CSR result from a CSR result share ----
+static void alloc_rowptr(Result *res, uint64_t M) { res->rowptr = (int64_t *)res->ctx->alloc((M + 1) * sizeof(int64_t)); }
+// (an empty result has arrays of one entry: its pointers are never null)
+template <class T>
+static void alloc_entries(Result *res, uint64_t nnz) {
+    res->colidx = (uint32_t *)res->ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(uint32_t));
+    res->vals = res->ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(T));
+}
+// the result of M rows without entries
+template <class T>
+static void empty_result(Result *res, uint64_t M, hipStream_t s) {
+    alloc_rowptr(res, M);
+    OSP_HIP(hipMemsetAsync(res->rowptr, 0, (M + 1) * sizeof(int64_t), s));
+    alloc_entries<T>(res, 0);
+}
+// The end of such a call: waits for its stream, then the result's size and the call's time.
+static void finish_csr(Result *res, EventPair &ev, uint64_t nnz, hipStream_t s) {
+    OSP_HIP(hipEventRecord(ev.b, s));
+    OSP_HIP(hipStreamSynchronize(s));
+    OSP_HIP(hipGetLastError());
+    res->info.nnz_c = nnz;
+    res->info.ms_total = ev.ms();
+}
+// The two passes of an operation that works row by row on M rows: count(cnt) launches what writes the entries each row
+// keeps to cnt[0..M), the scan of the counts is the result's row pointer, one read-back sizes the result, and write()
+// launches what fills it (not when it is empty).  Returns the result's nnz.
+template <class T, class Count, class Write>
+static uint64_t rows_two_pass(Scratch &sc, Result *res, uint64_t M, hipStream_t s, Count &&count, Write &&write) {
+    alloc_rowptr(res, M);
+    uint32_t *cnt = sc.get<uint32_t>(M + 1);
+    uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(M + 1));
+    count(cnt);
+    device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{cnt}, M, (uint64_t *)res->rowptr, tmp, s);
+    const uint64_t nnz = (uint64_t)d2h(res->rowptr + M, s);
+    alloc_entries<T>(res, nnz);
+    if (nnz) write();
+    return nnz;
+}
+// The compaction of `in` by one verdict bit per entry (osp_compact.h): flag(nchunks, bits) launches the filter's flag kernel,
+// then the scan, the call's ONE read-back (nnz, and whatever `more` adds to it), the result at its exact size, its row
+// pointer and its entries; with `fill` every kept entry gets that value and `in`'s values are not read.  An empty `in`
+// launches nothing.
+struct Compacted { uint64_t nnz; uint32_t launches; };
+template <class T, class Flag>
+static Compacted compact_by_bits(Scratch &sc, const Result *in, Result *res, hipStream_t s, Flag &&flag, const T *fill = nullptr,
+                                 const std::function<void(Gather &)> &more = nullptr) {
+    typedef typename std::conditional<sizeof(T) == 8, uint64_t, uint32_t>::type V;
+    const uint64_t M = in->info.M, nnz_in = in->info.nnz_c, nwords = (nnz_in + 63) / 64;
+    if (nnz_in == 0) {
+        empty_result<T>(res, M, s);
+        return {0, 0};
+    }
+    alloc_rowptr(res, M);
+    uint64_t *bits = sc.get<uint64_t>(nwords), *pos = sc.get<uint64_t>(nwords + 1);
+    uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(nwords));
+    flag(grid_for(nnz_in, (unsigned)kCompactChunk), bits);
+    uint32_t launches = 1 + device_exclusive_scan<LoadPopc64, uint64_t>(LoadPopc64{bits}, nwords, pos, tmp, s);
+    uint64_t nnz = 0;
+    Gather g(s);
+    g.add(&nnz, (const uint64_t *)pos + nwords);
+    if (more) more(g);
+    g.wait();
+    alloc_entries<T>(res, nnz);
+    compact_rowptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(in->rowptr, M, bits, pos, res->rowptr);
+    launches++;
+    if (nnz) {
+        V fill_bits = 0;
+        if (fill) memcpy(&fill_bits, fill, sizeof fill_bits);
+        const auto write = fill ? compact_write_kernel<V, true> : compact_write_kernel<V, false>;
+        write<<<grid_for(nnz_in, 256), 256, 0, s>>>(in->colidx, (const V *)in->vals, nnz_in, bits, pos, fill_bits, res->colidx, (V *)res->vals);
+        launches++;
+    }
+    return {nnz, launches};
+}
+
 // relu(C + bias) with the zeros dropped, as a new CSR (osp_epilogue.h)
 template <class T>
 static void bias_relu_impl(Context *ctx, const Result *in, Result *res, const T *bias_in, osp_memspace_t bias_space, int relu) {
@@ -594,23 +669,18 @@ static void bias_relu_impl(Context *ctx, const Result *in, Result *res, const T 
     const uint64_t M = in->info.M, N = in->info.N;
     const T *bias = bias_in ? to_device(sc, bias_in, N, bias_space, s) : nullptr;
     res->info = in->info;
-    res->rowptr = (int64_t *)ctx->alloc((M + 1) * sizeof(int64_t));
-    uint32_t *cnt = sc.get<uint32_t>(M + 1);
-    uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(M + 1));
     const unsigned grid = grid_for(std::max<uint64_t>(M, 1) * kWave, 256);
-    bias_relu_rows_kernel<T, false><<<grid, 256, 0, s>>>(in->rowptr, in->colidx, (const T *)in->vals, M, N, bias, relu, cnt, nullptr, nullptr, nullptr);
-    device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{cnt}, M, (uint64_t *)res->rowptr, tmp, s);
-    const uint64_t nnz = (uint64_t)d2h(res->rowptr + M, s);
-    res->colidx = (uint32_t *)ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(uint32_t));
-    res->vals = ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(T));
-    if (nnz)
-        bias_relu_rows_kernel<T, true><<<grid, 256, 0, s>>>(in->rowptr, in->colidx, (const T *)in->vals, M, N, bias, relu, nullptr, res->rowptr, res->colidx,
-                                                            (T *)res->vals);
-    OSP_HIP(hipEventRecord(ev.b, s));
-    OSP_HIP(hipStreamSynchronize(s));
-    OSP_HIP(hipGetLastError());
-    res->info.nnz_c = nnz;
-    res->info.ms_total = ev.ms();
+    const uint64_t nnz = rows_two_pass<T>(
+        sc, res, M, s,
+        [&](uint32_t *cnt) {
+            bias_relu_rows_kernel<T, false><<<grid, 256, 0, s>>>(in->rowptr, in->colidx, (const T *)in->vals, M, N, bias, relu, cnt, nullptr, nullptr,
+                                                                 nullptr);
+        },
+        [&] {
+            bias_relu_rows_kernel<T, true><<<grid, 256, 0, s>>>(in->rowptr, in->colidx, (const T *)in->vals, M, N, bias, relu, nullptr, res->rowptr,
+                                                                res->colidx, (T *)res->vals);
+        });
+    finish_csr(res, ev, nnz, s);
 }
 
 // ---- the conv stage of a sparse LeNet (osp_conv.h) ----
@@ -720,24 +790,18 @@ static void maxpool_impl(Context *ctx, const Result *in, Result *res, uint64_t N
     res->info.M = M;
     res->info.row_begin = 0;
     res->info.row_end = M;
-    res->rowptr = (int64_t *)ctx->alloc((M + 1) * sizeof(int64_t));
-    uint32_t *cnt = sc.get<uint32_t>(M + 1);
-    uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(M + 1));
     const unsigned grid = grid_for(std::max<uint64_t>(M, 1) * kWave, 256);
-    csr_maxpool_rows_kernel<T, false><<<grid, 256, 0, s>>>(in->rowptr, in->colidx, (const T *)in->vals, C, H, W, PH, PW, kh, kw, sh, sw, M, cnt,
-                                                           nullptr, nullptr, nullptr);
-    device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{cnt}, M, (uint64_t *)res->rowptr, tmp, s);
-    const uint64_t nnz = (uint64_t)d2h(res->rowptr + M, s);
-    res->colidx = (uint32_t *)ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(uint32_t));
-    res->vals = ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(T));
-    if (nnz)
-        csr_maxpool_rows_kernel<T, true><<<grid, 256, 0, s>>>(in->rowptr, in->colidx, (const T *)in->vals, C, H, W, PH, PW, kh, kw, sh, sw, M,
-                                                              nullptr, res->rowptr, res->colidx, (T *)res->vals);
-    OSP_HIP(hipEventRecord(ev.b, s));
-    OSP_HIP(hipStreamSynchronize(s));
-    OSP_HIP(hipGetLastError());
-    res->info.nnz_c = nnz;
-    res->info.ms_total = ev.ms();
+    const uint64_t nnz = rows_two_pass<T>(
+        sc, res, M, s,
+        [&](uint32_t *cnt) {
+            csr_maxpool_rows_kernel<T, false><<<grid, 256, 0, s>>>(in->rowptr, in->colidx, (const T *)in->vals, C, H, W, PH, PW, kh, kw, sh, sw, M, cnt,
+                                                                   nullptr, nullptr, nullptr);
+        },
+        [&] {
+            csr_maxpool_rows_kernel<T, true><<<grid, 256, 0, s>>>(in->rowptr, in->colidx, (const T *)in->vals, C, H, W, PH, PW, kh, kw, sh, sw, M,
+                                                                  nullptr, res->rowptr, res->colidx, (T *)res->vals);
+        });
+    finish_csr(res, ev, nnz, s);
 }
 
 // ---- the masked product (osp_masked.h) ----
@@ -886,17 +950,12 @@ static void masked_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
     device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{hit}, nm, pos, tmp, s);
     uint64_t nnz_c = 0, P = 0;
     { Gather g(s); g.add(&nnz_c, (const uint64_t *)pos + nm); g.add(&P, (const uint64_t *)products); g.wait(); }
-    res->rowptr = (int64_t *)ctx->alloc((M + 1) * sizeof(int64_t));
-    res->colidx = (uint32_t *)ctx->alloc(std::max<uint64_t>(nnz_c, 1) * sizeof(uint32_t));
-    res->vals = ctx->alloc(std::max<uint64_t>(nnz_c, 1) * sizeof(T));
+    alloc_rowptr(res, M);
+    alloc_entries<T>(res, nnz_c);
     masked_rowptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(m_rowptr, pos, M, res->rowptr);
     if (nnz_c) masked_scatter_kernel<T><<<grid_for(nm, 256), 256, 0, s>>>(hit, val, m_colidx, pos, nm, res->colidx, (T *)res->vals);
-    OSP_HIP(hipEventRecord(ev.b, s));
-    OSP_HIP(hipStreamSynchronize(s));
-    OSP_HIP(hipGetLastError());
-    res->info.nnz_c = nnz_c;
+    finish_csr(res, ev, nnz_c, s);
     res->info.partials = P;
-    res->info.ms_total = ev.ms();
     res->info.ms_ingest = ev_in.ms();
     res->info.ms_multiply_kernel = ev_k.ms();
     res->info.multiply_launches = launches;
@@ -938,41 +997,43 @@ static void inflate_prune_impl(Context *ctx, const Result *in, Result *res, cons
 
     // ---- pass 1: kept entries per row, then the output's row pointers ----
     res->info = in->info;
-    res->rowptr = (int64_t *)ctx->alloc((M + 1) * sizeof(int64_t));
-    uint32_t *cnt = sc.get<uint32_t>(M + 1), *nsurv = sc.get<uint32_t>(M + 1);
-    uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(M + 1));
+    uint32_t *nsurv = sc.get<uint32_t>(M + 1);
     constexpr uint64_t kSlice = 1ull << 30;   // rows per launch of the one-wave-per-row kernels (grid limit)
-    for (uint64_t r0 = 0; r0 < M; r0 += kSlice) {
-        mcl_count_kernel<T, kWave><<<(unsigned)std::min(kSlice, M - r0), kWave, 0, s>>>(in->rowptr, val, r0, M, nullptr, long_min, thr, step.max_per_row,
-                                                                                      nsurv, cnt, counters);
-        launches++;
-    }
-    if (n_long) {
-        mcl_count_kernel<T, kMclLongThreads><<<(unsigned)n_long, kMclLongThreads, 0, s>>>(in->rowptr, val, 0, M, long_rows, long_min, thr,
-                                                                                          step.max_per_row, nsurv, cnt, counters);
-        launches++;
-    }
-    device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{cnt}, M, (uint64_t *)res->rowptr, tmp, s);
-    const uint64_t nnz = (uint64_t)d2h(res->rowptr + M, s);
-    res->colidx = (uint32_t *)ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(uint32_t));
-    res->vals = ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(T));
-
-    // ---- pass 2: select, compact, inflate, normalise ----
-    OSP_HIP(hipEventRecord(ev_k.a, s));
-    if (nnz) {
-        for (uint64_t r0 = 0; r0 < M; r0 += kSlice) {
-            mcl_write_kernel<T, kWave><<<(unsigned)std::min(kSlice, M - r0), kWave, 0, s>>>(in->rowptr, in->colidx, val, r0, M, nullptr, long_min, thr, mode,
-                                                                                          power, nsurv, res->rowptr, res->colidx, (T *)res->vals, counters);
-            launches++;
-        }
-        if (n_long) {
-            mcl_write_kernel<T, kMclLongThreads><<<(unsigned)n_long, kMclLongThreads, 0, s>>>(in->rowptr, in->colidx, val, 0, M, long_rows, long_min, thr,
+    const uint64_t nnz = rows_two_pass<T>(
+        sc, res, M, s,
+        [&](uint32_t *cnt) {
+            for (uint64_t r0 = 0; r0 < M; r0 += kSlice) {
+                mcl_count_kernel<T, kWave><<<(unsigned)std::min(kSlice, M - r0), kWave, 0, s>>>(in->rowptr, val, r0, M, nullptr, long_min, thr,
+                                                                                              step.max_per_row, nsurv, cnt, counters);
+                launches++;
+            }
+            if (n_long) {
+                mcl_count_kernel<T, kMclLongThreads><<<(unsigned)n_long, kMclLongThreads, 0, s>>>(in->rowptr, val, 0, M, long_rows, long_min, thr,
+                                                                                                  step.max_per_row, nsurv, cnt, counters);
+                launches++;
+            }
+        },
+        // ---- pass 2: select, compact, inflate, normalise ----
+        [&] {
+            OSP_HIP(hipEventRecord(ev_k.a, s));
+            for (uint64_t r0 = 0; r0 < M; r0 += kSlice) {
+                mcl_write_kernel<T, kWave><<<(unsigned)std::min(kSlice, M - r0), kWave, 0, s>>>(in->rowptr, in->colidx, val, r0, M, nullptr, long_min, thr,
                                                                                               mode, power, nsurv, res->rowptr, res->colidx,
                                                                                               (T *)res->vals, counters);
-            launches++;
-        }
+                launches++;
+            }
+            if (n_long) {
+                mcl_write_kernel<T, kMclLongThreads><<<(unsigned)n_long, kMclLongThreads, 0, s>>>(in->rowptr, in->colidx, val, 0, M, long_rows, long_min,
+                                                                                                  thr, mode, power, nsurv, res->rowptr, res->colidx,
+                                                                                                  (T *)res->vals, counters);
+                launches++;
+            }
+            OSP_HIP(hipEventRecord(ev_k.b, s));
+        });
+    if (!nnz) {   // (no second pass: an empty interval)
+        OSP_HIP(hipEventRecord(ev_k.a, s));
+        OSP_HIP(hipEventRecord(ev_k.b, s));
     }
-    OSP_HIP(hipEventRecord(ev_k.b, s));
     uint64_t capped = 0, rescued = 0, chaos_bits = 0;
     {
         Gather g(s);
@@ -981,11 +1042,7 @@ static void inflate_prune_impl(Context *ctx, const Result *in, Result *res, cons
         g.add(&chaos_bits, (const uint64_t *)counters + MCL_CHAOS);
         g.wait();
     }
-    OSP_HIP(hipEventRecord(ev.b, s));
-    OSP_HIP(hipStreamSynchronize(s));
-    OSP_HIP(hipGetLastError());
-    res->info.nnz_c = nnz;
-    res->info.ms_total = ev.ms();
+    finish_csr(res, ev, nnz, s);
     *st = osp_mcl_stats_t{};
     st->nnz_in = nnz_in;
     st->nnz_out = nnz;
@@ -1013,7 +1070,6 @@ static void inflate_prune_impl(Context *ctx, const Result *in, Result *res, cons
 template <class T>
 static void apply_mask_impl(Context *ctx, const Result *in, Result *res, const int64_t *m_rowptr_in, const uint32_t *m_colidx_in,
                             osp_memspace_t space, int complement, int validate, osp_apply_mask_stats_t *st) {
-    typedef typename std::conditional<sizeof(T) == 8, uint64_t, uint32_t>::type V;
     hipStream_t s = ctx->stream;
     Scratch sc(ctx);
     EventPair ev;
@@ -1052,68 +1108,44 @@ static void apply_mask_impl(Context *ctx, const Result *in, Result *res, const i
     }
 
     res->info = in->info;
-    res->rowptr = (int64_t *)ctx->alloc((M + 1) * sizeof(int64_t));
-    uint64_t nnz = 0;
-    if (nnz_in == 0 || (have_nnz_m && nnz_m == 0)) {
-        // nothing to search: the result is empty, or (nothing is masked out) `in` itself
-        if (nnz_in && complement) {
-            nnz = nnz_in;
-            OSP_HIP(hipMemcpyAsync(res->rowptr, in->rowptr, (M + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-        } else {
-            OSP_HIP(hipMemsetAsync(res->rowptr, 0, (M + 1) * sizeof(int64_t), s));
-        }
-        res->colidx = (uint32_t *)ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(uint32_t));
-        res->vals = ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(T));
-        if (nnz) {
-            OSP_HIP(hipMemcpyAsync(res->colidx, in->colidx, nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-            OSP_HIP(hipMemcpyAsync(res->vals, in->vals, nnz * sizeof(T), hipMemcpyDeviceToDevice, s));
-        }
+    Compacted c{0, 0};
+    if (nnz_in && complement && have_nnz_m && nnz_m == 0) {
+        // nothing is masked out: `in` itself
+        c.nnz = nnz_in;
+        alloc_rowptr(res, M);
+        OSP_HIP(hipMemcpyAsync(res->rowptr, in->rowptr, (M + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        alloc_entries<T>(res, nnz_in);
+        OSP_HIP(hipMemcpyAsync(res->colidx, in->colidx, nnz_in * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        OSP_HIP(hipMemcpyAsync(res->vals, in->vals, nnz_in * sizeof(T), hipMemcpyDeviceToDevice, s));
+    } else if (have_nnz_m && nnz_m == 0) {
+        empty_result<T>(res, M, s);   // nothing to search for
     } else {
-        const uint64_t nwords = (nnz_in + 63) / 64;
-        uint64_t *bits = sc.get<uint64_t>(nwords), *pos = sc.get<uint64_t>(nwords + 1);
-        uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(nwords));
-        const unsigned nchunks = grid_for(nnz_in, (unsigned)kAmChunk);
-        apply_mask_flag_kernel<<<nchunks, kAmThreads, 0, s>>>(in->rowptr, in->colidx, M, nnz_in, m_rowptr, m_colidx, complement, bits);
-        device_exclusive_scan<LoadPopc64, uint64_t>(LoadPopc64{bits}, nwords, pos, tmp, s);
-        launches += 1 + ((nwords + kScanTile - 1) / kScanTile <= kScanSmallTiles ? 1 : 3);
-        {   // the call's one read-back
-            Gather g(s);
-            g.add(&nnz, (const uint64_t *)pos + nwords);
-            if (!have_nnz_m) g.add(&nnz_m, m_rowptr + M);
-            g.wait();
-        }
+        c = compact_by_bits<T>(
+            sc, in, res, s,
+            [&](unsigned nchunks, uint64_t *bits) {
+                apply_mask_flag_kernel<<<nchunks, kAmThreads, 0, s>>>(in->rowptr, in->colidx, M, nnz_in, m_rowptr, m_colidx, complement, bits);
+            },
+            nullptr, [&](Gather &g) { if (!have_nnz_m) g.add(&nnz_m, m_rowptr + M); });
         if (!have_nnz_m) check_nnz_m();
-        res->colidx = (uint32_t *)ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(uint32_t));
-        res->vals = ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(T));
-        apply_mask_rowptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(in->rowptr, M, bits, pos, res->rowptr);
-        launches++;
-        if (nnz) {
-            apply_mask_write_kernel<V><<<grid_for(nnz_in, 256), 256, 0, s>>>(in->colidx, (const V *)in->vals, nnz_in, bits, pos, res->colidx,
-                                                                               (V *)res->vals);
-            launches++;
-        }
+        launches += c.launches;
     }
-    OSP_HIP(hipEventRecord(ev.b, s));
-    OSP_HIP(hipStreamSynchronize(s));
-    OSP_HIP(hipGetLastError());
-    res->info.nnz_c = nnz;
-    res->info.ms_total = ev.ms();
+    finish_csr(res, ev, c.nnz, s);
     *st = osp_apply_mask_stats_t{};
     st->nnz_in = nnz_in;
     st->nnz_mask = (uint64_t)nnz_m;
-    st->nnz_out = nnz;
+    st->nnz_out = c.nnz;
     st->ms_total = res->info.ms_total;
     st->launches = launches;
     if (getenv("OSP_VERBOSE"))
         fprintf(stderr, "[osp] apply_mask%s M=%llu nnz %llu -> %llu (mask %llu) launches=%u %.3f ms\n", complement ? " (complement)" : "",
-                (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)nnz, (unsigned long long)nnz_m, launches, st->ms_total);
+                (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)c.nnz, (unsigned long long)nnz_m, launches, st->ms_total);
 }
 
 // ---- the entry filter of a CSR result (osp_select.h) ----
 template <class T, int OP = 0>
 static void launch_select_value(int op, unsigned grid, hipStream_t s, const T *val, uint64_t nnz, double threshold, uint64_t *bits) {
     if constexpr (OP <= SEL_NE) {
-        if (op == OP) select_flag_value_kernel<T, OP><<<grid, kAmThreads, 0, s>>>(val, nnz, threshold, bits);
+        if (op == OP) select_flag_value_kernel<T, OP><<<grid, kCompactThreads, 0, s>>>(val, nnz, threshold, bits);
         else launch_select_value<T, OP + 1>(op, grid, s, val, nnz, threshold, bits);
     }
 }
@@ -1121,75 +1153,44 @@ template <int OP = SEL_TRIL>
 static void launch_select_position(int op, unsigned grid, hipStream_t s, const int64_t *rowptr, const uint32_t *col, uint64_t M, uint64_t nnz,
                                    int64_t diag, uint64_t *bits) {
     if constexpr (OP < SEL_OPS) {
-        if (op == OP) select_flag_position_kernel<OP><<<grid, kAmThreads, 0, s>>>(rowptr, col, M, nnz, diag, bits);
+        if (op == OP) select_flag_position_kernel<OP><<<grid, kCompactThreads, 0, s>>>(rowptr, col, M, nnz, diag, bits);
         else launch_select_position<OP + 1>(op, grid, s, rowptr, col, M, nnz, diag, bits);
     }
 }
 
 template <class T>
 static void select_impl(Context *ctx, const Result *in, Result *res, const osp_select_t &sel, osp_select_stats_t *st) {
-    typedef typename std::conditional<sizeof(T) == 8, uint64_t, uint32_t>::type V;
     hipStream_t s = ctx->stream;
     Scratch sc(ctx);
     EventPair ev;
     OSP_HIP(hipEventRecord(ev.a, s));
     const uint64_t M = in->info.M, nnz_in = in->info.nnz_c;
-    uint32_t launches = 0;
     res->info = in->info;
-    res->rowptr = (int64_t *)ctx->alloc((M + 1) * sizeof(int64_t));
-    uint64_t nnz = 0;
-    if (nnz_in == 0) {
-        OSP_HIP(hipMemsetAsync(res->rowptr, 0, (M + 1) * sizeof(int64_t), s));
-        res->colidx = (uint32_t *)ctx->alloc(sizeof(uint32_t));
-        res->vals = ctx->alloc(sizeof(T));
-    } else {
-        const uint64_t nwords = (nnz_in + 63) / 64;
-        uint64_t *bits = sc.get<uint64_t>(nwords), *pos = sc.get<uint64_t>(nwords + 1);
-        uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(nwords));
-        const unsigned nchunks = grid_for(nnz_in, (unsigned)kAmChunk);
-        if (sel.op <= OSP_SELECT_NE) {
-            launch_select_value<T>(sel.op, nchunks, s, (const T *)in->vals, nnz_in, sel.threshold, bits);
-        } else {
-            // |col - row| < 2^32: a diagonal beyond +-2^33 selects what +-2^33 selects, and row + diag cannot overflow
-            const int64_t lim = (int64_t)1 << 33;
-            launch_select_position(sel.op, nchunks, s, in->rowptr, in->colidx, M, nnz_in, std::min(std::max(sel.diag, -lim), lim), bits);
-        }
-        device_exclusive_scan<LoadPopc64, uint64_t>(LoadPopc64{bits}, nwords, pos, tmp, s);
-        launches += 1 + ((nwords + kScanTile - 1) / kScanTile <= kScanSmallTiles ? 1 : 3);
-        nnz = d2h((const uint64_t *)pos + nwords, s);   // the call's one read-back
-        res->colidx = (uint32_t *)ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(uint32_t));
-        res->vals = ctx->alloc(std::max<uint64_t>(nnz, 1) * sizeof(T));
-        apply_mask_rowptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(in->rowptr, M, bits, pos, res->rowptr);
-        launches++;
-        if (nnz) {
-            if (sel.fill) {
-                // (a double beyond T's range has no defined conversion: it becomes the infinity of its sign)
-                const double fv = sel.fill_value;
-                const T fill = std::isfinite(fv) && std::fabs(fv) > (double)std::numeric_limits<T>::max()
-                                   ? (T)std::copysign((double)std::numeric_limits<T>::infinity(), fv) : (T)fv;
-                V fill_bits;
-                memcpy(&fill_bits, &fill, sizeof fill);
-                select_fill_kernel<V><<<grid_for(nnz_in, 256), 256, 0, s>>>(in->colidx, nnz_in, bits, pos, fill_bits, res->colidx, (V *)res->vals);
+    // (a double beyond T's range has no defined conversion: it becomes the infinity of its sign)
+    const double fv = sel.fill_value;
+    const T fill = std::isfinite(fv) && std::fabs(fv) > (double)std::numeric_limits<T>::max()
+                       ? (T)std::copysign((double)std::numeric_limits<T>::infinity(), fv) : (T)fv;
+    const Compacted c = compact_by_bits<T>(
+        sc, in, res, s,
+        [&](unsigned nchunks, uint64_t *bits) {
+            if (sel.op <= OSP_SELECT_NE) {
+                launch_select_value<T>(sel.op, nchunks, s, (const T *)in->vals, nnz_in, sel.threshold, bits);
             } else {
-                apply_mask_write_kernel<V><<<grid_for(nnz_in, 256), 256, 0, s>>>(in->colidx, (const V *)in->vals, nnz_in, bits, pos, res->colidx,
-                                                                                   (V *)res->vals);
+                // |col - row| < 2^32: a diagonal beyond +-2^33 selects what +-2^33 selects, and row + diag cannot overflow
+                const int64_t lim = (int64_t)1 << 33;
+                launch_select_position(sel.op, nchunks, s, in->rowptr, in->colidx, M, nnz_in, std::min(std::max(sel.diag, -lim), lim), bits);
             }
-            launches++;
-        }
-    }
-    OSP_HIP(hipEventRecord(ev.b, s));
-    OSP_HIP(hipStreamSynchronize(s));
-    OSP_HIP(hipGetLastError());
-    res->info.nnz_c = nnz;
-    res->info.ms_total = ev.ms();
+        },
+        sel.fill ? &fill : nullptr);
+    finish_csr(res, ev, c.nnz, s);
     *st = osp_select_stats_t{};
     st->nnz_in = nnz_in;
-    st->nnz_out = nnz;
+    st->nnz_out = c.nnz;
     st->ms_total = res->info.ms_total;
-    st->launches = launches;
+    st->launches = c.launches;
     if (getenv("OSP_VERBOSE"))
         fprintf(stderr, "[osp] select op=%d%s M=%llu nnz %llu -> %llu launches=%u %.3f ms\n", sel.op, sel.fill ? " (fill)" : "",
-                (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)nnz, launches, st->ms_total);
+                (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)c.nnz, c.launches, st->ms_total);
 }
 
 static void destroy_result(Result *r) {

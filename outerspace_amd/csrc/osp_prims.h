@@ -192,22 +192,23 @@ __global__ __launch_bounds__(kScanThreads) void scan_small_kernel(F f, uint64_t 
     if (threadIdx.x == 0) out[n] = carry;
 }
 
-// `tile_scratch` needs ceil(n / kScanTile) + 1 entries of TOut.
+// `tile_scratch` needs ceil(n / kScanTile) + 1 entries of TOut.  Returns the number of kernels it launched.
 template <class F, class TOut>
-inline void device_exclusive_scan(F f, uint64_t n, TOut *out, TOut *tile_scratch,
-                                  hipStream_t stream) {
+inline uint32_t device_exclusive_scan(F f, uint64_t n, TOut *out, TOut *tile_scratch,
+                                      hipStream_t stream) {
     if (n == 0) {
         scan_empty_kernel<TOut><<<1, 1, 0, stream>>>(out);
-        return;
+        return 1;
     }
     const uint64_t ntiles = (n + kScanTile - 1) / kScanTile;
     if (ntiles <= kScanSmallTiles) {
         scan_small_kernel<F, TOut><<<1, kScanThreads, 0, stream>>>(f, n, out);
-        return;
+        return 1;
     }
     scan_tile_sums_kernel<F, TOut><<<(unsigned)ntiles, kScanThreads, 0, stream>>>(f, n, tile_scratch);
     scan_tile_offsets_kernel<TOut><<<1, kScanThreads, 0, stream>>>(tile_scratch, ntiles);
     scan_tiles_kernel<F, TOut><<<(unsigned)ntiles, kScanThreads, 0, stream>>>(f, n, tile_scratch, out);
+    return 3;
 }
 inline uint64_t scan_scratch_entries(uint64_t n) { return (n + kScanTile - 1) / kScanTile + 2; }
 

@@ -2,6 +2,7 @@
 equal (compared as unsigned integers), both senses, f32 and f64, host and device masks, on inputs built for every rule of
 the filter, on a product's result, against the masked product, through the result's other entry points, and its errors."""
 import ctypes
+import functools
 import os
 import re
 
@@ -18,9 +19,9 @@ from tests import bfs_model as model
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_SRC = open(os.path.join(ROOT, "outerspace_amd", "csrc", "osp_apply_mask.h")).read()
-# the filter's unit of work: kAmThreads * kAmRounds consecutive entries of `in`
-CHUNK = int(re.search(r"kAmThreads\s*=\s*(\d+)", _SRC).group(1)) * int(re.search(r"kAmRounds\s*=\s*(\d+)", _SRC).group(1))
+_SRC = open(os.path.join(ROOT, "outerspace_amd", "csrc", "osp_compact.h")).read()
+# the filter's unit of work: kCompactThreads * kCompactRounds consecutive entries of `in`
+CHUNK = int(re.search(r"kCompactThreads\s*=\s*(\d+)", _SRC).group(1)) * int(re.search(r"kCompactRounds\s*=\s*(\d+)", _SRC).group(1))
 DEV = "cuda:0"
 
 
@@ -441,5 +442,44 @@ def test_fifty_back_to_back_calls_give_the_same_arrays(mctx):
                 assert np.array_equal(got[0], _[0]) and np.array_equal(got[1], _[1]) and np.array_equal(got[2], _bits(_[2]))
             else:
                 assert all(np.array_equal(x, y) for x, y in zip(got, first[complement])), i
+    finally:
+        src.close()
+
+
+# ---- the launches a call reports ------------------------------------------------------------------------------------------------
+# A filter of a non-empty `in` launches its flag kernel, the scan over the verdict words, the row-pointer kernel and, when
+# anything is kept, the write kernel.  The scan is one kernel up to 16 tiles of 2048 words of 64 entries and three above.
+SCAN_SMALL_MAX = 16 * 2048 * 64
+
+
+@functools.lru_cache(maxsize=None)
+def _launch_inputs():
+    """(ncol, csr, kernels of the scan) for the largest input of the one-kernel scan and the smallest of the three-kernel one."""
+    ncol = 1 << 20
+    lengths = [700000, 0, SCAN_SMALL_MAX - 1400000, 700000]
+    return tuple((ncol, _csr_from_lengths(lengths + extra, ncol, np.float32, seed=51, lo=0), scan) for extra, scan in (([], 1), ([1], 3)))
+
+
+def test_apply_mask_reports_its_launches(mctx):
+    for (ncol, csr, scan), nnz in zip(_launch_inputs(), (SCAN_SMALL_MAX, SCAN_SMALL_MAX + 1)):
+        assert len(csr[1]) == nnz
+        src = _upload(mctx, ncol, csr)
+        try:
+            # the mask is `in`'s own pattern: everything is kept, or (complement) nothing
+            for complement, validate, want in ((False, False, 1 + scan + 1 + 1), (True, False, 1 + scan + 1), (False, True, 3 + 1 + scan + 1 + 1)):
+                res, st = src.apply_mask(src, complement=complement, validate=validate)
+                try:
+                    assert st["nnz_out"] == res.nnz == (0 if complement else nnz)
+                    assert st["launches"] == want, (nnz, complement, validate, st["launches"], want)
+                finally:
+                    res.close()
+        finally:
+            src.close()
+    ncol, csr, mask = _simple("empty_in")(np.float32)
+    src = _upload(mctx, ncol, csr)
+    try:
+        res, st = src.apply_mask(mask, space="host")
+        assert st["launches"] == 0 and res.nnz == 0
+        res.close()
     finally:
         src.close()

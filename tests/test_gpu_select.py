@@ -411,3 +411,32 @@ def test_fifty_back_to_back_calls_give_the_same_arrays(mctx):
         assert np.array_equal(_bits(src.to_host()[2]), _bits(csr[2]))
     finally:
         src.close()
+
+
+def test_select_reports_its_launches(mctx):
+    """Flag, scan, row pointers and, when anything is kept, the write kernel (am.SCAN_SMALL_MAX: where the scan takes three)."""
+    for (ncol, csr, scan), nnz in zip(am._launch_inputs(), (am.SCAN_SMALL_MAX, am.SCAN_SMALL_MAX + 1)):
+        assert len(csr[1]) == nnz
+        src = am._upload(mctx, ncol, csr)
+        try:
+            for op, kw, fill, kept in (("gt", {"threshold": 0.0}, None, "some"), ("gt", {"threshold": 0.0}, 1.0, "some"),
+                                       ("tril", {"diag": ncol}, None, "all"), ("gt", {"threshold": 1e30}, None, "none"),
+                                       ("triu", {"diag": ncol}, 1.0, "none")):
+                res, st = src.select(op, fill=fill, **kw)
+                try:
+                    assert st["nnz_out"] == res.nnz
+                    assert {"some": 0 < res.nnz < nnz, "all": res.nnz == nnz, "none": res.nnz == 0}[kept]
+                    want = 1 + scan + 1 + (kept != "none")
+                    assert st["launches"] == want, (nnz, op, fill, st["launches"], want)
+                finally:
+                    res.close()
+        finally:
+            src.close()
+    ncol, csr = _input("empty_in", np.float32)
+    src = am._upload(mctx, ncol, csr)
+    try:
+        res, st = src.select("ne", 0.0)
+        assert st["launches"] == 0 and res.nnz == 0
+        res.close()
+    finally:
+        src.close()
