@@ -116,6 +116,24 @@ class SelectStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+EWISE_MODES = {"union": 0, "intersect": 1}  # osp_ewise_mode_t
+EWISE_OPS = {"plus": 0, "times": 1, "min": 2, "max": 3, "first": 4, "second": 5, "minus": 6, "div": 7}  # osp_ewise_op_t
+
+
+class Ewise(C.Structure):
+    """osp_ewise_t"""
+    _fields_ = [("mode", C.c_int32), ("op", C.c_int32), ("reserved", C.c_uint32 * 8)]
+
+
+class EwiseStats(C.Structure):
+    """osp_ewise_stats_t"""
+    _fields_ = [("nnz_a", C.c_uint64), ("nnz_b", C.c_uint64), ("nnz_both", C.c_uint64), ("nnz_out", C.c_uint64),
+                ("ms_total", C.c_float), ("launches", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -168,6 +186,9 @@ APPLY_MASK_EXPORTS = ["osp_csr_apply_mask"]
 
 # every symbol include/outerspace_spgemm_select.h declares
 SELECT_EXPORTS = ["osp_csr_select"]
+
+# every symbol include/outerspace_spgemm_ewise.h declares
+EWISE_EXPORTS = ["osp_csr_ewise"]
 
 _lib = None
 
@@ -249,6 +270,7 @@ def lib():
     L.osp_csr_inflate_prune.argtypes = [vp, C.POINTER(MclStep), i32, C.POINTER(vp), C.POINTER(MclStats)]
     L.osp_csr_apply_mask.argtypes = [vp, u64, u64, vp, vp, i32, i32, i32, C.POINTER(vp), C.POINTER(ApplyMaskStats)]
     L.osp_csr_select.argtypes = [vp, C.POINTER(Select), C.POINTER(vp), C.POINTER(SelectStats)]
+    L.osp_csr_ewise.argtypes = [vp, vp, C.POINTER(Ewise), C.POINTER(vp), C.POINTER(EwiseStats)]
     _lib = L
     return L
 

@@ -25,6 +25,7 @@
 #include "../../include/outerspace_spgemm_mcl.h"
 #include "../../include/outerspace_spgemm_apply_mask.h"
 #include "../../include/outerspace_spgemm_select.h"
+#include "../../include/outerspace_spgemm_ewise.h"
 #include "osp_internal.h"
 #include "osp_kernels.h"
 #include "osp_split.h"
@@ -35,6 +36,7 @@
 #include "osp_mcl.h"
 #include "osp_apply_mask.h"
 #include "osp_select.h"
+#include "osp_ewise.h"
 
 namespace osp {
 
@@ -622,38 +624,47 @@ static uint64_t rows_two_pass(Scratch &sc, Result *res, uint64_t M, hipStream_t 
     if (nnz) write();
     return nnz;
 }
-// The compaction of `in` by one verdict bit per entry (osp_compact.h): flag(nchunks, bits) launches the filter's flag kernel,
-// then the scan, the call's ONE read-back (nnz, and whatever `more` adds to it), the result at its exact size, its row
-// pointer and its entries; with `fill` every kept entry gets that value and `in`'s values are not read.  An empty `in`
+// The first two passes of osp_compact.h over `n` (> 0) entries: flag(nchunks, bits) launches the flag kernel, then the scan of
+// the words' popcounts and the call's ONE read-back (the number of set bits, and whatever `more` adds to it).
+struct BitScan { uint64_t *bits, *pos; uint64_t count; uint32_t launches; };
+template <class Flag>
+static BitScan flag_and_scan(Scratch &sc, uint64_t n, hipStream_t s, Flag &&flag, const std::function<void(Gather &)> &more = nullptr) {
+    const uint64_t nwords = (n + 63) / 64;
+    BitScan b{sc.get<uint64_t>(nwords), sc.get<uint64_t>(nwords + 1), 0, 0};
+    uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(nwords));
+    flag(grid_for(n, (unsigned)kCompactChunk), b.bits);
+    b.launches = 1 + device_exclusive_scan<LoadPopc64, uint64_t>(LoadPopc64{b.bits}, nwords, b.pos, tmp, s);
+    Gather g(s);
+    g.add(&b.count, (const uint64_t *)b.pos + nwords);
+    if (more) more(g);
+    g.wait();
+    return b;
+}
+// The compaction of `in` by one verdict bit per entry (osp_compact.h): flag_and_scan, then the result at its exact size, its
+// row pointer and its entries; with `fill` every kept entry gets that value and `in`'s values are not read.  An empty `in`
 // launches nothing.
 struct Compacted { uint64_t nnz; uint32_t launches; };
 template <class T, class Flag>
 static Compacted compact_by_bits(Scratch &sc, const Result *in, Result *res, hipStream_t s, Flag &&flag, const T *fill = nullptr,
                                  const std::function<void(Gather &)> &more = nullptr) {
     typedef typename std::conditional<sizeof(T) == 8, uint64_t, uint32_t>::type V;
-    const uint64_t M = in->info.M, nnz_in = in->info.nnz_c, nwords = (nnz_in + 63) / 64;
+    const uint64_t M = in->info.M, nnz_in = in->info.nnz_c;
     if (nnz_in == 0) {
         empty_result<T>(res, M, s);
         return {0, 0};
     }
     alloc_rowptr(res, M);
-    uint64_t *bits = sc.get<uint64_t>(nwords), *pos = sc.get<uint64_t>(nwords + 1);
-    uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(nwords));
-    flag(grid_for(nnz_in, (unsigned)kCompactChunk), bits);
-    uint32_t launches = 1 + device_exclusive_scan<LoadPopc64, uint64_t>(LoadPopc64{bits}, nwords, pos, tmp, s);
-    uint64_t nnz = 0;
-    Gather g(s);
-    g.add(&nnz, (const uint64_t *)pos + nwords);
-    if (more) more(g);
-    g.wait();
+    const BitScan b = flag_and_scan(sc, nnz_in, s, flag, more);
+    const uint64_t nnz = b.count;
+    uint32_t launches = b.launches;
     alloc_entries<T>(res, nnz);
-    compact_rowptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(in->rowptr, M, bits, pos, res->rowptr);
+    compact_rowptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(in->rowptr, M, b.bits, b.pos, res->rowptr);
     launches++;
     if (nnz) {
         V fill_bits = 0;
         if (fill) memcpy(&fill_bits, fill, sizeof fill_bits);
         const auto write = fill ? compact_write_kernel<V, true> : compact_write_kernel<V, false>;
-        write<<<grid_for(nnz_in, 256), 256, 0, s>>>(in->colidx, (const V *)in->vals, nnz_in, bits, pos, fill_bits, res->colidx, (V *)res->vals);
+        write<<<grid_for(nnz_in, 256), 256, 0, s>>>(in->colidx, (const V *)in->vals, nnz_in, b.bits, b.pos, fill_bits, res->colidx, (V *)res->vals);
         launches++;
     }
     return {nnz, launches};
@@ -1193,6 +1204,106 @@ static void select_impl(Context *ctx, const Result *in, Result *res, const osp_s
                 (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)c.nnz, c.launches, st->ms_total);
 }
 
+// ---- the element-wise union / intersection of two CSR results (osp_ewise.h) ----
+template <class T, int OP = 0>
+static void launch_ewise_union_a(int op, unsigned grid, hipStream_t s, const Result *a, const Result *b, const BitScan &h, Result *res) {
+    typedef ValueBits<T> V;
+    if constexpr (OP <= EW_SECOND) {
+        if (op == OP)
+            ewise_union_write_a_kernel<T, OP><<<grid, kCompactThreads, 0, s>>>(a->rowptr, a->colidx, (const V *)a->vals, a->info.M, a->info.nnz_c,
+                                                                              b->rowptr, b->colidx, (const V *)b->vals, h.bits, h.pos, res->colidx,
+                                                                              (V *)res->vals);
+        else launch_ewise_union_a<T, OP + 1>(op, grid, s, a, b, h, res);
+    }
+}
+template <class T, int OP = 0>
+static void launch_ewise_intersect(int op, unsigned grid, hipStream_t s, const Result *a, const Result *b, const BitScan &h, const uint32_t *qpos,
+                                   Result *res) {
+    typedef ValueBits<T> V;
+    if constexpr (OP < EW_OPS) {
+        if (op == OP)
+            ewise_intersect_write_kernel<T, OP><<<grid, 256, 0, s>>>(a->colidx, (const V *)a->vals, a->info.nnz_c, (const V *)b->vals, h.bits, h.pos,
+                                                                     qpos, res->colidx, (V *)res->vals);
+        else launch_ewise_intersect<T, OP + 1>(op, grid, s, a, b, h, qpos, res);
+    }
+}
+
+template <class T>
+static void copy_csr(const Result *in, Result *res, hipStream_t s) {
+    const uint64_t M = in->info.M, nnz = in->info.nnz_c;
+    alloc_rowptr(res, M);
+    OSP_HIP(hipMemcpyAsync(res->rowptr, in->rowptr, (M + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    alloc_entries<T>(res, nnz);
+    OSP_HIP(hipMemcpyAsync(res->colidx, in->colidx, nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    OSP_HIP(hipMemcpyAsync(res->vals, in->vals, nnz * sizeof(T), hipMemcpyDeviceToDevice, s));
+}
+
+template <class T>
+static void ewise_impl(Context *ctx, const Result *a, const Result *b, Result *res, const osp_ewise_t &ew, osp_ewise_stats_t *st) {
+    typedef ValueBits<T> V;
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint64_t M = a->info.M, nnz_a = a->info.nnz_c, nnz_b = b->info.nnz_c;
+    const bool uni = ew.mode == OSP_EWISE_UNION;
+    res->info = a->info;
+    uint64_t nnz_both = 0, nnz_out = 0;
+    uint32_t launches = 0;
+    if (M == 0 || (uni ? nnz_a + nnz_b == 0 : nnz_a == 0 || nnz_b == 0)) {
+        empty_result<T>(res, M, s);
+    } else if (nnz_a == 0 || nnz_b == 0) {
+        // a union with an empty side: the other side
+        copy_csr<T>(nnz_a ? a : b, res, s);
+        nnz_out = nnz_a + nnz_b;
+    } else if (uni) {
+        // the flag runs over b: hitsB, and every entry of b's lower bound in a
+        uint32_t *qpos = sc.get<uint32_t>(nnz_b);
+        alloc_rowptr(res, M);
+        const BitScan h = flag_and_scan(sc, nnz_b, s, [&](unsigned nchunks, uint64_t *bits) {
+            ewise_flag_kernel<<<nchunks, kCompactThreads, 0, s>>>(b->rowptr, b->colidx, M, nnz_b, a->rowptr, a->colidx, bits, qpos);
+        });
+        nnz_both = h.count;
+        nnz_out = nnz_a + nnz_b - nnz_both;
+        alloc_entries<T>(res, nnz_out);
+        ewise_union_rowptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(a->rowptr, b->rowptr, M, h.bits, h.pos, res->rowptr);
+        launches = h.launches + 2;
+        if (nnz_both < nnz_b) {   // (else b has no entry of its own)
+            ewise_union_write_b_kernel<V><<<grid_for(nnz_b, 256), 256, 0, s>>>(b->colidx, (const V *)b->vals, nnz_b, h.bits, h.pos, qpos, res->colidx,
+                                                                               (V *)res->vals);
+            launches++;
+        }
+        launch_ewise_union_a<T>(ew.op, grid_for(nnz_a, (unsigned)kCompactChunk), s, a, b, h, res);
+    } else {
+        // the flag runs over a: the common entries are a's with their bit set, b's value is at the stored lower bound
+        uint32_t *qpos = sc.get<uint32_t>(nnz_a);
+        alloc_rowptr(res, M);
+        const BitScan h = flag_and_scan(sc, nnz_a, s, [&](unsigned nchunks, uint64_t *bits) {
+            ewise_flag_kernel<<<nchunks, kCompactThreads, 0, s>>>(a->rowptr, a->colidx, M, nnz_a, b->rowptr, b->colidx, bits, qpos);
+        });
+        nnz_both = nnz_out = h.count;
+        alloc_entries<T>(res, nnz_out);
+        compact_rowptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(a->rowptr, M, h.bits, h.pos, res->rowptr);
+        launches = h.launches + 1;
+        if (nnz_out) {
+            launch_ewise_intersect<T>(ew.op, grid_for(nnz_a, 256), s, a, b, h, qpos, res);
+            launches++;
+        }
+    }
+    finish_csr(res, ev, nnz_out, s);
+    *st = osp_ewise_stats_t{};
+    st->nnz_a = nnz_a;
+    st->nnz_b = nnz_b;
+    st->nnz_both = nnz_both;
+    st->nnz_out = nnz_out;
+    st->ms_total = res->info.ms_total;
+    st->launches = launches;
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] ewise %s op=%d M=%llu nnz %llu , %llu -> %llu (both %llu) launches=%u %.3f ms\n", uni ? "union" : "intersect", ew.op,
+                (unsigned long long)M, (unsigned long long)nnz_a, (unsigned long long)nnz_b, (unsigned long long)nnz_out,
+                (unsigned long long)nnz_both, launches, st->ms_total);
+}
+
 static void destroy_result(Result *r) {
     if (!r) return;
     if (r->ctx) {
@@ -1464,6 +1575,31 @@ int osp_csr_select(osp_result_t in_, const osp_select_t *sel, osp_result_t *out,
         osp_select_stats_t st{};
         const int rc = new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {
             select_impl<decltype(tag)>(in->ctx, in, res, *sel, &st);
+        });
+        if (stats) *stats = st;
+        return rc;
+    });
+}
+
+int osp_csr_ewise(osp_result_t a_, osp_result_t b_, const osp_ewise_t *ew, osp_result_t *out, osp_ewise_stats_t *stats) {
+    Result *a = (Result *)a_, *b = (Result *)b_;
+    if (!a || !b || !ew || !out) return fail(OSP_ERR_ARG, "null argument");
+    if (a->partials || b->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
+    return guard([&] {
+        if (ew->mode != OSP_EWISE_UNION && ew->mode != OSP_EWISE_INTERSECT) throw Error(OSP_ERR_ARG, "ewise: mode is not one of osp_ewise_mode_t");
+        if (ew->op < OSP_EWISE_PLUS || ew->op > OSP_EWISE_DIV) throw Error(OSP_ERR_ARG, "ewise: op is not one of osp_ewise_op_t");
+        if (ew->mode == OSP_EWISE_UNION && (ew->op == OSP_EWISE_MINUS || ew->op == OSP_EWISE_DIV))
+            throw Error(OSP_ERR_ARG, "ewise: MINUS and DIV are not defined for a union (an entry of b alone would be copied as it is)");
+        for (uint32_t w : ew->reserved)
+            if (w) throw Error(OSP_ERR_ARG, "ewise: reserved words must be 0");
+        if (a->ctx != b->ctx) throw Error(OSP_ERR_ARG, "ewise: the operands belong to different contexts");
+        if (a->info.M != b->info.M || a->info.N != b->info.N) throw Error(OSP_ERR_ARG, "ewise: the operands' shapes differ");
+        if (a->dtype != b->dtype) throw Error(OSP_ERR_ARG, "ewise: the operands' dtypes differ");
+        if (a->info.nnz_c >= 0xffffffffull || b->info.nnz_c >= 0xffffffffull)
+            throw Error(OSP_ERR_ARG, "ewise: operands with >= 2^32 - 1 non-zeros are not supported");
+        osp_ewise_stats_t st{};
+        const int rc = new_result(a->ctx, a->dtype, out, [&](auto tag, Result *res) {
+            ewise_impl<decltype(tag)>(a->ctx, a, b, res, *ew, &st);
         });
         if (stats) *stats = st;
         return rc;

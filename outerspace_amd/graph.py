@@ -2,7 +2,8 @@
 clustering on the plain one with ``osp_csr_inflate_prune`` between two expansions (``markov_cluster``), and traversals
 that use both with the mask filter ``osp_csr_apply_mask`` between two levels (``bfs_levels``, ``betweenness_centrality``),
 and edge support and k-truss on the masked product with the entry filter ``osp_csr_select`` between two rounds
-(``edge_support``, ``k_truss``, ``truss_decomposition``, at the end).
+(``edge_support``, ``k_truss``, ``truss_decomposition``, at the end), and personalised PageRank, which sums a series of
+products with the element-wise union ``osp_csr_ewise`` (``personalized_pagerank``).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -250,12 +251,27 @@ def _device_mask_filter(product, visited):
     return product.apply_mask(visited, complement=True)
 
 
-def _bfs_forward(ctx, device, adj, src, max_levels=None, keep_levels=False, mask_filter=_device_mask_filter):
+def _device_union(ctx, visited, new):
+    """V + Nx of a traversal by the element-wise union: the patterns are disjoint, so no value is computed.  The traversals'
+    default: measured at a tenth of ``_sort_union``'s time (MEASUREMENTS.md section 0h)."""
+    U, st = visited.ewise(new, "union", "first")
+    return U, st["ms_total"]
+
+
+def _sort_union(ctx, visited, new):
+    """The same union by the sorting merge of two CSR parts, the default before osp_csr_ewise (tools/time_bfs.py --sort-union)."""
+    S, n = visited.shape
+    U = ctx.merge_csr_parts_device(np.float64, S, n, [visited.device_ptrs(), new.device_ptrs()])
+    return U, U.info["ms_total"]
+
+
+def _bfs_forward(ctx, device, adj, src, max_levels=None, keep_levels=False, mask_filter=_device_mask_filter, union=_device_union):
     """The forward sweep both traversals share.  Returns (level, sigma, info, levels): the dense int32 / float64
     [len(src), n] tensors on `device`, the per-level lists, and -- with keep_levels -- per level d = 0..D the pair
     (N_d as a CsrResult, its entries' positions row * n + col in the dense arrays); the caller closes those results.
     ``mask_filter(product, visited) -> (CsrResult, stats)`` is the step between the product and the union
-    (tools/time_bfs.py --host-mask passes the host round trip)."""
+    (tools/time_bfs.py --host-mask passes the host round trip); ``union(ctx, visited, new) -> (CsrResult, device ms)`` is the
+    step after it, ``_device_union`` or ``_sort_union`` (tools/time_bfs.py --sort-union passes the latter)."""
     from .sparse_util import _result_as_input
     S, n = int(src.size), adj.n
     level = torch.full((S, n), -1, dtype=torch.int32, device=device)
@@ -301,11 +317,11 @@ def _bfs_forward(ctx, device, adj, src, max_levels=None, keep_levels=False, mask
                 info["ms_union"].append(0.0)
                 break
             try:
-                U = ctx.merge_csr_parts_device(np.float64, S, n, [V.device_ptrs(), Nx.device_ptrs()])
+                U, ms_union = union(ctx, V, Nx)
             except Exception:
                 Nx.close()
                 raise
-            info["ms_union"].append(U.info["ms_total"])
+            info["ms_union"].append(ms_union)
             info["levels"] = d
             torch.cuda.synchronize(device)   # torch holds views of F's arrays: nothing of it is in flight when they go back to the pool
             del a
@@ -409,6 +425,98 @@ def betweenness_centrality(rows, cols, n=None, sources=None, *, batch=64, ctx=No
             for res, _ in levels:
                 res.close()
     return bc.cpu().numpy()
+
+
+# ---- personalised PageRank ---------------------------------------------------------------------------------
+def ppr_steps(alpha, tol, max_iter=None):
+    """The number of steps K of ``personalized_pagerank``: the smallest k with alpha^(k+1) < tol (what the series' tail
+    beyond step k sums to), capped by ``max_iter``."""
+    alpha, tol = float(alpha), float(tol)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("alpha must lie in (0, 1)")
+    if not tol > 0.0:
+        raise ValueError("tol must be positive")
+    k = 0
+    while alpha ** (k + 1) >= tol:
+        k += 1
+    return k if max_iter is None else min(k, max(int(max_iter), 0))
+
+
+def personalized_pagerank(rows, cols, n=None, sources=(0,), *, alpha=0.85, tol=1e-6, max_iter=None, prune=0.0, ctx=None):
+    """Personalised PageRank from every vertex of ``sources`` at once on the undirected graph with edges (rows[e], cols[e])
+    on vertices [0, n), every step on the GPU, float64: the truncated series  ppr = (1 - alpha) sum_{k=0..K} alpha^k e_s P^k
+    with P = D^-1 Adj (row-stochastic, ``symmetric_adjacency``).  With the term F (one row per source) and the sum PI as CSR
+    results, a step is  F <- F @ (alpha P)  (the library's product, F handed over in HBM; the operand holds alpha / deg),
+    with ``prune > 0``  F <- F.select("ge", prune),  and  PI <- PI.ewise(F, "union", "plus").  K = ``ppr_steps(alpha, tol,
+    max_iter)`` is fixed before the loop; the loop ends early only when F is empty.
+
+    Returns (ppr, info): ``ppr`` float64 [len(sources), n]; without pruning a row sums to 1 - alpha^(K+1) (an isolated
+    source keeps 1 - alpha on itself and nothing else).  ``info`` = iterations (steps taken), steps (K), and per step the
+    lists frontier_nnz (entries of F going into the product), nnz_result (entries of PI after it), ms_product, ms_union,
+    ms_select (device times; 0 where the step did not run).  Duplicate sources are independent rows; a source out of range
+    is a ValueError.  rows / cols: torch tensors (any device; the plumbing runs on cuda:ctx.device) or array-likes."""
+    from .sparse_util import _result_as_input
+    K = ppr_steps(alpha, tol, max_iter)
+    alpha, prune = float(alpha), float(prune)
+    ctx = ctx or _S.default_context()
+    device = torch.device("cuda", ctx.device)
+    adj = _Adjacency(rows, cols, n, device)
+    n = adj.n
+    src = _check_sources(sources, n)
+    S = int(src.size)
+    info = {"iterations": 0, "steps": K, "frontier_nnz": [], "nnz_result": [], "ms_product": [], "ms_union": [], "ms_select": []}
+    ppr = torch.zeros((S, n), dtype=torch.float64, device=device)
+    if S == 0 or n == 0:
+        return ppr.cpu().numpy(), info
+    # alpha P as the product's COO operand: entry (u, v) holds alpha / deg(u)
+    deg = (adj.rowptr[1:] - adj.rowptr[:-1]).to(torch.float64)
+    w = (alpha / deg)[adj.rows.to(torch.int64)]
+    b_ptrs = tuple(t.data_ptr() if adj.nnz else 0 for t in (adj.rows, adj.cols, w))
+    rp0 = torch.arange(S + 1, dtype=torch.int64, device=device)
+    c0 = torch.as_tensor(src, device=device).to(torch.int32)
+    v0 = torch.full((S,), 1.0 - alpha, dtype=torch.float64, device=device)
+    torch.cuda.synchronize(device)   # the library works on its own stream
+    # the sources as library CSR results: the merge of ONE part is the part itself.  F = the series' term, PI = its sum
+    part = [(rp0.data_ptr(), c0.data_ptr(), v0.data_ptr())]
+    F = PI = a = None
+    try:
+        F = ctx.merge_csr_parts_device(np.float64, S, n, part)
+        PI = ctx.merge_csr_parts_device(np.float64, S, n, part)
+        for _ in range(K):
+            a = _result_as_input(F, device)
+            P = ctx.spgemm_coo_device(np.float64, S, n, n, a.nnz, (a.rows.data_ptr(), a.cols.data_ptr(), a.vals.data_ptr()), adj.nnz, b_ptrs)
+            info["frontier_nnz"].append(a.nnz)
+            info["ms_product"].append(P.info["ms_total"])
+            torch.cuda.synchronize(device)   # torch holds views of F's arrays: nothing of it is in flight when they go back to the pool
+            a = None
+            F.close()
+            F = P
+            ms_select = 0.0
+            if prune > 0.0:
+                F, st = P.select("ge", prune)
+                P.close()
+                ms_select = st["ms_total"]
+            info["ms_select"].append(ms_select)
+            info["iterations"] += 1
+            if F.nnz == 0:
+                info["ms_union"].append(0.0)
+                info["nnz_result"].append(PI.nnz)
+                break
+            U, st = PI.ewise(F, "union", "plus")
+            PI.close()
+            PI = U
+            info["ms_union"].append(st["ms_total"])
+            info["nnz_result"].append(PI.nnz)
+        a = _result_as_input(PI, device)
+        ppr.view(-1)[a.rows.to(torch.int64)[:a.nnz] * n + a.cols.to(torch.int64)] = a.vals
+    finally:
+        torch.cuda.synchronize(device)
+        a = None
+        if F is not None:
+            F.close()
+        if PI is not None:
+            PI.close()
+    return ppr.cpu().numpy(), info
 
 
 # ---- edge support, k-truss (DESIGN.md section 12) -------------------------------------------------------------------------------

@@ -168,6 +168,39 @@ class CsrResult:
         _lib.check(_lib.lib().osp_csr_select(self._h, C.byref(sel), C.byref(h), C.byref(stats)))
         return CsrResult(self._ctx, h), stats.as_dict()
 
+    def ewise(self, other, mode, op):
+        """This CSR combined with ``other`` entry by entry as a new CSR result on the device (``osp_csr_ewise``); nothing is
+        sorted.  ``mode`` ``"union"``: the pattern is the union, a coordinate in both gets ``op(self, other)``, one in a
+        single operand keeps that operand's value bits.  ``mode`` ``"intersect"``: the common pattern, every value
+        ``op(self, other)``.  ``op`` is ``"plus" "times" "min" "max" "first" "second"``, and for an intersection also
+        ``"minus" "div"``: one IEEE operation in the results' dtype.  ``other`` is a ``CsrResult`` of the same context, shape
+        and dtype (``self`` itself is allowed).  Returns (result, stats dict): nnz_a, nnz_b, nnz_both, nnz_out, ms_total,
+        launches."""
+        if mode not in _lib.EWISE_MODES:
+            raise ValueError(f"mode must be one of {' '.join(_lib.EWISE_MODES)} (got {mode!r})")
+        if op not in _lib.EWISE_OPS:
+            raise ValueError(f"op must be one of {' '.join(_lib.EWISE_OPS)} (got {op!r})")
+        if not isinstance(other, CsrResult):
+            raise TypeError("other must be a CsrResult")
+        if other.shape != self.shape:
+            raise OspError(_lib.ERR_ARG, f"the operands' shapes differ: {self.shape} and {other.shape}")
+        if other.dtype != self.dtype:
+            raise OspError(_lib.ERR_ARG, f"the operands' dtypes differ: {np.dtype(self.dtype)} and {np.dtype(other.dtype)}")
+        ew = _lib.Ewise()
+        ew.mode, ew.op = _lib.EWISE_MODES[mode], _lib.EWISE_OPS[op]
+        stats = _lib.EwiseStats()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_csr_ewise(self._h, other._h, C.byref(ew), C.byref(h), C.byref(stats)))
+        return CsrResult(self._ctx, h), stats.as_dict()
+
+    def union(self, other, op="plus"):
+        """``ewise(other, "union", op)``: the accumulation ``self (+) other``."""
+        return self.ewise(other, "union", op)
+
+    def intersect(self, other, op="times"):
+        """``ewise(other, "intersect", op)``: ``op`` on the common pattern."""
+        return self.ewise(other, "intersect", op)
+
     def coo_rows_into(self, rows_device_ptr):
         """Row index of every entry into caller-owned DEVICE memory (nnz u32 values): with ``device_ptrs()[1:]`` the COO
         form ``Context.spgemm_coo_device`` takes (``osp_result_coo_rows``)."""

@@ -8,10 +8,13 @@
 --host-mask      the same search the way a user had to write it before the filter existed: every level's product and the
                  visited set copied to the host, filtered with scipy, and uploaded again; per level the host clock around
                  that round trip is printed beside the filter's device time of the default form.
+--ewise-union    the union of every level by osp_csr_ewise (union, first): the default, named so that a run says which it took.
+--sort-union     the union of every level by the sorting merge (merge_csr_parts_device) instead, as it was before osp_csr_ewise:
+                 the ms_union column is what the two differ in.
 --centrality     graph.betweenness_centrality from --sources vertices, --batch at a time: wall time.
 --standalone     no graph: apply_mask on the self-product of the R-MAT matrix (--preset uniform) with the product's own
                  pattern thinned to every second entry as the mask, both senses (with --host-mask: the host round trip too).
-Prints one JSON line per level (or per case) and a summary line."""
+--runs N repeats the traversal N times (one summary line each).  Prints one JSON line per level (or per case) and a summary line."""
 import argparse
 import json
 import os
@@ -64,14 +67,16 @@ def run_bfs(ctx, dev, args, n, rows, cols, src, copy_gbps, head):
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     flt = host_mask_filter(ctx, clock) if args.host_mask else graph._device_mask_filter
-    level, sigma, info, _ = graph._bfs_forward(ctx, dev, adj, src, mask_filter=flt)
+    union = graph._sort_union if args.sort_union else graph._device_union
+    level, sigma, info, _ = graph._bfs_forward(ctx, dev, adj, src, mask_filter=flt, union=union)
     torch.cuda.synchronize(dev)
     wall = time.perf_counter() - t0
     S_ = len(src)
     for d in range(len(info["nnz_product"])):
         nin, nm, nout, ms = info["nnz_product"][d], info["nnz_visited"][d], info["nnz_new"][d], info["ms_mask"][d]
         line = {"what": "host-mask" if args.host_mask else "device", "level": d + 1, "frontier_nnz": info["frontier_nnz"][d], "nnz_product": nin,
-                "nnz_visited": nm, "nnz_new": nout, "ms_product": info["ms_product"][d], "ms_union": info["ms_union"][d]}
+                "nnz_visited": nm, "nnz_new": nout, "ms_product": info["ms_product"][d], "ms_union": info["ms_union"][d],
+                "union": "sort" if args.sort_union else "ewise"}
         if args.host_mask:
             line.update(clock[d])
         else:
@@ -79,7 +84,7 @@ def run_bfs(ctx, dev, args, n, rows, cols, src, copy_gbps, head):
             line.update({"ms_mask": ms, "mask_GBps": gbps, "mask_over_copy": gbps / copy_gbps})
         print(json.dumps(line), flush=True)
     print(json.dumps({**head, "what": ("host-mask" if args.host_mask else "device") + " summary", "sources": S_, "levels": info["levels"],
-                      "reached": int((level >= 0).sum().item()), "wall_s": wall, "copy_probe_GBps": copy_gbps,
+                      "reached": int((level >= 0).sum().item()), "wall_s": wall, "union": "sort" if args.sort_union else "ewise", "copy_probe_GBps": copy_gbps,
                       "ms_product_sum": sum(info["ms_product"]), "ms_mask_sum": sum(info["ms_mask"]), "ms_union_sum": sum(info["ms_union"])}),
           flush=True)
 
@@ -134,6 +139,9 @@ def main():
     ap.add_argument("--sources", type=int, default=64)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--host-mask", action="store_true")
+    ap.add_argument("--sort-union", action="store_true")
+    ap.add_argument("--ewise-union", action="store_true")
+    ap.add_argument("--runs", type=int, default=1)
     ap.add_argument("--centrality", action="store_true")
     ap.add_argument("--standalone", action="store_true")
     ap.add_argument("--reps", type=int, default=5)
@@ -159,7 +167,8 @@ def main():
         print(json.dumps({**head, "what": "centrality summary", "sources": len(src), "batch": args.batch, "wall_s": wall,
                           "nonzero": int((bc != 0).sum()), "largest": float(bc.max()), "copy_probe_GBps": copy_gbps}), flush=True)
     else:
-        run_bfs(ctx, dev, args, n, rows, cols, src, copy_gbps, head)
+        for _ in range(args.runs):
+            run_bfs(ctx, dev, args, n, rows, cols, src, copy_gbps, head)
     ctx.close()
 
 
