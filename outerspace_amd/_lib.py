@@ -134,6 +134,30 @@ class EwiseStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+AXES = {"rows": 0, "cols": 1}  # osp_axis_t
+REDUCE_OPS = {"plus": 0, "min": 1, "max": 2, "count": 3}  # osp_reduce_op_t
+VECTOR_NONE = -1  # OSP_VECTOR_NONE
+# the operators of osp_vector_apply_t: osp_ewise_op_t without "first"
+VECTOR_APPLY_OPS = {name: v for name, v in EWISE_OPS.items() if name != "first"}
+
+
+class VectorApply(C.Structure):
+    """osp_vector_apply_t"""
+    _fields_ = [("row_op", C.c_int32), ("col_op", C.c_int32), ("reserved", C.c_uint32 * 8)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+class VectorStats(C.Structure):
+    """osp_vector_stats_t"""
+    _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("long_segments", C.c_uint64), ("ms_total", C.c_float),
+                ("launches", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -189,6 +213,9 @@ SELECT_EXPORTS = ["osp_csr_select"]
 
 # every symbol include/outerspace_spgemm_ewise.h declares
 EWISE_EXPORTS = ["osp_csr_ewise"]
+
+# every symbol include/outerspace_spgemm_vector.h declares
+VECTOR_EXPORTS = ["osp_csr_reduce", "osp_csr_apply_vectors", "osp_csr_select_vertices"]
 
 _lib = None
 
@@ -271,6 +298,9 @@ def lib():
     L.osp_csr_apply_mask.argtypes = [vp, u64, u64, vp, vp, i32, i32, i32, C.POINTER(vp), C.POINTER(ApplyMaskStats)]
     L.osp_csr_select.argtypes = [vp, C.POINTER(Select), C.POINTER(vp), C.POINTER(SelectStats)]
     L.osp_csr_ewise.argtypes = [vp, vp, C.POINTER(Ewise), C.POINTER(vp), C.POINTER(EwiseStats)]
+    L.osp_csr_reduce.argtypes = [vp, i32, i32, vp, i32, C.POINTER(VectorStats)]
+    L.osp_csr_apply_vectors.argtypes = [vp, C.POINTER(VectorApply), vp, vp, i32, C.POINTER(vp), C.POINTER(VectorStats)]
+    L.osp_csr_select_vertices.argtypes = [vp, vp, vp, i32, C.POINTER(vp), C.POINTER(VectorStats)]
     _lib = L
     return L
 

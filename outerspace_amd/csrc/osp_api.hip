@@ -26,6 +26,7 @@
 #include "../../include/outerspace_spgemm_apply_mask.h"
 #include "../../include/outerspace_spgemm_select.h"
 #include "../../include/outerspace_spgemm_ewise.h"
+#include "../../include/outerspace_spgemm_vector.h"
 #include "osp_internal.h"
 #include "osp_kernels.h"
 #include "osp_split.h"
@@ -37,6 +38,7 @@
 #include "osp_apply_mask.h"
 #include "osp_select.h"
 #include "osp_ewise.h"
+#include "osp_vector.h"
 
 namespace osp {
 
@@ -1304,6 +1306,200 @@ static void ewise_impl(Context *ctx, const Result *a, const Result *b, Result *r
                 (unsigned long long)nnz_both, launches, st->ms_total);
 }
 
+// ---- a CSR result and dense vectors: reduce, apply, vertex select (osp_vector.h) ----
+// R over every segment of (ptr, vals) into out[0, nseg): the short segments by a wave each, the long ones block by block
+// into a pool buffer whose segments (one per long segment) are the next level's input.  nent: an upper bound of the level's
+// entries.  One read-back per level that can hold a long segment (the number of long segments).
+template <class T, int OP>
+static void reduce_segments(Scratch &sc, hipStream_t s, const int64_t *ptr, const T *vals, uint64_t nseg, uint64_t nent, T *out,
+                            uint64_t &long_segments, uint32_t &launches) {
+    const uint32_t *map = nullptr;
+    for (int level = 0;; level++) {
+        reduce_short_kernel<T, OP><<<grid_for(nseg, kReduceWaves), kReduceWaves * kWave, 0, s>>>(ptr, vals, nseg, map, out);
+        launches++;
+        if (nent <= kReduceBlock) return;   // (no segment can be long)
+        unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MCL_COUNTERS);
+        zero_async(s, {{counters, MCL_COUNTERS * sizeof(uint64_t)}});
+        uint32_t *long_segs = sc.get<uint32_t>(nent / ((uint64_t)kReduceBlock + 1) + 1);
+        mcl_classify_kernel<<<grid_for(nseg, 256), 256, 0, s>>>(ptr, nseg, kReduceBlock, long_segs, counters);
+        launches += 2;
+        const uint64_t n_long = d2h((const uint64_t *)counters + MCL_NLONG, s);
+        if (level == 0) long_segments = n_long;
+        if (!n_long) return;
+        // the long segments' blocks: sum ceil(m / block) <= nent / block + n_long, the exact number stays on the device
+        const uint64_t max_blocks = nent / kReduceBlock + n_long;
+        uint32_t *nblk = sc.get<uint32_t>(n_long + 1), *next_map = sc.get<uint32_t>(n_long);
+        int64_t *blkptr = sc.get<int64_t>(n_long + 1);
+        uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(n_long + 1));
+        T *partial = sc.get<T>(max_blocks);
+        reduce_long_setup_kernel<<<grid_for(n_long, 256), 256, 0, s>>>(ptr, long_segs, n_long, map, nblk, next_map);
+        launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{nblk}, n_long, (uint64_t *)blkptr, tmp, s);
+        reduce_blocks_kernel<T, OP><<<grid_for(max_blocks, kReduceWaves), kReduceWaves * kWave, 0, s>>>(ptr, vals, long_segs, blkptr, n_long, partial);
+        launches++;
+        ptr = blkptr;
+        vals = partial;
+        nseg = n_long;
+        nent = max_blocks;
+        map = next_map;
+    }
+}
+
+template <class T>
+static void reduce_impl(Context *ctx, const Result *in, int axis, int op, void *out_vec, osp_memspace_t space, osp_vector_stats_t *st) {
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint64_t M = in->info.M, N = in->info.N, nnz = in->info.nnz_c;
+    const uint64_t nout = axis == OSP_AXIS_ROWS ? M : N;
+    uint64_t long_segments = 0;
+    uint32_t launches = 0;
+    // (the vector is formed in a pool buffer and copied out last: a call that fails leaves out_vec as it was)
+    T *out = sc.get<T>(nout);
+    const T inf = std::numeric_limits<T>::infinity();
+    const T id = op == OSP_REDUCE_MIN ? inf : op == OSP_REDUCE_MAX ? -inf : T(0);
+    std::vector<T> ids;
+    if (nout && nnz) {
+        const int64_t *ptr = in->rowptr;
+        const T *vals = (const T *)in->vals;
+        if (axis == OSP_AXIS_COLS) {
+            // the column-major view: entries of one column keep ascending row order (its kernels are not counted below)
+            int64_t *vptr;
+            uint32_t *vidx;
+            T *vvals;
+            masked_view<T>(ctx, sc, M, N, nnz, in->rowptr, in->colidx, vals, &vptr, &vidx, &vvals);
+            ptr = vptr;
+            vals = vvals;
+        }
+        if (op == OSP_REDUCE_COUNT) {
+            unsigned long long *counter = (unsigned long long *)sc.get<uint64_t>(1);
+            zero_async(s, {{counter, sizeof(uint64_t)}});
+            reduce_count_kernel<T><<<grid_for(nout, 256), 256, 0, s>>>(ptr, nout, out, counter);
+            launches = 2;
+            long_segments = d2h((const uint64_t *)counter, s);
+        } else if (op == OSP_REDUCE_PLUS) {
+            reduce_segments<T, RED_PLUS>(sc, s, ptr, vals, nout, nnz, out, long_segments, launches);
+        } else if (op == OSP_REDUCE_MIN) {
+            reduce_segments<T, RED_MIN>(sc, s, ptr, vals, nout, nnz, out, long_segments, launches);
+        } else {
+            reduce_segments<T, RED_MAX>(sc, s, ptr, vals, nout, nnz, out, long_segments, launches);
+        }
+    } else if (nout) {
+        ids.assign(nout, id);   // every segment is empty: no kernel
+    }
+    OSP_HIP(hipEventRecord(ev.b, s));
+    OSP_HIP(hipStreamSynchronize(s));
+    OSP_HIP(hipGetLastError());
+    if (nout) {
+        if (!ids.empty()) {
+            if (space == OSP_DEVICE) copy_h2d(out_vec, ids.data(), nout * sizeof(T), s);
+            else memcpy(out_vec, ids.data(), nout * sizeof(T));
+        } else if (space == OSP_DEVICE) {
+            OSP_HIP(hipMemcpyAsync(out_vec, out, nout * sizeof(T), hipMemcpyDeviceToDevice, s));
+        } else {
+            copy_d2h(out_vec, out, nout * sizeof(T), s);
+        }
+        OSP_HIP(hipStreamSynchronize(s));
+    }
+    *st = osp_vector_stats_t{};
+    st->nnz_in = nnz;
+    st->nnz_out = nout;
+    st->long_segments = long_segments;
+    st->ms_total = ev.ms();
+    st->launches = launches;
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] reduce axis=%d op=%d M=%llu N=%llu nnz=%llu long=%llu launches=%u %.3f ms\n", axis, op, (unsigned long long)M,
+                (unsigned long long)N, (unsigned long long)nnz, (unsigned long long)long_segments, launches, st->ms_total);
+}
+
+template <class T, int OP = 0>
+static void launch_apply_rows(int op, hipStream_t s, const Result *in, const ValueBits<T> *src, const ValueBits<T> *x, Result *res) {
+    if constexpr (OP < EW_OPS) {
+        if (OP != EW_FIRST && op == OP)
+            apply_rows_kernel<T, OP == EW_FIRST ? EW_SECOND : OP><<<grid_for(in->info.nnz_c, (unsigned)kCompactChunk), kCompactThreads, 0, s>>>(
+                in->rowptr, in->colidx, in->info.M, in->info.nnz_c, src, x, (ValueBits<T> *)res->vals);
+        else launch_apply_rows<T, OP + 1>(op, s, in, src, x, res);
+    }
+}
+template <class T, int OP = 0>
+static void launch_apply_cols(int op, hipStream_t s, const Result *in, const ValueBits<T> *src, const ValueBits<T> *y, Result *res) {
+    if constexpr (OP < EW_OPS) {
+        if (OP != EW_FIRST && op == OP)
+            apply_cols_kernel<T, OP == EW_FIRST ? EW_SECOND : OP><<<grid_for(in->info.nnz_c, 256), 256, 0, s>>>(in->colidx, in->info.nnz_c, src, y,
+                                                                                                             (ValueBits<T> *)res->vals);
+        else launch_apply_cols<T, OP + 1>(op, s, in, src, y, res);
+    }
+}
+
+template <class T>
+static void apply_vectors_impl(Context *ctx, const Result *in, Result *res, const osp_vector_apply_t &ap, const void *x_in, const void *y_in,
+                               osp_memspace_t space, osp_vector_stats_t *st) {
+    typedef ValueBits<T> V;
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint64_t M = in->info.M, N = in->info.N, nnz = in->info.nnz_c;
+    res->info = in->info;
+    uint32_t launches = 0;
+    if (M == 0 || nnz == 0) {
+        empty_result<T>(res, M, s);
+    } else {
+        const bool rows = ap.row_op != OSP_VECTOR_NONE, cols = ap.col_op != OSP_VECTOR_NONE;
+        const V *x = rows ? to_device(sc, (const V *)x_in, M, space, s) : nullptr;
+        const V *y = cols ? to_device(sc, (const V *)y_in, N, space, s) : nullptr;
+        alloc_rowptr(res, M);
+        OSP_HIP(hipMemcpyAsync(res->rowptr, in->rowptr, (M + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        alloc_entries<T>(res, nnz);
+        OSP_HIP(hipMemcpyAsync(res->colidx, in->colidx, nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        // one launch per side, the second in place on out's values
+        const V *src = (const V *)in->vals;
+        if (rows) {
+            launch_apply_rows<T>(ap.row_op, s, in, src, x, res);
+            src = (const V *)res->vals;
+            launches++;
+        }
+        if (cols) {
+            launch_apply_cols<T>(ap.col_op, s, in, src, y, res);
+            launches++;
+        }
+    }
+    finish_csr(res, ev, nnz, s);
+    *st = osp_vector_stats_t{};
+    st->nnz_in = st->nnz_out = nnz;
+    st->ms_total = res->info.ms_total;
+    st->launches = launches;
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] apply_vectors row_op=%d col_op=%d M=%llu nnz=%llu launches=%u %.3f ms\n", ap.row_op, ap.col_op, (unsigned long long)M,
+                (unsigned long long)nnz, launches, st->ms_total);
+}
+
+template <class T>
+static void select_vertices_impl(Context *ctx, const Result *in, Result *res, const uint8_t *keep_rows_in, const uint8_t *keep_cols_in,
+                                 osp_memspace_t space, osp_vector_stats_t *st) {
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint64_t M = in->info.M, N = in->info.N, nnz_in = in->info.nnz_c;
+    res->info = in->info;
+    const uint8_t *kr = keep_rows_in && nnz_in ? to_device(sc, keep_rows_in, M, space, s) : nullptr;
+    const uint8_t *kc = keep_cols_in && nnz_in ? to_device(sc, keep_cols_in, N, space, s) : nullptr;
+    const Compacted c = compact_by_bits<T>(sc, in, res, s, [&](unsigned nchunks, uint64_t *bits) {
+        const auto flag = kr && kc ? vertex_flag_kernel<true, true> : kr ? vertex_flag_kernel<true, false> : vertex_flag_kernel<false, true>;
+        flag<<<nchunks, kCompactThreads, 0, s>>>(in->rowptr, in->colidx, M, nnz_in, kr, kc, bits);
+    });
+    finish_csr(res, ev, c.nnz, s);
+    *st = osp_vector_stats_t{};
+    st->nnz_in = nnz_in;
+    st->nnz_out = c.nnz;
+    st->ms_total = res->info.ms_total;
+    st->launches = c.launches;
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] select_vertices rows=%d cols=%d M=%llu nnz %llu -> %llu launches=%u %.3f ms\n", kr != nullptr, kc != nullptr,
+                (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)c.nnz, c.launches, st->ms_total);
+}
+
 static void destroy_result(Result *r) {
     if (!r) return;
     if (r->ctx) {
@@ -1600,6 +1796,65 @@ int osp_csr_ewise(osp_result_t a_, osp_result_t b_, const osp_ewise_t *ew, osp_r
         osp_ewise_stats_t st{};
         const int rc = new_result(a->ctx, a->dtype, out, [&](auto tag, Result *res) {
             ewise_impl<decltype(tag)>(a->ctx, a, b, res, *ew, &st);
+        });
+        if (stats) *stats = st;
+        return rc;
+    });
+}
+
+int osp_csr_reduce(osp_result_t in_, int axis, int op, void *out_vec, osp_memspace_t space, osp_vector_stats_t *stats) {
+    Result *in = (Result *)in_;
+    if (!in || !out_vec) return fail(OSP_ERR_ARG, "null argument");
+    if (in->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
+    return guard([&] {
+        check_space(space);
+        if (axis != OSP_AXIS_ROWS && axis != OSP_AXIS_COLS) throw Error(OSP_ERR_ARG, "reduce: axis is not one of osp_axis_t");
+        if (op < OSP_REDUCE_PLUS || op > OSP_REDUCE_COUNT) throw Error(OSP_ERR_ARG, "reduce: op is not one of osp_reduce_op_t");
+        if (axis == OSP_AXIS_COLS && in->info.nnz_c >= 0xffffffffull)
+            throw Error(OSP_ERR_ARG, "reduce: the column axis does not support results with >= 2^32 - 1 non-zeros");
+        osp_vector_stats_t st{};
+        on_device(in->ctx, [&] { with_type(in->dtype, [&](auto tag) { reduce_impl<decltype(tag)>(in->ctx, in, axis, op, out_vec, space, &st); }); });
+        if (stats) *stats = st;
+        return (int)OSP_OK;
+    });
+}
+
+int osp_csr_apply_vectors(osp_result_t in_, const osp_vector_apply_t *ap, const void *x_rows, const void *y_cols, osp_memspace_t space,
+                          osp_result_t *out, osp_vector_stats_t *stats) {
+    Result *in = (Result *)in_;
+    if (!in || !ap || !out) return fail(OSP_ERR_ARG, "null argument");
+    if (in->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
+    return guard([&] {
+        check_space(space);
+        for (int32_t o : {ap->row_op, ap->col_op})
+            if (o != OSP_VECTOR_NONE && (o < OSP_EWISE_PLUS || o > OSP_EWISE_DIV || o == OSP_EWISE_FIRST))
+                throw Error(OSP_ERR_ARG, "apply_vectors: an op is PLUS, TIMES, MINUS, DIV, MIN, MAX, SECOND or OSP_VECTOR_NONE");
+        if (ap->row_op == OSP_VECTOR_NONE && ap->col_op == OSP_VECTOR_NONE) throw Error(OSP_ERR_ARG, "apply_vectors: both sides are OSP_VECTOR_NONE");
+        for (uint32_t w : ap->reserved)
+            if (w) throw Error(OSP_ERR_ARG, "apply_vectors: reserved words must be 0");
+        if ((ap->row_op != OSP_VECTOR_NONE && !x_rows) || (ap->col_op != OSP_VECTOR_NONE && !y_cols))
+            throw Error(OSP_ERR_ARG, "apply_vectors: a side with an op needs its vector");
+        osp_vector_stats_t st{};
+        const int rc = new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {
+            apply_vectors_impl<decltype(tag)>(in->ctx, in, res, *ap, x_rows, y_cols, space, &st);
+        });
+        if (stats) *stats = st;
+        return rc;
+    });
+}
+
+int osp_csr_select_vertices(osp_result_t in_, const uint8_t *keep_rows, const uint8_t *keep_cols, osp_memspace_t space, osp_result_t *out,
+                            osp_vector_stats_t *stats) {
+    Result *in = (Result *)in_;
+    if (!in || !out) return fail(OSP_ERR_ARG, "null argument");
+    if (in->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
+    return guard([&] {
+        check_space(space);
+        if (!keep_rows && !keep_cols) throw Error(OSP_ERR_ARG, "select_vertices: keep_rows and keep_cols are both null");
+        if (in->info.nnz_c >= 0xffffffffull) throw Error(OSP_ERR_ARG, "select_vertices: results with >= 2^32 - 1 non-zeros are not supported");
+        osp_vector_stats_t st{};
+        const int rc = new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {
+            select_vertices_impl<decltype(tag)>(in->ctx, in, res, keep_rows, keep_cols, space, &st);
         });
         if (stats) *stats = st;
         return rc;

@@ -123,11 +123,7 @@ template <class T>
 __device__ __forceinline__ T mcl_finish_row(T *__restrict__ vals, uint64_t m) {
 #pragma clang fp contract(off)
     const unsigned lane = lane_id();
-    T p = T(0);
-    for (uint64_t i = lane; i < m; i += kWave) p = p + vals[i];
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) p = p + __shfl_down(p, d, kWave);   // p_l += p_{l+d} for l < d (lanes >= d: unused)
-    const T s = __shfl(p, 0, kWave);
+    const T s = __shfl(wave_ordered_reduce<RED_PLUS>(vals, m), 0, kWave);   // (the order osp_csr_reduce shares)
     T q = T(0), mx = T(0);
     for (uint64_t i = lane; i < m; i += kWave) {
         const T o = vals[i] / s;

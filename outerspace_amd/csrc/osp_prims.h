@@ -74,6 +74,30 @@ __device__ __forceinline__ uint64_t wave_reduce_sum_u62(uint64_t v) {
     return sa + (sb << 24) + (sc << 48);
 }
 
+// ---- the reduction whose order is part of an interface (osp_csr_inflate_prune's row sums, osp_csr_reduce) -----------------
+// (the values of osp_reduce_op_t that combine values)
+enum { RED_PLUS = 0, RED_MIN = 1, RED_MAX = 2 };
+template <int OP, class T>
+__device__ __forceinline__ T ordered_identity() {
+    return OP == RED_PLUS ? T(0) : OP == RED_MIN ? (T)__builtin_inf() : -(T)__builtin_inf();
+}
+// a (+) b: ONE IEEE addition, or a copy of one operand (a comparison with a NaN is false: a is kept)
+template <int OP, class T>
+__device__ __forceinline__ T ordered_combine(T a, T b) {
+#pragma clang fp contract(off)
+    return OP == RED_PLUS ? a + b : OP == RED_MIN ? (b < a ? b : a) : (b > a ? b : a);
+}
+// R(vals[0, m)) by ONE wave: lane l combines the entries l, l + 64, ... left to right into the identity, then
+// p_l = p_l (+) p_{l + d} for l < d, d = 32 .. 1.  Lane 0 holds the result (the other lanes' values are unused).
+template <int OP, class T>
+__device__ __forceinline__ T wave_ordered_reduce(const T *__restrict__ vals, uint64_t m) {
+    T p = ordered_identity<OP, T>();
+    for (uint64_t i = lane_id(); i < m; i += kWave) p = ordered_combine<OP>(p, vals[i]);
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) p = ordered_combine<OP>(p, __shfl_down(p, d, kWave));
+    return p;
+}
+
 // Exclusive scan across a block of NT threads (NT multiple of 64, <= 1024).  `scratch` holds
 // NT/64 entries of T.  Returns the exclusive prefix of `v`; *total gets the block sum.
 // TAILSYNC = false leaves out the barrier that protects `scratch` against the caller's NEXT scan: for callers that pass

@@ -3,7 +3,9 @@ clustering on the plain one with ``osp_csr_inflate_prune`` between two expansion
 that use both with the mask filter ``osp_csr_apply_mask`` between two levels (``bfs_levels``, ``betweenness_centrality``),
 and edge support and k-truss on the masked product with the entry filter ``osp_csr_select`` between two rounds
 (``edge_support``, ``k_truss``, ``truss_decomposition``, at the end), and personalised PageRank, which sums a series of
-products with the element-wise union ``osp_csr_ewise`` (``personalized_pagerank``).
+products with the element-wise union ``osp_csr_ewise`` (``personalized_pagerank``), and k-core, Jaccard similarity and the
+clustering coefficient on ``osp_csr_reduce`` / ``osp_csr_apply_vectors`` / ``osp_csr_select_vertices`` (``core_numbers``,
+``k_core``, ``jaccard_similarity``, ``local_clustering``).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -688,3 +690,174 @@ def truss_decomposition(rows, cols, n=None, *, dtype=np.float64, ctx=None):
             S.close()
     info["products"] = info["rounds"]
     return u, v, trussness, info
+
+
+# ---- k-core, Jaccard similarity, clustering coefficient --------------------------------------------------
+def _torch_dtype(dtype):
+    return torch.float32 if dtype == np.float32 else torch.float64
+
+
+def _degrees(A, deg, device):
+    """deg <- the entries per row of the CSR result A (``reduce("rows", "count")``), written on the device into the torch
+    vector ``deg`` of A's dtype.  Returns the call's device time."""
+    torch.cuda.synchronize(device)   # the library works on its own stream
+    _, st = A.reduce("rows", "count", out=deg)
+    return st["ms_total"]
+
+
+def _core_info():
+    return {"rounds": 0, "nnz_graph": [], "ms_reduce": [], "ms_select": []}
+
+
+def _peel_level(A, k, deg, device, info):
+    """Rounds of level k on the graph A (a symmetric CSR result): the degrees, and -- unless every vertex that still has an
+    edge has at least k of them -- the subgraph induced by the vertices of degree >= k, until nothing is removed.  A is
+    closed here when it is replaced.  Returns A', the k-core; ``deg`` holds its degrees."""
+    while True:
+        ms = _degrees(A, deg, device)
+        info["rounds"] += 1
+        info["nnz_graph"].append(A.nnz)
+        info["ms_reduce"].append(ms)
+        keep = deg >= k
+        if not bool(((deg > 0) & ~keep).any().item()):
+            info["ms_select"].append(0.0)
+            return A
+        keep8 = keep.to(torch.uint8)
+        torch.cuda.synchronize(device)
+        try:
+            new, st = A.select_vertices(keep8, keep8)
+        except Exception:
+            A.close()
+            raise
+        info["ms_select"].append(st["ms_total"])
+        A.close()
+        A = new
+
+
+def core_numbers(rows, cols, n=None, *, dtype=np.float64, ctx=None):
+    """The core number of every vertex of the undirected graph with edges (rows[e], cols[e]) on vertices [0, n) (any
+    direction, duplicates and self loops allowed): the largest k whose k-core -- the largest subgraph in which every vertex
+    has at least k neighbours -- contains the vertex (``networkx.core_number``).  Peeling, every matrix step on the GPU:
+    for k = 1, 2, ... a ROUND is  deg = A.reduce("rows", "count")  and, when a vertex with 0 < deg < k exists,
+    A = A.select_vertices(deg >= k, deg >= k);  a level ends with the first round that removes nothing.  A vertex removed at
+    level k has core number k - 1, an isolated vertex 0.  torch touches the length-n vectors only.
+
+    Returns (core int64[n], info): info = rounds, k_max (the largest core number), and per round the lists nnz_graph
+    (directed entries: twice the edges), ms_reduce, ms_select (device times; 0 where the round removed nothing)."""
+    ctx, device, dtype, adj = _truss_setup(rows, cols, n, dtype, ctx)
+    info = dict(_core_info(), k_max=0)
+    core = torch.zeros(adj.n, dtype=torch.int64, device=device)
+    if adj.nnz == 0:
+        return core.cpu().numpy(), info
+    deg = torch.empty(adj.n, dtype=_torch_dtype(dtype), device=device)
+    A = _adjacency_result(ctx, adj, dtype, device)
+    try:
+        k = 1
+        while True:
+            A = _peel_level(A, k, deg, device, info)
+            if A.nnz == 0:
+                break
+            core[deg > 0] = k   # (every vertex that still has an edge is in the k-core)
+            info["k_max"] = k
+            k += 1
+    finally:
+        torch.cuda.synchronize(device)
+        A.close()
+    return core.cpu().numpy(), info
+
+
+def k_core(rows, cols, n=None, k=1, *, dtype=np.float64, ctx=None):
+    """The k-core of the undirected graph with edges (rows[e], cols[e]) on vertices [0, n): the largest subgraph in which
+    every vertex has at least k neighbours (``networkx.k_core``'s definition), by the rounds of ``core_numbers`` at the one
+    level k.  k >= 0; the 0-core and the 1-core hold every edge.
+
+    Returns (u, v, info): the core's edges once each, u < v, ascending by (u, v), int64; info = rounds and the per-round
+    lists of ``core_numbers``."""
+    k = int(k)
+    if k < 0:
+        raise ValueError("k must be at least 0")
+    ctx, device, dtype, adj = _truss_setup(rows, cols, n, dtype, ctx)
+    info = _core_info()
+    if adj.nnz == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), info
+    deg = torch.empty(adj.n, dtype=_torch_dtype(dtype), device=device)
+    A = _adjacency_result(ctx, adj, dtype, device)
+    try:
+        A = _peel_level(A, k, deg, device, info)
+        u, v, _ = _upper_entries(A)
+    finally:
+        torch.cuda.synchronize(device)
+        A.close()
+    return u, v, info
+
+
+def jaccard_similarity(rows, cols, n=None, *, dtype=np.float64, ctx=None):
+    """The Jaccard similarity |N(u) & N(v)| / |N(u) | N(v)| of the ends of every edge of the undirected graph with edges
+    (rows[e], cols[e]) on vertices [0, n), every matrix step on the GPU:  S = (A @ A)<A>  (the common neighbours, the
+    masked product as it stands),  D = S.apply_vectors(deg, "second", deg, "plus")  (deg u + deg v on S's pattern),
+    U = D.ewise(S, "intersect", "minus")  (the union's size),  J = S.ewise(U, "intersect", "div").  Every value is ONE
+    correctly rounded division of two exact integers, so float64 equals ``networkx.jaccard_coefficient`` as floats.
+
+    Returns (u, v, jaccard): every edge once, u < v, ascending by (u, v); jaccard float64, 0 for an edge without a common
+    neighbour.  float32 is allowed while deg u + deg v is exact (maximum degree below 2^23, else ValueError); its values are
+    the float32 quotients widened."""
+    ctx, device, dtype, adj = _truss_setup(rows, cols, n, dtype, ctx)
+    if adj.nnz == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float64)
+    if dtype == np.float32 and int((adj.rowptr[1:] - adj.rowptr[:-1]).max().item()) >= 1 << 23:
+        raise ValueError("float32 holds deg u + deg v exactly only while the maximum degree is below 2^23: use float64")
+    deg = torch.empty(adj.n, dtype=_torch_dtype(dtype), device=device)
+    A = _adjacency_result(ctx, adj, dtype, device)
+    held = [A]
+    try:
+        _degrees(A, deg, device)
+        u, v, _ = _upper_entries(A)
+        S = _support_product(ctx, A)
+        held.append(S)
+        D, _ = S.apply_vectors(deg, "second", deg, "plus")
+        held.append(D)
+        U, _ = D.ewise(S, "intersect", "minus")
+        held.append(U)
+        J, _ = S.ewise(U, "intersect", "div")
+        held.append(J)
+        ju, jv, jval = _upper_entries(J)
+    finally:
+        torch.cuda.synchronize(device)
+        for res in held:
+            res.close()
+    jaccard = np.zeros(len(u), np.float64)
+    jaccard[np.searchsorted(u * adj.n + v, ju * adj.n + jv)] = jval.astype(np.float64)   # (the product has no entry where it is 0)
+    return u, v, jaccard
+
+
+def local_clustering(rows, cols, n=None, *, dtype=np.float64, ctx=None):
+    """The local clustering coefficient of every vertex of the undirected graph with edges (rows[e], cols[e]) on vertices
+    [0, n): with S = (A @ A)<A>,  t = S.reduce("rows", "plus")  is twice the number of triangles through the vertex, and
+    the coefficient is  t / (deg (deg - 1)),  0 where deg < 2 -- ONE correctly rounded float64 division of two exact
+    integers, so it equals ``networkx.clustering`` as floats.  The division runs on the host on the length-n vectors.
+
+    Returns float64[n].  float32 is allowed while t is exact (maximum degree below 2^12, else ValueError)."""
+    ctx, device, dtype, adj = _truss_setup(rows, cols, n, dtype, ctx)
+    if adj.nnz == 0:
+        return np.zeros(adj.n, np.float64)
+    if dtype == np.float32 and int((adj.rowptr[1:] - adj.rowptr[:-1]).max().item()) >= 1 << 12:
+        raise ValueError("float32 holds a vertex's triangle sum exactly only while the maximum degree is below 2^12: use float64")
+    deg = torch.empty(adj.n, dtype=_torch_dtype(dtype), device=device)
+    t = torch.empty(adj.n, dtype=_torch_dtype(dtype), device=device)
+    A = _adjacency_result(ctx, adj, dtype, device)
+    held = [A]
+    try:
+        _degrees(A, deg, device)
+        S = _support_product(ctx, A)
+        held.append(S)
+        S.reduce("rows", "plus", out=t)
+    finally:
+        torch.cuda.synchronize(device)
+        for res in held:
+            res.close()
+    # the one division, in float64 on the host: numpy's is the IEEE division whatever the device's
+    d64, t64 = deg.cpu().numpy().astype(np.float64), t.cpu().numpy().astype(np.float64)
+    cc = np.zeros(adj.n, np.float64)
+    some = d64 >= 2.0
+    cc[some] = t64[some] / (d64[some] * (d64[some] - 1.0))
+    return cc

@@ -201,6 +201,86 @@ class CsrResult:
         """``ewise(other, "intersect", op)``: ``op`` on the common pattern."""
         return self.ewise(other, "intersect", op)
 
+    def _vector_arg(self, v, n, dtype, space, what):
+        """A dense vector argument of the ``osp_csr_*`` functions that take one: (pointer, keep-alive).  ``space="host"``: an
+        array-like of n values, converted to ``dtype``; ``space="device"``: a device address, or an object with
+        ``data_ptr()`` (a torch tensor of n values of ``dtype``: the caller has synchronised its stream)."""
+        if space not in ("device", "host"):
+            raise ValueError('space must be "device" or "host"')
+        if v is None:
+            return None, None
+        if space == "host" or n == 0:   # (n == 0: nothing is read, and the pointer is never null)
+            a = np.ascontiguousarray(v, dtype) if space == "host" else np.zeros(0, dtype)
+            if a.shape != (n,):
+                raise OspError(_lib.ERR_ARG, f"{what} must have {n} entries (got shape {a.shape})")
+            a = a if n else np.zeros(1, dtype)
+            return C.c_void_p(a.ctypes.data), a
+        if hasattr(v, "data_ptr"):
+            if v.numel() != n or v.element_size() != np.dtype(dtype).itemsize or not v.is_contiguous():
+                raise OspError(_lib.ERR_ARG, f"{what} must be a contiguous tensor of {n} values of {np.dtype(dtype)}")
+            return C.c_void_p(v.data_ptr()), v
+        return C.c_void_p(int(v)), None
+
+    def reduce(self, axis, op, out=None):
+        """One value per row (``axis="rows"``, M values) or per column (``"cols"``, N values) of this CSR
+        (``osp_csr_reduce``): ``op`` ``"plus"``, ``"min"``, ``"max"`` or ``"count"``, in this result's dtype, in an order that
+        is defined to the bit and depends on the segment's length alone.  An empty row gives +0.0,
+        +inf, -inf, 0.  ``out=None``: returns (numpy array on the host, stats dict); ``out`` a device address (or a torch
+        tensor of that many values of this dtype): fills it and returns (out, stats dict).  Stats: nnz_in, nnz_out,
+        long_segments, ms_total, launches."""
+        if axis not in _lib.AXES:
+            raise ValueError(f"axis must be one of {' '.join(_lib.AXES)} (got {axis!r})")
+        if op not in _lib.REDUCE_OPS:
+            raise ValueError(f"op must be one of {' '.join(_lib.REDUCE_OPS)} (got {op!r})")
+        n = self.shape[_lib.AXES[axis]]
+        stats = _lib.VectorStats()
+        if out is None:
+            buf = np.empty(max(n, 1), self.dtype)   # (never a null pointer)
+            ptr, space, ret = C.c_void_p(buf.ctypes.data), _lib.OSP_HOST, buf[:n]
+        else:
+            ptr, _ = self._vector_arg(out, n, self.dtype, "device", "out")
+            space, ret = _lib.OSP_DEVICE, out
+        _lib.check(_lib.lib().osp_csr_reduce(self._h, _lib.AXES[axis], _lib.REDUCE_OPS[op], ptr, space, C.byref(stats)))
+        return ret, stats.as_dict()
+
+    def apply_vectors(self, rows=None, row_op=None, cols=None, col_op=None, space="device"):
+        """This CSR's pattern with every value ``col_op(row_op(c, rows[i]), cols[j])`` as a new CSR result on the device
+        (``osp_csr_apply_vectors``).  Each op is ``"plus" "times" "minus" "div" "min" "max" "second"`` -- one IEEE operation
+        with the entry in a's place and the vector's element in b's, as ``ewise`` defines them -- or None to skip that side
+        (at least one side is needed).  ``rows``: M values, ``cols``: N values of this dtype, device addresses / torch
+        tensors (``space="device"``) or array-likes (``space="host"``).  Returns (result, stats dict): nnz_in, nnz_out,
+        long_segments, ms_total, launches."""
+        ap = _lib.VectorApply()
+        for side, op in (("row_op", row_op), ("col_op", col_op)):
+            if op is not None and op not in _lib.VECTOR_APPLY_OPS:
+                raise ValueError(f"{side} must be None or one of {' '.join(_lib.VECTOR_APPLY_OPS)} (got {op!r})")
+            setattr(ap, side, _lib.VECTOR_NONE if op is None else _lib.VECTOR_APPLY_OPS[op])
+        M, N = self.shape
+        x, keep_x = self._vector_arg(rows if row_op is not None else None, M, self.dtype, space, "rows")
+        y, keep_y = self._vector_arg(cols if col_op is not None else None, N, self.dtype, space, "cols")
+        stats = _lib.VectorStats()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_csr_apply_vectors(self._h, C.byref(ap), x, y, _lib.OSP_HOST if space == "host" else _lib.OSP_DEVICE,
+                                                    C.byref(h), C.byref(stats)))
+        del keep_x, keep_y
+        return CsrResult(self._ctx, h), stats.as_dict()
+
+    def select_vertices(self, keep_rows=None, keep_cols=None, space="device"):
+        """The entries (i, j) of this CSR with ``keep_rows[i] != 0`` and ``keep_cols[j] != 0`` as a new CSR result on the
+        device (``osp_csr_select_vertices``); a vector given as None keeps everything on its side (one of them is needed).
+        The shape stays: a removed vertex is an empty row or column.  ``keep_rows``: M bytes, ``keep_cols``: N bytes (uint8 /
+        bool), device addresses / torch tensors (``space="device"``) or array-likes (``space="host"``).  Returns (result,
+        stats dict): nnz_in, nnz_out, long_segments, ms_total, launches."""
+        M, N = self.shape
+        kr, keep_r = self._vector_arg(keep_rows, M, np.uint8, space, "keep_rows")
+        kc, keep_c = self._vector_arg(keep_cols, N, np.uint8, space, "keep_cols")
+        stats = _lib.VectorStats()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_csr_select_vertices(self._h, kr, kc, _lib.OSP_HOST if space == "host" else _lib.OSP_DEVICE, C.byref(h),
+                                                      C.byref(stats)))
+        del keep_r, keep_c
+        return CsrResult(self._ctx, h), stats.as_dict()
+
     def coo_rows_into(self, rows_device_ptr):
         """Row index of every entry into caller-owned DEVICE memory (nnz u32 values): with ``device_ptrs()[1:]`` the COO
         form ``Context.spgemm_coo_device`` takes (``osp_result_coo_rows``)."""
