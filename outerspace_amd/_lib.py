@@ -158,6 +158,26 @@ class VectorStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+# the operators osp_semiring_t takes (osp_ewise_op_t values)
+MXM_ADD_OPS = {name: EWISE_OPS[name] for name in ("plus", "min", "max", "first")}
+MXM_MUL_OPS = {name: EWISE_OPS[name] for name in ("times", "plus", "min", "max", "first", "second")}
+
+
+class Semiring(C.Structure):
+    """osp_semiring_t"""
+    _fields_ = [("add", C.c_int32), ("mul", C.c_int32), ("reserved", C.c_uint32 * 8)]
+
+
+class MxmStats(C.Structure):
+    """osp_mxm_stats_t"""
+    _fields_ = [("nnz_a", C.c_uint64), ("nnz_b", C.c_uint64), ("products", C.c_uint64), ("nnz_out", C.c_uint64),
+                ("short_rows", C.c_uint64), ("long_rows", C.c_uint64), ("batches", C.c_uint32), ("launches", C.c_uint32),
+                ("ms_total", C.c_float), ("reserved", C.c_uint32 * 7)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -216,6 +236,9 @@ EWISE_EXPORTS = ["osp_csr_ewise"]
 
 # every symbol include/outerspace_spgemm_vector.h declares
 VECTOR_EXPORTS = ["osp_csr_reduce", "osp_csr_apply_vectors", "osp_csr_select_vertices"]
+
+# every symbol include/outerspace_spgemm_mxm.h declares
+MXM_EXPORTS = ["osp_csr_mxm"]
 
 _lib = None
 
@@ -301,6 +324,7 @@ def lib():
     L.osp_csr_reduce.argtypes = [vp, i32, i32, vp, i32, C.POINTER(VectorStats)]
     L.osp_csr_apply_vectors.argtypes = [vp, C.POINTER(VectorApply), vp, vp, i32, C.POINTER(vp), C.POINTER(VectorStats)]
     L.osp_csr_select_vertices.argtypes = [vp, vp, vp, i32, C.POINTER(vp), C.POINTER(VectorStats)]
+    L.osp_csr_mxm.argtypes = [vp, vp, C.POINTER(Semiring), C.POINTER(vp), C.POINTER(MxmStats)]
     _lib = L
     return L
 

@@ -27,6 +27,7 @@
 #include "../../include/outerspace_spgemm_select.h"
 #include "../../include/outerspace_spgemm_ewise.h"
 #include "../../include/outerspace_spgemm_vector.h"
+#include "../../include/outerspace_spgemm_mxm.h"
 #include "osp_internal.h"
 #include "osp_kernels.h"
 #include "osp_split.h"
@@ -39,6 +40,7 @@
 #include "osp_select.h"
 #include "osp_ewise.h"
 #include "osp_vector.h"
+#include "osp_mxm.h"
 
 namespace osp {
 
@@ -1306,6 +1308,209 @@ static void ewise_impl(Context *ctx, const Result *a, const Result *b, Result *r
                 (unsigned long long)nnz_both, launches, st->ms_total);
 }
 
+// ---- the product of two CSR results under a semiring (osp_mxm.h) ----
+struct MxmOperands {
+    const int64_t *a_rowptr; const uint32_t *a_col; const void *a_val;
+    const int64_t *b_rowptr; const uint32_t *b_col; const void *b_val;
+    const uint64_t *wscan;
+};
+template <class T, int ADD>
+static void launch_mxm_short_add(const MxmOperands &op, hipStream_t s, uint64_t r0, uint64_t nrows, uint32_t cap, int mul, uint64_t p0, uint32_t *tcol,
+                                 ValueBits<T> *tval, uint32_t *cnt) {
+    typedef ValueBits<T> V;
+    mxm_short_kernel<T, ADD><<<(unsigned)nrows, kWave, 0, s>>>(op.a_rowptr, op.a_col, (const V *)op.a_val, op.b_rowptr, op.b_col, (const V *)op.b_val,
+                                                                op.wscan, r0, cap, mul, p0, tcol, tval, cnt);
+}
+template <class T>
+static void launch_mxm_short(int add, const MxmOperands &op, hipStream_t s, uint64_t r0, uint64_t nrows, uint32_t cap, int mul, uint64_t p0,
+                             uint32_t *tcol, ValueBits<T> *tval, uint32_t *cnt) {
+    if (add == EW_PLUS) launch_mxm_short_add<T, EW_PLUS>(op, s, r0, nrows, cap, mul, p0, tcol, tval, cnt);
+    else if (add == EW_MIN) launch_mxm_short_add<T, EW_MIN>(op, s, r0, nrows, cap, mul, p0, tcol, tval, cnt);
+    else if (add == EW_MAX) launch_mxm_short_add<T, EW_MAX>(op, s, r0, nrows, cap, mul, p0, tcol, tval, cnt);
+    else launch_mxm_short_add<T, EW_FIRST>(op, s, r0, nrows, cap, mul, p0, tcol, tval, cnt);
+}
+template <class T, int MUL = 0>
+static void launch_mxm_expand(int mul, const MxmOperands &op, hipStream_t s, const uint32_t *long_rows, const uint64_t *loff, uint32_t nlong,
+                              uint64_t nprod, int colbits, uint64_t *key, uint32_t *pos, ValueBits<T> *pval) {
+    typedef ValueBits<T> V;
+    if constexpr (MUL <= EW_SECOND) {
+        if (mul == MUL)
+            mxm_expand_kernel<T, MUL><<<grid_for(nprod, 256), 256, 0, s>>>(op.a_rowptr, op.a_col, (const V *)op.a_val, op.b_rowptr, op.b_col,
+                                                                          (const V *)op.b_val, op.wscan, long_rows, loff, nlong, nprod, colbits, key,
+                                                                          pos, pval);
+        else launch_mxm_expand<T, MUL + 1>(mul, op, s, long_rows, loff, nlong, nprod, colbits, key, pos, pval);
+    }
+}
+template <class T, int ADD>
+static void launch_mxm_fold_add(const MxmOperands &op, hipStream_t s, const uint64_t *key, const ValueBits<T> *sorted_val, const uint64_t *headscan,
+                                const uint64_t *head_pos, uint64_t nprod, const uint32_t *long_rows, const uint64_t *loff, int colbits, uint64_t p0,
+                                uint32_t *tcol, ValueBits<T> *tval) {
+    mxm_fold_kernel<T, ADD><<<grid_for(nprod, 256), 256, 0, s>>>(key, sorted_val, headscan, head_pos, nprod, op.a_rowptr, op.wscan, long_rows, loff,
+                                                                 colbits, p0, tcol, tval);
+}
+// kernels of one device_exclusive_scan over n entries
+static uint32_t scan_launches(uint64_t n) { return n == 0 || (n + kScanTile - 1) / kScanTile <= kScanSmallTiles ? 1u : 3u; }
+
+template <class T>
+static void mxm_impl(Context *ctx, const Result *a, const Result *b, Result *res, const osp_semiring_t &sr, osp_mxm_stats_t *st) {
+    typedef ValueBits<T> V;
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint64_t M = a->info.M, K = a->info.N, N = b->info.N, nnz_a = a->info.nnz_c, nnz_b = b->info.nnz_c;
+    res->info = osp_result_info_t{};   // every field the product does not name stays 0
+    res->info.dtype = res->dtype;
+    res->info.M = M; res->info.K = K; res->info.N = N;
+    res->info.row_begin = 0; res->info.row_end = M;
+    res->info.nnz_a = nnz_a; res->info.nnz_b = nnz_b;
+    uint64_t products = 0, nnz_out = 0, n_short = 0, n_long = 0;
+    uint32_t nb = 0, launches = 0;
+
+    // ---- symbolic: the products of every entry of a, scanned ----
+    uint64_t *wscan = nullptr;
+    if (M && nnz_a && nnz_b) {
+        uint32_t *w = sc.get<uint32_t>(nnz_a);
+        wscan = sc.get<uint64_t>(nnz_a + 1);
+        uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(nnz_a));
+        mxm_entry_len_kernel<<<grid_for(nnz_a, 256), 256, 0, s>>>(a->colidx, nnz_a, b->rowptr, w);
+        launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{w}, nnz_a, wscan, tmp, s);
+        products = d2h((const uint64_t *)wscan + nnz_a, s);
+    }
+    if (products == 0) {
+        empty_result<T>(res, M, s);
+    } else {
+        const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(env_u64("OSP_MXM_SHORT_CAP", kMxmShortMax), 1), kMxmShortMax);
+        const uint64_t budget = std::min<uint64_t>(std::max<uint64_t>(env_u64("OSP_MXM_BATCH", kMxmBatchDefault), 1), 0xfffffffeull);
+        const MxmOperands op{a->rowptr, a->colidx, a->vals, b->rowptr, b->colidx, b->vals, wscan};
+        // ---- the rows' classes and the batches ----
+        // (two consecutive batches hold more than `budget` products between them, or the cut would not lie there)
+        const uint32_t max_batches = (uint32_t)std::min<uint64_t>(M, 2 * (products / budget) + 3);
+        unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MXM_COUNTERS);
+        uint64_t *cuts = sc.get<uint64_t>(2 * ((uint64_t)max_batches + 1));
+        uint32_t *d_nb = sc.get<uint32_t>(1);
+        zero_async(s, {{counters, MXM_COUNTERS * sizeof(uint64_t)}});
+        mxm_classify_kernel<<<grid_for(M, 256), 256, 0, s>>>(a->rowptr, M, wscan, cap, counters);
+        mxm_cut_kernel<<<1, 1, 0, s>>>(a->rowptr, wscan, M, budget, max_batches, cuts, d_nb);
+        launches += 3;
+        uint64_t n_toobig = 0;
+        {
+            Gather g(s);
+            g.add(&n_short, (const uint64_t *)counters + MXM_NSHORT);
+            g.add(&n_long, (const uint64_t *)counters + MXM_NLONG);
+            g.add(&n_toobig, (const uint64_t *)counters + MXM_NTOOBIG);
+            g.add(&nb, (const uint32_t *)d_nb);
+            g.wait();
+        }
+        if (n_toobig) throw Error(OSP_ERR_CAPACITY, "mxm: an output row has >= 2^32 - 1 products (positions inside a batch are 32 bits)");
+        if (nb > max_batches) throw Error(OSP_ERR_CAPACITY, "mxm: the batch list overflowed its bound");
+        std::vector<uint64_t> cut((size_t)2 * (nb + 1));
+        copy_d2h(cut.data(), cuts, cut.size() * sizeof(uint64_t), s);
+
+        alloc_rowptr(res, M);
+        uint32_t *cnt = sc.get<uint32_t>(M + 1);
+        const int colbits = bits_for(N);
+        struct BatchOut { uint32_t *col; V *val; uint64_t nnz; };
+        std::vector<BatchOut> outs;
+        for (uint32_t t = 0; t < nb; t++) {
+            const uint64_t r0 = cut[2 * t], p0 = cut[2 * t + 1], nrows = cut[2 * t + 2] - r0, pb = cut[2 * t + 3] - p0;
+            Scratch sb(ctx);
+            // a row's slot is its place in the batch's expansion: it holds at most as many entries as the row has products
+            uint32_t *tcol = sb.get<uint32_t>(pb);
+            V *tval = sb.get<V>(pb);
+            launch_mxm_short<T>(sr.add, op, s, r0, nrows, cap, sr.mul, p0, tcol, tval, cnt);
+            launches++;
+            if (n_long) {
+                uint32_t *flag = sb.get<uint32_t>(nrows + 1), *lp = sb.get<uint32_t>(nrows + 1);
+                uint64_t *rank = sb.get<uint64_t>(nrows + 1), *lpscan = sb.get<uint64_t>(nrows + 1);
+                uint64_t *tmp = sb.get<uint64_t>(scan_scratch_entries(nrows + 1));
+                mxm_long_flag_kernel<<<grid_for(nrows, 256), 256, 0, s>>>(a->rowptr, wscan, r0, nrows, cap, flag, lp);
+                launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{flag}, nrows, rank, tmp, s);
+                launches += device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{lp}, nrows, lpscan, tmp, s);
+                uint64_t nl = 0, pl = 0;
+                { Gather g(s); g.add(&nl, (const uint64_t *)rank + nrows); g.add(&pl, (const uint64_t *)lpscan + nrows); g.wait(); }
+                if (nl) {
+                    uint32_t *long_rows = sb.get<uint32_t>(nl);
+                    uint64_t *loff = sb.get<uint64_t>(nl + 1);
+                    mxm_long_list_kernel<<<grid_for(nrows + 1, 256), 256, 0, s>>>(flag, rank, lpscan, r0, nrows, long_rows, loff);
+                    uint64_t *keys[2] = {sb.get<uint64_t>(pl + 1), sb.get<uint64_t>(pl + 1)};   // +1: the idle one holds the run heads later
+                    uint32_t *poss[2] = {sb.get<uint32_t>(pl), sb.get<uint32_t>(pl)};
+                    uint32_t *hist = sb.get<uint32_t>(sort_hist_entries(pl));
+                    uint32_t *hist_tmp = sb.get<uint32_t>(scan_scratch_entries(sort_hist_entries(pl)));
+                    V *pval = sb.get<V>(pl), *sorted_val = sb.get<V>(pl);
+                    launch_mxm_expand<T>(sr.mul, op, s, long_rows, loff, (uint32_t)nl, pl, colbits, keys[0], poss[0], pval);
+                    const int nbits = colbits + bits_for(nl);
+                    const int cur = device_radix_sort_pairs<uint64_t>(keys, poss, pl, nbits, hist, hist_tmp, s, ctx->rank_atomic);
+                    launches += 2 + (uint32_t)((nbits + 7) / 8) * (2 + scan_launches(sort_blocks(pl) * kRadix));
+                    mxm_sorted_values_kernel<V><<<grid_for(pl, 256), 256, 0, s>>>(poss[cur], pval, pl, sorted_val);
+                    uint64_t *headscan = sb.get<uint64_t>(pl + 1);
+                    uint64_t *headscan_tmp = sb.get<uint64_t>(scan_scratch_entries(pl));
+                    launches += 1 + device_exclusive_scan<HeavyHeadFlag, uint64_t>(HeavyHeadFlag{keys[cur]}, pl, headscan, headscan_tmp, s);
+                    uint64_t *head_pos = keys[cur ^ 1];   // one entry per run and a sentinel, <= pl + 1
+                    heavy_heads_kernel<<<grid_for(pl + 1, 256), 256, 0, s>>>(keys[cur], headscan, pl, head_pos);
+                    if (sr.add == EW_PLUS) launch_mxm_fold_add<T, EW_PLUS>(op, s, keys[cur], sorted_val, headscan, head_pos, pl, long_rows, loff, colbits, p0, tcol, tval);
+                    else if (sr.add == EW_MIN) launch_mxm_fold_add<T, EW_MIN>(op, s, keys[cur], sorted_val, headscan, head_pos, pl, long_rows, loff, colbits, p0, tcol, tval);
+                    else if (sr.add == EW_MAX) launch_mxm_fold_add<T, EW_MAX>(op, s, keys[cur], sorted_val, headscan, head_pos, pl, long_rows, loff, colbits, p0, tcol, tval);
+                    else launch_mxm_fold_add<T, EW_FIRST>(op, s, keys[cur], sorted_val, headscan, head_pos, pl, long_rows, loff, colbits, p0, tcol, tval);
+                    mxm_long_counts_kernel<<<grid_for(nl, 256), 256, 0, s>>>(long_rows, loff, (uint32_t)nl, headscan, cnt);
+                    launches += 3;
+                }
+            }
+            // the batch's output at its exact size: the scan of its rows' counts, ONE read-back, the slots' entries gathered
+            uint64_t *bptr = nb == 1 ? (uint64_t *)res->rowptr : sb.get<uint64_t>(nrows + 1);
+            uint64_t *tmp = sb.get<uint64_t>(scan_scratch_entries(nrows + 1));
+            launches += device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{cnt + r0}, nrows, bptr, tmp, s);
+            const uint64_t nnz_b_out = d2h((const uint64_t *)bptr + nrows, s);
+            BatchOut o{nullptr, nullptr, nnz_b_out};
+            if (nb == 1) {
+                alloc_entries<T>(res, nnz_b_out);
+                o.col = res->colidx;
+                o.val = (V *)res->vals;
+            } else {
+                o.col = sc.get<uint32_t>(nnz_b_out);
+                o.val = sc.get<V>(nnz_b_out);
+            }
+            if (nnz_b_out) {
+                mxm_gather_kernel<V><<<grid_for(nnz_b_out, 256), 256, 0, s>>>(a->rowptr, wscan, r0, nrows, p0, bptr, nnz_b_out, tcol, tval, o.col, o.val);
+                launches++;
+            }
+            outs.push_back(o);
+            nnz_out += nnz_b_out;
+            OSP_HIP(hipStreamSynchronize(s));   // (sb goes back to the pool)
+        }
+        if (nb > 1) {
+            // the result is the batches' outputs one after another, its row pointer the scan of all rows' counts
+            uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(M + 1));
+            launches += device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{cnt}, M, (uint64_t *)res->rowptr, tmp, s);
+            alloc_entries<T>(res, nnz_out);
+            uint64_t at = 0;
+            for (const BatchOut &o : outs) {
+                if (!o.nnz) continue;
+                OSP_HIP(hipMemcpyAsync(res->colidx + at, o.col, o.nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+                OSP_HIP(hipMemcpyAsync((V *)res->vals + at, o.val, o.nnz * sizeof(V), hipMemcpyDeviceToDevice, s));
+                at += o.nnz;
+            }
+        }
+    }
+    finish_csr(res, ev, nnz_out, s);
+    res->info.partials = products;
+    *st = osp_mxm_stats_t{};
+    st->nnz_a = nnz_a;
+    st->nnz_b = nnz_b;
+    st->products = products;
+    st->nnz_out = nnz_out;
+    st->short_rows = n_short;
+    st->long_rows = n_long;
+    st->batches = nb;
+    st->launches = launches;
+    st->ms_total = res->info.ms_total;
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] mxm add=%d mul=%d M=%llu K=%llu N=%llu nnz %llu , %llu -> %llu products=%llu short=%llu long=%llu batches=%u launches=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
+                sr.add, sr.mul, (unsigned long long)M, (unsigned long long)K, (unsigned long long)N, (unsigned long long)nnz_a,
+                (unsigned long long)nnz_b, (unsigned long long)nnz_out, (unsigned long long)products, (unsigned long long)n_short,
+                (unsigned long long)n_long, nb, launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
+}
+
 // ---- a CSR result and dense vectors: reduce, apply, vertex select (osp_vector.h) ----
 // R over every segment of (ptr, vals) into out[0, nseg): the short segments by a wave each, the long ones block by block
 // into a pool buffer whose segments (one per long segment) are the next level's input.  nent: an upper bound of the level's
@@ -1796,6 +2001,30 @@ int osp_csr_ewise(osp_result_t a_, osp_result_t b_, const osp_ewise_t *ew, osp_r
         osp_ewise_stats_t st{};
         const int rc = new_result(a->ctx, a->dtype, out, [&](auto tag, Result *res) {
             ewise_impl<decltype(tag)>(a->ctx, a, b, res, *ew, &st);
+        });
+        if (stats) *stats = st;
+        return rc;
+    });
+}
+
+int osp_csr_mxm(osp_result_t a_, osp_result_t b_, const osp_semiring_t *sr, osp_result_t *out, osp_mxm_stats_t *stats) {
+    Result *a = (Result *)a_, *b = (Result *)b_;
+    if (!a || !b || !sr || !out) return fail(OSP_ERR_ARG, "null argument");
+    if (a->partials || b->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
+    return guard([&] {
+        if (sr->add != OSP_EWISE_PLUS && sr->add != OSP_EWISE_MIN && sr->add != OSP_EWISE_MAX && sr->add != OSP_EWISE_FIRST)
+            throw Error(OSP_ERR_ARG, "mxm: add is not one of PLUS, MIN, MAX, FIRST");
+        if (sr->mul < OSP_EWISE_PLUS || sr->mul > OSP_EWISE_SECOND) throw Error(OSP_ERR_ARG, "mxm: mul is not one of TIMES, PLUS, MIN, MAX, FIRST, SECOND");
+        for (uint32_t w : sr->reserved)
+            if (w) throw Error(OSP_ERR_ARG, "mxm: reserved words must be 0");
+        if (a->ctx != b->ctx) throw Error(OSP_ERR_ARG, "mxm: the operands belong to different contexts");
+        if (a->dtype != b->dtype) throw Error(OSP_ERR_ARG, "mxm: the operands' dtypes differ");
+        if (a->info.nnz_c >= 0xffffffffull || b->info.nnz_c >= 0xffffffffull)
+            throw Error(OSP_ERR_ARG, "mxm: operands with >= 2^32 - 1 non-zeros are not supported");
+        if (a->info.N != b->info.M) throw Error(OSP_ERR_DIM, "mxm: a's N differs from b's M");
+        osp_mxm_stats_t st{};
+        const int rc = new_result(a->ctx, a->dtype, out, [&](auto tag, Result *res) {
+            mxm_impl<decltype(tag)>(a->ctx, a, b, res, *sr, &st);
         });
         if (stats) *stats = st;
         return rc;

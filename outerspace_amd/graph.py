@@ -5,7 +5,8 @@ and edge support and k-truss on the masked product with the entry filter ``osp_c
 (``edge_support``, ``k_truss``, ``truss_decomposition``, at the end), and personalised PageRank, which sums a series of
 products with the element-wise union ``osp_csr_ewise`` (``personalized_pagerank``), and k-core, Jaccard similarity and the
 clustering coefficient on ``osp_csr_reduce`` / ``osp_csr_apply_vectors`` / ``osp_csr_select_vertices`` (``core_numbers``,
-``k_core``, ``jaccard_similarity``, ``local_clustering``).
+``k_core``, ``jaccard_similarity``, ``local_clustering``), and weighted paths on the semiring product of two results
+``osp_csr_mxm`` (``shortest_paths``, ``widest_paths``, ``min_plus_closure``, at the end).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -861,3 +862,223 @@ def local_clustering(rows, cols, n=None, *, dtype=np.float64, ctx=None):
     some = d64 >= 2.0
     cc[some] = t64[some] / (d64[some] * (d64[some] - 1.0))
     return cc
+
+
+# ---- weighted paths on the semiring product of two results (osp_csr_mxm) -------------------------------
+
+def weighted_adjacency(rows, cols, n=None, weights=None, *, directed=False, keep="min", device=None):
+    """The weighted adjacency matrix of an edge list (duplicates and self loops allowed): self loops are dropped, an
+    undirected graph (``directed=False``) gets every edge in both directions, and duplicate edges become one that keeps the
+    smallest (``keep="min"``) or the largest (``"max"``) of their weights.  ``weights=None`` means 1.0 for every edge.
+    Returns (n, rowptr int64, colidx int64, vals float64) as tensors on `device` (default: the edges'), CSR with ascending
+    columns.  Runs on the CPU as well."""
+    if keep not in ("min", "max"):
+        raise ValueError('keep must be "min" or "max"')
+    device = torch.device(device) if device is not None else (rows.device if torch.is_tensor(rows) else torch.device("cpu"))
+    r, c = _as_index(rows, device), _as_index(cols, device)
+    if r.shape != c.shape:
+        raise ValueError("rows and cols must have the same length")
+    if n is None:
+        n = int(torch.maximum(r.max(), c.max()).item()) + 1 if r.numel() else 0
+    n = int(n)
+    if r.numel() and (int(torch.minimum(r.min(), c.min()).item()) < 0 or int(torch.maximum(r.max(), c.max()).item()) >= n):
+        raise ValueError(f"vertex ids must lie in [0, {n})")
+    if weights is None:
+        wt = torch.ones(r.numel(), dtype=torch.float64, device=device)
+    else:
+        wt = torch.as_tensor(np.asarray(weights, np.float64) if not torch.is_tensor(weights) else weights).to(device=device, dtype=torch.float64)
+        if wt.shape != r.shape:
+            raise ValueError("weights must have one entry per edge")
+    loop = r != c
+    r, c, wt = r[loop], c[loop], wt[loop]
+    keys = r * n + c
+    if not directed:
+        keys, wt = torch.cat([keys, c * n + r]), torch.cat([wt, wt])
+    key, inv = torch.unique(keys, return_inverse=True)
+    w = torch.zeros(key.numel(), dtype=torch.float64, device=device)
+    if key.numel():
+        w.scatter_reduce_(0, inv, wt, reduce="amin" if keep == "min" else "amax", include_self=False)
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    if n:
+        rowptr[1:] = torch.cumsum(torch.bincount(key // n, minlength=n), 0)
+    return n, rowptr, key % n, w
+
+
+def _check_weights(weights):
+    if weights is None:
+        return
+    w = np.asarray(weights.cpu() if torch.is_tensor(weights) else weights, np.float64)
+    if w.size and not bool((w >= 0).all()):
+        raise ValueError("weights must be non-negative (and not NaN)")
+
+
+def _paths_setup(rows, cols, n, weights, directed, keep, dtype, ctx):
+    """What the path functions share: the checks of the arguments, the context (without a GPU this is where they fail), and
+    the weighted adjacency on its device.  Returns (ctx, device, dtype, n, rowptr, cols int32, vals of dtype)."""
+    dtype = np.dtype(dtype).type
+    if dtype not in (np.float32, np.float64):
+        raise TypeError("dtype must be float32 or float64")
+    _check_weights(weights)
+    ctx = ctx or _S.default_context()
+    device = torch.device("cuda", ctx.device)
+    n, rowptr, colidx, vals = weighted_adjacency(rows, cols, n, weights, directed=directed, keep=keep, device=device)
+    return ctx, device, dtype, n, rowptr, colidx.to(torch.int32), vals.to(_torch_dtype(dtype))
+
+
+def _csr_result(ctx, dtype, M, N, rowptr, cols, vals, device):
+    """Non-empty CSR arrays (torch, on the device) as a library result: the merge of ONE part is the part itself."""
+    torch.cuda.synchronize(device)   # the library works on its own stream
+    return ctx.merge_csr_parts_device(dtype, M, N, [(rowptr.data_ptr(), cols.data_ptr(), vals.data_ptr())])
+
+
+def _paths_info():
+    return {"rounds": 0, "frontier_nnz": [], "nnz_product": [], "products": [], "ms_product": []}
+
+
+def _relax_rounds(W, D, F, add, mul, better, keep, max_iter, info):
+    """The frontier rounds ``shortest_paths`` and ``widest_paths`` share, every step on the device.  D holds the best value
+    known per (source, vertex), F the entries that changed in the last round:
+
+        P   = F.mxm(W, add, mul)                       the values reached through the frontier
+        New = P.apply_mask(D, complement=True)         reached for the first time
+        Imp = P.intersect(D, "minus").select(better, 0)   P - D < 0 (> 0) iff P beats D: denormals are kept
+        F'  = New.union(P.apply_mask(Imp), "first")
+        D'  = D.union(P, keep)
+
+    until F' is empty or ``max_iter`` rounds were taken.  D and F are closed here when they are replaced; returns the last D
+    and F."""
+    while F.nnz and info["rounds"] < max_iter:
+        made = []
+        try:
+            P, st = F.mxm(W, add, mul)
+            made.append(P)
+            info["rounds"] += 1
+            info["frontier_nnz"].append(F.nnz)
+            info["nnz_product"].append(P.nnz)
+            info["products"].append(st["products"])
+            info["ms_product"].append(st["ms_total"])
+            New, _ = P.apply_mask(D, complement=True)
+            made.append(New)
+            Diff, _ = P.intersect(D, "minus")
+            made.append(Diff)
+            Imp, _ = Diff.select(better, 0.0)
+            made.append(Imp)
+            Pi, _ = P.apply_mask(Imp)
+            made.append(Pi)
+            F2, _ = New.union(Pi, "first")
+            made.append(F2)
+            D2, _ = D.union(P, keep)
+        except Exception:
+            for r in made:
+                r.close()
+            raise
+        for r in (P, New, Diff, Imp, Pi, F, D):
+            r.close()
+        F, D = F2, D2
+    return D, F
+
+
+def _semiring_paths(rows, cols, n, sources, weights, directed, max_iter, dtype, ctx, add, mul, better, keep, start, absent):
+    ctx, device, dtype, n, rowptr, ci, va = _paths_setup(rows, cols, n, weights, directed, keep, dtype, ctx)
+    src = _check_sources(sources, n)
+    S = int(src.size)
+    tdt = _torch_dtype(dtype)
+    out = torch.full((S, n), absent, dtype=tdt, device=device)
+    info = _paths_info()
+    if S == 0 or n == 0:
+        return out.cpu().numpy(), info
+    s_dev = torch.as_tensor(src, device=device)
+    out.view(-1)[torch.arange(S, dtype=torch.int64, device=device) * n + s_dev] = start
+    if ci.numel() == 0:
+        return out.cpu().numpy(), info
+    max_iter = n if max_iter is None else int(max_iter)
+    from .sparse_util import _result_as_input
+    rp0 = torch.arange(S + 1, dtype=torch.int64, device=device)
+    c0, v0 = s_dev.to(torch.int32), torch.full((S,), start, dtype=tdt, device=device)
+    W = D = F = None
+    try:
+        W = _csr_result(ctx, dtype, n, n, rowptr, ci, va, device)
+        D = _csr_result(ctx, dtype, S, n, rp0, c0, v0, device)
+        F = _csr_result(ctx, dtype, S, n, rp0, c0, v0, device)
+        D, F = _relax_rounds(W, D, F, add, mul, better, keep, max_iter, info)
+        a = _result_as_input(D, device)
+        out.view(-1)[a.rows.to(torch.int64)[:a.nnz] * n + a.cols.to(torch.int64)] = a.vals
+        torch.cuda.synchronize(device)   # torch holds views of D's arrays: nothing of it is in flight when they go back to the pool
+        del a
+    finally:
+        torch.cuda.synchronize(device)
+        for r in (W, D, F):
+            if r is not None:
+                r.close()
+    return out.cpu().numpy(), info
+
+
+def shortest_paths(rows, cols, n=None, sources=(0,), *, weights=None, directed=False, max_iter=None, dtype=np.float64, ctx=None):
+    """Single-source shortest paths from every vertex of ``sources`` at once on the graph with edges (rows[e], cols[e]) of
+    weight weights[e] >= 0 on vertices [0, n): a frontier Bellman-Ford under the (MIN, PLUS) semiring, every step on the GPU.
+    D (the distances) and F (the frontier) start as the sources with value 0 and are CSR results with one row per source; a
+    round is ``P = F.mxm(W, "min", "plus")``, the entries of P that are new or smaller than D's are the next frontier, and
+    ``D = D.union(P, "min")`` (``_relax_rounds``).  The loop ends when the frontier is empty, after at most ``max_iter``
+    rounds (default n).  ``weights=None`` means 1.0: hop counts.  ``directed=False`` uses every edge in both directions;
+    duplicate edges keep the smallest weight, self loops are dropped; a negative (or NaN) weight is a ValueError.
+
+    Returns (dist, info): ``dist`` [len(sources), n] of ``dtype``, +inf where unreachable; ``info`` = rounds and per round the
+    lists frontier_nnz, nnz_product, products, ms_product (device time of the product).  A path's length is summed from the
+    source outwards, one IEEE addition per edge."""
+    return _semiring_paths(rows, cols, n, sources, weights, directed, max_iter, dtype, ctx, "min", "plus", "lt", "min", 0.0, float("inf"))
+
+
+def widest_paths(rows, cols, n=None, sources=(0,), *, weights=None, directed=False, max_iter=None, dtype=np.float64, ctx=None):
+    """Widest (maximum-bottleneck) paths from every vertex of ``sources`` at once: ``shortest_paths``' rounds under the
+    (MAX, MIN) semiring.  A path's width is the smallest weight on it; a source starts at +inf, an entry of P replaces D's
+    when it is larger, ``D = D.union(P, "max")``.  Duplicate edges keep the largest weight.
+
+    Returns (width, info): ``width`` [len(sources), n] of ``dtype``, 0 where unreachable and +inf at the source; ``info`` as
+    ``shortest_paths``."""
+    return _semiring_paths(rows, cols, n, sources, weights, directed, max_iter, dtype, ctx, "max", "min", "gt", "max", float("inf"), 0.0)
+
+
+def min_plus_closure(rows, cols, n=None, *, weights=None, dtype=np.float64, ctx=None):
+    """All-pairs distances of a SMALL undirected graph as a CSR result, by repeated squaring under (MIN, PLUS): D starts as
+    W with a zero diagonal, a round is ``D = D.union(D.mxm(D, "min", "plus"), "min")``, and the rounds end when D's nnz and
+    its row sums (``reduce``) no longer change, after at most ceil(log2 n) of them.  D[i, j] exists iff j is reachable from
+    i.  Memory is QUADRATIC in the size of a connected component: this is for graphs of a few thousand vertices.  Weights
+    as ``shortest_paths``.  Returns the CsrResult (the caller closes it); its ``rounds`` attribute is the number of
+    squarings."""
+    ctx, device, dtype, n, rowptr, ci, va = _paths_setup(rows, cols, n, weights, False, "min", dtype, ctx)
+    tdt = _torch_dtype(dtype)
+    rpi = torch.arange(n + 1, dtype=torch.int64, device=device)
+    ident = (rpi, torch.arange(n, dtype=torch.int32, device=device), torch.zeros(n, dtype=tdt, device=device))
+    if n == 0:
+        raise ValueError("the graph has no vertex")
+    D = _csr_result(ctx, dtype, n, n, *ident, device)
+    D.rounds = 0
+    if ci.numel() == 0:
+        return D
+    try:
+        W = _csr_result(ctx, dtype, n, n, rowptr, ci, va, device)
+        try:
+            D0, _ = W.union(D, "min")
+        finally:
+            W.close()
+        D.close()
+        D = D0
+        D.rounds = 0
+        sums, _ = D.reduce("rows", "plus")
+        for _ in range(int(np.ceil(np.log2(n))) if n > 1 else 0):
+            P, _ = D.mxm(D, "min", "plus")
+            try:
+                D2, _ = D.union(P, "min")
+            finally:
+                P.close()
+            D2.rounds = D.rounds + 1
+            sums2, _ = D2.reduce("rows", "plus")
+            same = D2.nnz == D.nnz and np.array_equal(sums2.view(np.uint8), sums.view(np.uint8))
+            D.close()
+            D, sums = D2, sums2.copy()
+            if same:
+                break
+    except Exception:
+        D.close()
+        raise
+    return D

@@ -201,6 +201,33 @@ class CsrResult:
         """``ewise(other, "intersect", op)``: ``op`` on the common pattern."""
         return self.ewise(other, "intersect", op)
 
+    def mxm(self, other, add="plus", mul="times"):
+        """This CSR (M x K) times ``other`` (K x N) under the semiring ``(add, mul)`` as a new M x N CSR result on the device
+        (``osp_csr_mxm``): a row-wise product of two results, nothing is ingested or transposed.  An output entry (i, j)
+        exists when some k has a stored ``self[i, k]`` and a stored ``other[k, j]``; its value is the products
+        ``mul(self[i, k], other[k, j])`` folded with ``add`` left to right in ascending k, starting AS the first product.
+        ``add`` is ``"plus" "min" "max" "first"``, ``mul`` is ``"times" "plus" "min" "max" "first" "second"``: one IEEE
+        operation each, as ``ewise`` defines them.  ``("plus", "times")`` equals ``spgemm_coo_device`` of the same operands
+        bit for bit; ``("min", "plus")`` relaxes a frontier of distances.  ``other`` is a ``CsrResult`` of the same context and
+        dtype (``self`` itself is allowed).  Returns (result, stats dict): nnz_a, nnz_b, products, nnz_out, short_rows,
+        long_rows, batches, launches, ms_total."""
+        if add not in _lib.MXM_ADD_OPS:
+            raise ValueError(f"add must be one of {' '.join(_lib.MXM_ADD_OPS)} (got {add!r})")
+        if mul not in _lib.MXM_MUL_OPS:
+            raise ValueError(f"mul must be one of {' '.join(_lib.MXM_MUL_OPS)} (got {mul!r})")
+        if not isinstance(other, CsrResult):
+            raise TypeError("other must be a CsrResult")
+        if other._ctx is not self._ctx:
+            raise OspError(_lib.ERR_ARG, "the operands belong to different contexts")
+        if other.dtype != self.dtype:
+            raise OspError(_lib.ERR_ARG, f"the operands' dtypes differ: {np.dtype(self.dtype)} and {np.dtype(other.dtype)}")
+        sr = _lib.Semiring()
+        sr.add, sr.mul = _lib.MXM_ADD_OPS[add], _lib.MXM_MUL_OPS[mul]
+        stats = _lib.MxmStats()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_csr_mxm(self._h, other._h, C.byref(sr), C.byref(h), C.byref(stats)))
+        return CsrResult(self._ctx, h), stats.as_dict()
+
     def _vector_arg(self, v, n, dtype, space, what):
         """A dense vector argument of the ``osp_csr_*`` functions that take one: (pointer, keep-alive).  ``space="host"``: an
         array-like of n values, converted to ``dtype``; ``space="device"``: a device address, or an object with
