@@ -178,6 +178,20 @@ class MxmStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class Transpose(C.Structure):
+    """osp_transpose_t"""
+    _fields_ = [("reserved", C.c_uint32 * 8)]
+
+
+class TransposeStats(C.Structure):
+    """osp_transpose_stats_t"""
+    _fields_ = [("nnz", C.c_uint64), ("path", C.c_uint32), ("passes", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float),
+                ("reserved", C.c_uint32 * 6)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -239,6 +253,9 @@ VECTOR_EXPORTS = ["osp_csr_reduce", "osp_csr_apply_vectors", "osp_csr_select_ver
 
 # every symbol include/outerspace_spgemm_mxm.h declares
 MXM_EXPORTS = ["osp_csr_mxm"]
+
+# every symbol include/outerspace_spgemm_transpose.h declares
+TRANSPOSE_EXPORTS = ["osp_csr_transpose"]
 
 _lib = None
 
@@ -325,6 +342,7 @@ def lib():
     L.osp_csr_apply_vectors.argtypes = [vp, C.POINTER(VectorApply), vp, vp, i32, C.POINTER(vp), C.POINTER(VectorStats)]
     L.osp_csr_select_vertices.argtypes = [vp, vp, vp, i32, C.POINTER(vp), C.POINTER(VectorStats)]
     L.osp_csr_mxm.argtypes = [vp, vp, C.POINTER(Semiring), C.POINTER(vp), C.POINTER(MxmStats)]
+    L.osp_csr_transpose.argtypes = [vp, C.POINTER(Transpose), C.POINTER(vp), C.POINTER(TransposeStats)]
     _lib = L
     return L
 

@@ -28,6 +28,7 @@
 #include "../../include/outerspace_spgemm_ewise.h"
 #include "../../include/outerspace_spgemm_vector.h"
 #include "../../include/outerspace_spgemm_mxm.h"
+#include "../../include/outerspace_spgemm_transpose.h"
 #include "osp_internal.h"
 #include "osp_kernels.h"
 #include "osp_split.h"
@@ -41,6 +42,7 @@
 #include "osp_ewise.h"
 #include "osp_vector.h"
 #include "osp_mxm.h"
+#include "osp_transpose.h"
 
 namespace osp {
 
@@ -1511,6 +1513,83 @@ static void mxm_impl(Context *ctx, const Result *a, const Result *b, Result *res
                 (unsigned long long)n_long, nb, launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
 }
 
+// ---- the transpose of a CSR result (osp_transpose.h) ----
+static bool env_is(const char *name, const char *value) {
+    const char *e = getenv(name);
+    return e && strcmp(e, value) == 0;
+}
+
+template <class T>
+static void transpose_impl(Context *ctx, const Result *in, Result *res, osp_transpose_stats_t *st) {
+    typedef ValueBits<T> V;
+    typedef typename TrRecord<V>::type Rec;
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint64_t M = in->info.M, N = in->info.N, nnz = in->info.nnz_c;
+    res->info = osp_result_info_t{};   // every field the transpose does not name stays 0
+    res->info.dtype = res->dtype;
+    res->info.M = N; res->info.K = in->info.K; res->info.N = M;
+    res->info.row_begin = 0; res->info.row_end = N;
+    res->info.nnz_a = nnz;
+    uint32_t path = 0, passes = 0, launches = 0;
+    if (nnz == 0) {
+        empty_result<T>(res, N, s);
+    } else if (M <= kTrMaskRows && !env_is("OSP_TRANSPOSE_PATH", "sort")) {
+        path = 1;
+        alloc_rowptr(res, N);
+        alloc_entries<T>(res, nnz);
+        // (pool buffers are recycled, and OSP_POISON fills them: the words are zeroed on every call)
+        uint64_t *mask = sc.get<uint64_t>(N);
+        uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(N));
+        OSP_HIP(hipMemsetAsync(mask, 0, N * sizeof(uint64_t), s));
+        const unsigned nchunks = grid_for(nnz, (unsigned)kCompactChunk);
+        tr_rowmask_kernel<<<nchunks, kCompactThreads, 0, s>>>(in->rowptr, in->colidx, M, N, nnz, (unsigned long long *)mask);
+        launches = 1 + device_exclusive_scan<LoadPopc64, uint64_t>(LoadPopc64{mask}, N, (uint64_t *)res->rowptr, tmp, s);
+        tr_place_kernel<V><<<nchunks, kCompactThreads, 0, s>>>(in->rowptr, in->colidx, (const V *)in->vals, M, N, nnz, mask, res->rowptr,
+                                                              res->colidx, (V *)res->vals);
+        launches++;
+    } else {
+        path = 2;
+        alloc_rowptr(res, N);
+        alloc_entries<T>(res, nnz);
+        const int nbits = std::max(1, bits_for(N));   // the bits of N - 1
+        passes = (uint32_t)((nbits + 7) / 8);
+        // the sort's (key, position) pairs between two passes: none with one pass, one pair of arrays with two
+        uint32_t *ka = nullptr, *pa = nullptr, *kb = nullptr, *pb = nullptr;
+        if (passes > 1) { ka = sc.get<uint32_t>(nnz); pa = sc.get<uint32_t>(nnz); }
+        if (passes > 2) { kb = sc.get<uint32_t>(nnz); pb = sc.get<uint32_t>(nnz); }
+        uint32_t *hist = sc.get<uint32_t>(rs_hist_entries(nnz));
+        uint32_t *hist_tmp = sc.get<uint32_t>(scan_scratch_entries(rs_hist_entries(nnz)));
+        uint32_t *sorted_cols = sc.get<uint32_t>(nnz);
+        if (env_is("OSP_TRANSPOSE_GATHER", "bisect")) {
+            const TrEpilogue<V, false> epi{nullptr, in->rowptr, (const V *)in->vals, M, res->colidx, sorted_cols, (V *)res->vals};
+            device_sort_rows(in->colidx, nnz, nbits, ka, pa, kb, pb, hist, hist_tmp, epi, s, ctx->rank_atomic);
+        } else {
+            Rec *rec = sc.get<Rec>(nnz);
+            tr_pack_kernel<V><<<grid_for(nnz, (unsigned)kCompactChunk), kCompactThreads, 0, s>>>(in->rowptr, in->colidx, (const V *)in->vals, M, nnz, rec);
+            launches++;
+            const TrEpilogue<V, true> epi{rec, nullptr, nullptr, M, res->colidx, sorted_cols, (V *)res->vals};
+            device_sort_rows(in->colidx, nnz, nbits, ka, pa, kb, pb, hist, hist_tmp, epi, s, ctx->rank_atomic);
+        }
+        launches += passes * (2 + scan_launches((uint64_t)rs_blocks(nnz) * kRadix));
+        ingest_ptr_kernel<<<grid_for(N + 1, 256), 256, 0, s>>>(sorted_cols, nnz, N, res->rowptr);
+        launches++;
+    }
+    finish_csr(res, ev, nnz, s);
+    *st = osp_transpose_stats_t{};
+    st->nnz = nnz;
+    st->path = path;
+    st->passes = passes;
+    st->launches = launches;
+    st->ms_total = res->info.ms_total;
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] transpose M=%llu N=%llu nnz=%llu path=%u passes=%u launches=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
+                (unsigned long long)M, (unsigned long long)N, (unsigned long long)nnz, path, passes, launches, st->ms_total,
+                (unsigned long long)ctx->malloc_calls);
+}
+
 // ---- a CSR result and dense vectors: reduce, apply, vertex select (osp_vector.h) ----
 // R over every segment of (ptr, vals) into out[0, nseg): the short segments by a wave each, the long ones block by block
 // into a pool buffer whose segments (one per long segment) are the next level's input.  nent: an upper bound of the level's
@@ -2025,6 +2104,25 @@ int osp_csr_mxm(osp_result_t a_, osp_result_t b_, const osp_semiring_t *sr, osp_
         osp_mxm_stats_t st{};
         const int rc = new_result(a->ctx, a->dtype, out, [&](auto tag, Result *res) {
             mxm_impl<decltype(tag)>(a->ctx, a, b, res, *sr, &st);
+        });
+        if (stats) *stats = st;
+        return rc;
+    });
+}
+
+int osp_csr_transpose(osp_result_t in_, const osp_transpose_t *tp, osp_result_t *out, osp_transpose_stats_t *stats) {
+    Result *in = (Result *)in_;
+    if (!in || !out) return fail(OSP_ERR_ARG, "null argument");
+    if (in->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
+    return guard([&] {
+        if (tp)
+            for (uint32_t w : tp->reserved)
+                if (w) throw Error(OSP_ERR_ARG, "transpose: reserved words must be 0");
+        if (in->info.nnz_c >= 0xffffffffull) throw Error(OSP_ERR_ARG, "transpose: an operand with >= 2^32 - 1 non-zeros is not supported");
+        if (in->info.M > (1ull << 32)) throw Error(OSP_ERR_DIM, "transpose: a row index of in must fit a column of out");
+        osp_transpose_stats_t st{};
+        const int rc = new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {
+            transpose_impl<decltype(tag)>(in->ctx, in, res, &st);
         });
         if (stats) *stats = st;
         return rc;

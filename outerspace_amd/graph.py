@@ -6,7 +6,9 @@ and edge support and k-truss on the masked product with the entry filter ``osp_c
 products with the element-wise union ``osp_csr_ewise`` (``personalized_pagerank``), and k-core, Jaccard similarity and the
 clustering coefficient on ``osp_csr_reduce`` / ``osp_csr_apply_vectors`` / ``osp_csr_select_vertices`` (``core_numbers``,
 ``k_core``, ``jaccard_similarity``, ``local_clustering``), and weighted paths on the semiring product of two results
-``osp_csr_mxm`` (``shortest_paths``, ``widest_paths``, ``min_plus_closure``, at the end).
+``osp_csr_mxm`` (``shortest_paths``, ``widest_paths``, ``min_plus_closure``), and the first functions on a DIRECTED graph,
+which need the transpose of a result ``osp_csr_transpose`` (``strongly_connected``, ``cocitation``,
+``bibliographic_coupling``, at the end).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -1082,3 +1084,131 @@ def min_plus_closure(rows, cols, n=None, *, weights=None, dtype=np.float64, ctx=
         D.close()
         raise
     return D
+
+
+# ---- directed graphs on the transpose of a result (osp_csr_transpose) ---------------------------------
+
+def _scc_info():
+    return {"rounds_forward": 0, "rounds_backward": 0, "nnz_forward": 0, "nnz_backward": 0, "ms_transpose": 0.0, "path": 0}
+
+
+def strongly_connected(rows, cols, n=None, sources=(0,), *, max_iter=None, ctx=None):
+    """For every vertex s of ``sources`` the vertices of s's strongly connected component in the DIRECTED graph with edges
+    (rows[e], cols[e]) on vertices [0, n), every step on the GPU.  W is the directed unit-weight adjacency as a CSR result;
+    the relaxation rounds of ``shortest_paths`` (``_relax_rounds``, (MIN, PLUS)) run forwards on W and backwards on
+    ``W.transpose()``, and the members are the coordinates BOTH distance results hold (``intersect``): the vertices s reaches
+    that reach s.  Each direction takes at most ``max_iter`` rounds (default n); fewer rounds than the component's diameter
+    cut it short.  Duplicate edges and self loops are allowed.
+
+    Returns (member, info): ``member`` bool [len(sources), n], a source always in its own component; ``info`` =
+    rounds_forward, rounds_backward, nnz_forward, nnz_backward (the entries of the two distance results), ms_transpose and
+    path (the transpose's: 0 nothing launched, 1 row mask, 2 sort)."""
+    dtype = np.float64
+    ctx, device, dtype, n, rowptr, ci, va = _paths_setup(rows, cols, n, None, True, "min", dtype, ctx)
+    src = _check_sources(sources, n)
+    S = int(src.size)
+    info = _scc_info()
+    out = torch.zeros((S, n), dtype=torch.bool, device=device)
+    if S == 0 or n == 0:
+        return out.cpu().numpy(), info
+    s_dev = torch.as_tensor(src, device=device)
+    out.view(-1)[torch.arange(S, dtype=torch.int64, device=device) * n + s_dev] = True
+    if ci.numel() == 0:
+        return out.cpu().numpy(), info
+    max_iter = n if max_iter is None else int(max_iter)
+    from .sparse_util import _result_as_input
+    tdt = _torch_dtype(dtype)
+    rp0 = torch.arange(S + 1, dtype=torch.int64, device=device)
+    c0, v0 = s_dev.to(torch.int32), torch.zeros(S, dtype=tdt, device=device)
+    held, dist = [], {}
+    try:
+        W = _csr_result(ctx, dtype, n, n, rowptr, ci, va, device)
+        held.append(W)
+        Wt, st = W.transpose()
+        held.append(Wt)
+        info["ms_transpose"], info["path"] = st["ms_total"], st["path"]
+        for side, graph in (("forward", W), ("backward", Wt)):
+            D = _csr_result(ctx, dtype, S, n, rp0, c0, v0, device)
+            F = _csr_result(ctx, dtype, S, n, rp0, c0, v0, device)
+            rounds = _paths_info()
+            D, F = _relax_rounds(graph, D, F, "min", "plus", "lt", "min", max_iter, rounds)   # (closes what it replaces)
+            F.close()
+            held.append(D)
+            dist[side] = D
+            info["rounds_" + side], info["nnz_" + side] = rounds["rounds"], D.nnz
+        both, _ = dist["forward"].intersect(dist["backward"], "first")
+        held.append(both)
+        a = _result_as_input(both, device)
+        out.view(-1)[a.rows.to(torch.int64)[:a.nnz] * n + a.cols.to(torch.int64)] = True
+        torch.cuda.synchronize(device)   # torch holds views of the result's arrays: nothing of it is in flight when they go back to the pool
+        del a
+    finally:
+        torch.cuda.synchronize(device)
+        for r in held:
+            r.close()
+    return out.cpu().numpy(), info
+
+
+def _directed_pattern_result(rows, cols, n, dtype, ctx):
+    """The deduplicated directed 0/1 adjacency of an edge list, self loops kept, as a CSR result with unit values of
+    ``dtype`` (the context first: without a GPU this is where the callers fail).  Returns (ctx, A)."""
+    ctx = ctx or _S.default_context()
+    device = torch.device("cuda", ctx.device)
+    dtype = np.dtype(dtype).type
+    if dtype not in (np.float32, np.float64):
+        raise TypeError("dtype must be float32 or float64")
+    r, c = _as_index(rows, device), _as_index(cols, device)
+    if r.shape != c.shape:
+        raise ValueError("rows and cols must have the same length")
+    if n is None:
+        n = int(torch.maximum(r.max(), c.max()).item()) + 1 if r.numel() else 0
+    n = int(n)
+    if r.numel() and (int(torch.minimum(r.min(), c.min()).item()) < 0 or int(torch.maximum(r.max(), c.max()).item()) >= n):
+        raise ValueError(f"vertex ids must lie in [0, {n})")
+    key = torch.unique(r * n + c)
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    if n and key.numel():
+        rowptr[1:] = torch.cumsum(torch.bincount(key // n, minlength=n), 0)
+    # (an edgeless graph: arrays of one unused element, a pointer is never null)
+    ci = (key % n).to(torch.int32) if key.numel() else torch.zeros(1, dtype=torch.int32, device=device)
+    va = torch.ones(max(int(key.numel()), 1), dtype=_torch_dtype(dtype), device=device)
+    # a count is at most a vertex's degree
+    if dtype == np.float32 and key.numel() and max(int(torch.bincount(key // n).max().item()), int(torch.bincount(key % n).max().item())) >= 1 << 24:
+        raise ValueError("float32 holds the counts exactly only while the maximum degree is below 2^24: use float64")
+    return ctx, _csr_result(ctx, dtype, n, n, rowptr, ci, va, device)
+
+
+def cocitation(rows, cols, n=None, *, dtype=np.float64, ctx=None):
+    """The co-citation counts of the DIRECTED graph with edges (rows[e], cols[e]) on vertices [0, n): C = A^T A without its
+    diagonal, A the deduplicated 0/1 adjacency (self loops kept), so C[u, v] = the number of vertices with an edge to both
+    u and v.  ``A.matmul(A, self_transposed=True)`` -- A's CSR arrays are the CSC of A^T, nothing is transposed -- then
+    ``select("offdiag")``.  Returns the CsrResult (the caller closes it); the counts are small integers, exact in both
+    dtypes."""
+    ctx, A = _directed_pattern_result(rows, cols, n, dtype, ctx)
+    try:
+        P = A.matmul(A, self_transposed=True)
+    finally:
+        A.close()
+    try:
+        return P.select("offdiag")[0]
+    finally:
+        P.close()
+
+
+def bibliographic_coupling(rows, cols, n=None, *, dtype=np.float64, ctx=None):
+    """The bibliographic coupling counts of the DIRECTED graph: B = A A^T without its diagonal, A as in ``cocitation``, so
+    B[u, v] = the number of vertices both u and v have an edge to.  One ``At = A.transpose()`` on the device, then
+    ``A.matmul(At)`` and ``select("offdiag")``.  Returns the CsrResult (the caller closes it)."""
+    ctx, A = _directed_pattern_result(rows, cols, n, dtype, ctx)
+    At = None
+    try:
+        At, _ = A.transpose()
+        P = A.matmul(At)
+    finally:
+        A.close()
+        if At is not None:
+            At.close()
+    try:
+        return P.select("offdiag")[0]
+    finally:
+        P.close()

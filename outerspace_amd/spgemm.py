@@ -228,6 +228,41 @@ class CsrResult:
         _lib.check(_lib.lib().osp_csr_mxm(self._h, other._h, C.byref(sr), C.byref(h), C.byref(stats)))
         return CsrResult(self._ctx, h), stats.as_dict()
 
+    def transpose(self):
+        """This CSR (M x N) transposed as a new N x M CSR result on the device (``osp_csr_transpose``): entry (j, i) exists
+        iff this result has (i, j), columns ascend in every row, values keep their bits, and transposing twice gives the same
+        three arrays back.  A result of at most 64 rows takes the row-mask path (nothing is sorted), everything else a
+        stable radix sort by column.  Returns (result, stats dict): nnz, path (0 nothing launched, 1 row mask, 2 sort),
+        passes, launches, ms_total."""
+        stats = _lib.TransposeStats()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_csr_transpose(self._h, None, C.byref(h), C.byref(stats)))
+        return CsrResult(self._ctx, h), stats.as_dict()
+
+    def matmul(self, other, *, self_transposed=False, validate=False, partial_capacity=0):
+        """This CSR (M x K) times ``other`` (K x N) with + and x through the outer-product pipeline
+        (``osp_spgemm_csc_csr``), as a new M x N CSR result: this result is transposed on the device -- the CSR arrays of the
+        transpose ARE this result's CSC arrays, which the pipeline takes for its left operand -- and the temporary is closed.
+        ``self_transposed=True`` computes ``self^T @ other`` instead (self K x M), with no transpose at all: self's own CSR
+        arrays are the CSC of ``self^T``.  Equals ``mxm(other, "plus", "times")`` in row pointers, columns and value bits.
+        ``other`` is a ``CsrResult`` of the same context and dtype (``self`` itself is allowed)."""
+        if not isinstance(other, CsrResult):
+            raise TypeError("other must be a CsrResult")
+        if other._ctx is not self._ctx:
+            raise OspError(_lib.ERR_ARG, "the operands belong to different contexts")
+        if other.dtype != self.dtype:
+            raise OspError(_lib.ERR_ARG, f"the operands' dtypes differ: {np.dtype(self.dtype)} and {np.dtype(other.dtype)}")
+        M, K = (self.shape[1], self.shape[0]) if self_transposed else self.shape
+        if K != other.shape[0]:
+            raise OspError(_lib.ERR_DIM, f"the inner dimensions differ: {K} and {other.shape[0]}")
+        at = self if self_transposed else self.transpose()[0]
+        try:
+            return self._ctx.spgemm_csc_csr_device(self.dtype, M, K, other.shape[1], (*at.device_ptrs(), *other.device_ptrs()),
+                                                   validate=validate, partial_capacity=partial_capacity)
+        finally:
+            if at is not self:
+                at.close()
+
     def _vector_arg(self, v, n, dtype, space, what):
         """A dense vector argument of the ``osp_csr_*`` functions that take one: (pointer, keep-alive).  ``space="host"``: an
         array-like of n values, converted to ``dtype``; ``space="device"``: a device address, or an object with
