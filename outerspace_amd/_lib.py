@@ -178,6 +178,19 @@ class MxmStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+# the add operators osp_csr_mxv takes: the value operators of osp_csr_reduce (mul: MXM_MUL_OPS)
+MXV_ADD_OPS = {name: EWISE_OPS[name] for name in ("plus", "min", "max")}
+
+
+class MxvStats(C.Structure):
+    """osp_mxv_stats_t"""
+    _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("long_segments", C.c_uint64), ("group", C.c_uint32),
+                ("launches", C.c_uint32), ("ms_total", C.c_float), ("reserved", C.c_uint32 * 7)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 class Transpose(C.Structure):
     """osp_transpose_t"""
     _fields_ = [("reserved", C.c_uint32 * 8)]
@@ -256,6 +269,9 @@ MXM_EXPORTS = ["osp_csr_mxm"]
 
 # every symbol include/outerspace_spgemm_transpose.h declares
 TRANSPOSE_EXPORTS = ["osp_csr_transpose"]
+
+# every symbol include/outerspace_spgemm_mxv.h declares
+MXV_EXPORTS = ["osp_csr_mxv"]
 
 _lib = None
 
@@ -343,6 +359,7 @@ def lib():
     L.osp_csr_select_vertices.argtypes = [vp, vp, vp, i32, C.POINTER(vp), C.POINTER(VectorStats)]
     L.osp_csr_mxm.argtypes = [vp, vp, C.POINTER(Semiring), C.POINTER(vp), C.POINTER(MxmStats)]
     L.osp_csr_transpose.argtypes = [vp, C.POINTER(Transpose), C.POINTER(vp), C.POINTER(TransposeStats)]
+    L.osp_csr_mxv.argtypes = [vp, C.POINTER(Semiring), vp, vp, i32, C.POINTER(MxvStats)]
     _lib = L
     return L
 

@@ -29,6 +29,7 @@
 #include "../../include/outerspace_spgemm_vector.h"
 #include "../../include/outerspace_spgemm_mxm.h"
 #include "../../include/outerspace_spgemm_transpose.h"
+#include "../../include/outerspace_spgemm_mxv.h"
 #include "osp_internal.h"
 #include "osp_kernels.h"
 #include "osp_split.h"
@@ -43,6 +44,7 @@
 #include "osp_vector.h"
 #include "osp_mxm.h"
 #include "osp_transpose.h"
+#include "osp_mxv.h"
 
 namespace osp {
 
@@ -1593,11 +1595,11 @@ static void transpose_impl(Context *ctx, const Result *in, Result *res, osp_tran
 // ---- a CSR result and dense vectors: reduce, apply, vertex select (osp_vector.h) ----
 // R over every segment of (ptr, vals) into out[0, nseg): the short segments by a wave each, the long ones block by block
 // into a pool buffer whose segments (one per long segment) are the next level's input.  nent: an upper bound of the level's
-// entries.  One read-back per level that can hold a long segment (the number of long segments).
+// entries.  One read-back per level that can hold a long segment (the number of long segments).  map: where a segment's
+// result goes in out (null: at its own number).
 template <class T, int OP>
 static void reduce_segments(Scratch &sc, hipStream_t s, const int64_t *ptr, const T *vals, uint64_t nseg, uint64_t nent, T *out,
-                            uint64_t &long_segments, uint32_t &launches) {
-    const uint32_t *map = nullptr;
+                            uint64_t &long_segments, uint32_t &launches, const uint32_t *map = nullptr) {
     for (int level = 0;; level++) {
         reduce_short_kernel<T, OP><<<grid_for(nseg, kReduceWaves), kReduceWaves * kWave, 0, s>>>(ptr, vals, nseg, map, out);
         launches++;
@@ -1694,6 +1696,114 @@ static void reduce_impl(Context *ctx, const Result *in, int axis, int op, void *
     if (getenv("OSP_VERBOSE"))
         fprintf(stderr, "[osp] reduce axis=%d op=%d M=%llu N=%llu nnz=%llu long=%llu launches=%u %.3f ms\n", axis, op, (unsigned long long)M,
                 (unsigned long long)N, (unsigned long long)nnz, (unsigned long long)long_segments, launches, st->ms_total);
+}
+
+// ---- a CSR result times a dense vector under a semiring (osp_mxv.h) ----
+// body(integral_constant ADD, integral_constant MUL) for the RED_* value `add` and the EW_* value `mul` (PLUS .. SECOND)
+template <int ADD, int MUL = 0, class F>
+static void mxv_with_mul(int mul, F &&body) {
+    if constexpr (MUL <= EW_SECOND) {
+        if (mul == MUL) body(std::integral_constant<int, ADD>{}, std::integral_constant<int, MUL>{});
+        else mxv_with_mul<ADD, MUL + 1>(mul, body);
+    }
+}
+template <class F>
+static void mxv_with_ops(int add, int mul, F &&body) {
+    if (add == RED_PLUS) mxv_with_mul<RED_PLUS>(mul, body);
+    else if (add == RED_MIN) mxv_with_mul<RED_MIN>(mul, body);
+    else mxv_with_mul<RED_MAX>(mul, body);
+}
+
+// log2 of the lanes a packed row gets.  OSP_MXV_GROUP = 4, 8, 16, 32 or 64 forces it (any other value: automatic).
+// Automatic: the smallest g of at least the mean row length, the fastest of the five on the R-MAT adjacency that was measured
+// (by 2-4 % over g = 64, MEASUREMENTS.md section 0l; means below 4 and other distributions: not measured).
+static uint32_t mxv_group_log2(uint64_t M, uint64_t nnz) {
+    const uint64_t forced = env_u64("OSP_MXV_GROUP", 0);
+    for (uint32_t lg = 2; lg <= 6; lg++)
+        if (forced == (1ull << lg)) return lg;
+    uint32_t lg = 2;
+    while (lg < 6 && (M << lg) < nnz) lg++;
+    return lg;
+}
+
+template <class T>
+static void mxv_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, const void *x_in, void *y_out, osp_memspace_t space,
+                     osp_mxv_stats_t *st) {
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint64_t M = in->info.M, N = in->info.N, nnz = in->info.nnz_c;
+    const int add = sr.add == OSP_EWISE_PLUS ? RED_PLUS : sr.add == OSP_EWISE_MIN ? RED_MIN : RED_MAX;
+    const uint32_t lg = mxv_group_log2(M, nnz);
+    uint64_t long_segments = 0;
+    uint32_t launches = 0;
+    // (the vector is formed in a pool buffer and copied out last: x may be y, and a call that fails leaves y as it was)
+    T *out = sc.get<T>(M);
+    std::vector<T> ids;
+    if (M && nnz) {
+        const T *x = sr.mul == OSP_EWISE_FIRST ? nullptr : to_device(sc, (const T *)x_in, N, space, s);
+        const int64_t *rowptr = in->rowptr;
+        const uint32_t *col = in->colidx;
+        const T *vals = (const T *)in->vals;
+        mxv_with_ops(add, sr.mul, [&](auto a, auto m) {
+            constexpr int ADD = decltype(a)::value, MUL = decltype(m)::value;
+            const uint64_t waves = (M + (kWave >> lg) - 1) >> (6 - lg);
+            mxv_rows_kernel<T, ADD, MUL><<<grid_for(waves, kReduceWaves), kReduceWaves * kWave, 0, s>>>(rowptr, col, vals, x, M, lg, out);
+            launches++;
+            if (nnz <= kReduceBlock) return;   // (no row can be long)
+            // the long rows, listed and cut into blocks as reduce_segments lists and cuts a level's long segments
+            unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MCL_COUNTERS);
+            zero_async(s, {{counters, MCL_COUNTERS * sizeof(uint64_t)}});
+            uint32_t *long_rows = sc.get<uint32_t>(nnz / ((uint64_t)kReduceBlock + 1) + 1);
+            mcl_classify_kernel<<<grid_for(M, 256), 256, 0, s>>>(rowptr, M, kReduceBlock, long_rows, counters);
+            launches += 2;
+            const uint64_t n_long = d2h((const uint64_t *)counters + MCL_NLONG, s);
+            long_segments = n_long;
+            if (!n_long) return;
+            const uint64_t max_blocks = nnz / kReduceBlock + n_long;
+            uint32_t *nblk = sc.get<uint32_t>(n_long + 1), *map = sc.get<uint32_t>(n_long);
+            int64_t *blkptr = sc.get<int64_t>(n_long + 1);
+            uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(n_long + 1));
+            T *partial = sc.get<T>(max_blocks);
+            reduce_long_setup_kernel<<<grid_for(n_long, 256), 256, 0, s>>>(rowptr, long_rows, n_long, nullptr, nblk, map);
+            launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{nblk}, n_long, (uint64_t *)blkptr, tmp, s);
+            mxv_blocks_kernel<T, ADD, MUL><<<grid_for(max_blocks, kReduceWaves), kReduceWaves * kWave, 0, s>>>(rowptr, col, vals, x, long_rows, blkptr,
+                                                                                                               n_long, partial);
+            launches++;
+            // the blocks' results are plain values: every further level is osp_csr_reduce's
+            uint64_t deeper = 0;
+            reduce_segments<T, ADD>(sc, s, blkptr, partial, n_long, max_blocks, out, deeper, launches, map);
+        });
+    } else if (M) {
+        const T inf = std::numeric_limits<T>::infinity();
+        ids.assign(M, add == RED_MIN ? inf : add == RED_MAX ? -inf : T(0));   // every row is empty: no kernel
+    }
+    OSP_HIP(hipEventRecord(ev.b, s));
+    OSP_HIP(hipStreamSynchronize(s));
+    OSP_HIP(hipGetLastError());
+    if (M) {
+        if (!ids.empty()) {
+            if (space == OSP_DEVICE) copy_h2d(y_out, ids.data(), M * sizeof(T), s);
+            else memcpy(y_out, ids.data(), M * sizeof(T));
+        } else if (space == OSP_DEVICE) {
+            OSP_HIP(hipMemcpyAsync(y_out, out, M * sizeof(T), hipMemcpyDeviceToDevice, s));
+        } else {
+            copy_d2h(y_out, out, M * sizeof(T), s);
+        }
+        OSP_HIP(hipStreamSynchronize(s));
+    }
+    *st = osp_mxv_stats_t{};
+    st->nnz_in = nnz;
+    st->nnz_out = M;
+    st->long_segments = long_segments;
+    st->group = 1u << lg;
+    st->launches = launches;
+    st->ms_total = ev.ms();
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] mxv add=%d mul=%d M=%llu N=%llu nnz=%llu group=%u long=%llu launches=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
+                sr.add, sr.mul, (unsigned long long)M, (unsigned long long)N, (unsigned long long)nnz, 1u << lg, (unsigned long long)long_segments,
+                launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
 }
 
 template <class T, int OP = 0>
@@ -2141,6 +2251,24 @@ int osp_csr_reduce(osp_result_t in_, int axis, int op, void *out_vec, osp_memspa
             throw Error(OSP_ERR_ARG, "reduce: the column axis does not support results with >= 2^32 - 1 non-zeros");
         osp_vector_stats_t st{};
         on_device(in->ctx, [&] { with_type(in->dtype, [&](auto tag) { reduce_impl<decltype(tag)>(in->ctx, in, axis, op, out_vec, space, &st); }); });
+        if (stats) *stats = st;
+        return (int)OSP_OK;
+    });
+}
+
+int osp_csr_mxv(osp_result_t in_, const osp_semiring_t *sr, const void *x, void *y, osp_memspace_t space, osp_mxv_stats_t *stats) {
+    Result *in = (Result *)in_;
+    if (!in || !sr || !y) return fail(OSP_ERR_ARG, "null argument");
+    if (in->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
+    return guard([&] {
+        check_space(space);
+        if (sr->add != OSP_EWISE_PLUS && sr->add != OSP_EWISE_MIN && sr->add != OSP_EWISE_MAX) throw Error(OSP_ERR_ARG, "mxv: add is not one of PLUS, MIN, MAX");
+        if (sr->mul < OSP_EWISE_PLUS || sr->mul > OSP_EWISE_SECOND) throw Error(OSP_ERR_ARG, "mxv: mul is not one of TIMES, PLUS, MIN, MAX, FIRST, SECOND");
+        for (uint32_t w : sr->reserved)
+            if (w) throw Error(OSP_ERR_ARG, "mxv: reserved words must be 0");
+        if (!x && sr->mul != OSP_EWISE_FIRST) throw Error(OSP_ERR_ARG, "mxv: x may be null only when mul is FIRST");
+        osp_mxv_stats_t st{};
+        on_device(in->ctx, [&] { with_type(in->dtype, [&](auto tag) { mxv_impl<decltype(tag)>(in->ctx, in, *sr, x, y, space, &st); }); });
         if (stats) *stats = st;
         return (int)OSP_OK;
     });

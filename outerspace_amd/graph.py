@@ -8,7 +8,8 @@ clustering coefficient on ``osp_csr_reduce`` / ``osp_csr_apply_vectors`` / ``osp
 ``k_core``, ``jaccard_similarity``, ``local_clustering``), and weighted paths on the semiring product of two results
 ``osp_csr_mxm`` (``shortest_paths``, ``widest_paths``, ``min_plus_closure``), and the first functions on a DIRECTED graph,
 which need the transpose of a result ``osp_csr_transpose`` (``strongly_connected``, ``cocitation``,
-``bibliographic_coupling``, at the end).
+``bibliographic_coupling``), and global PageRank and connected components on the product of a result with a dense vector
+``osp_csr_mxv`` (``pagerank``, ``connected_components``, at the end).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -1212,3 +1213,113 @@ def bibliographic_coupling(rows, cols, n=None, *, dtype=np.float64, ctx=None):
         return P.select("offdiag")[0]
     finally:
         P.close()
+
+
+# ---- a result times a dense vector (osp_csr_mxv): global PageRank, connected components ---------------------------------------------
+def _pattern_result(rows, cols, n, directed, dtype, ctx):
+    """The 0/1 pattern of an edge list as a CSR result with unit values of ``dtype``: ``_directed_pattern_result`` (self
+    loops kept) for a directed graph, ``symmetric_adjacency`` (a simple graph: no self loops) for an undirected one.
+    Returns (ctx, device, dtype, n, A); A is None when the graph has no edge."""
+    if directed:
+        ctx, A = _directed_pattern_result(rows, cols, n, dtype, ctx)
+        n, dtype = A.shape[0], A.dtype
+        if A.nnz == 0:
+            A.close()
+            A = None
+        return ctx, torch.device("cuda", ctx.device), dtype, n, A
+    ctx, device, dtype, adj = _truss_setup(rows, cols, n, dtype, ctx)
+    return ctx, device, dtype, adj.n, _adjacency_result(ctx, adj, dtype, device) if adj.nnz else None
+
+
+def pagerank(rows, cols, n=None, *, alpha=0.85, tol=1e-6, max_iter=100, directed=False, dtype=np.float64, ctx=None):
+    """The PageRank of every vertex of the graph with edges (rows[e], cols[e]) on vertices [0, n) (duplicates allowed;
+    ``directed=False``: any direction, self loops dropped; ``directed=True``: self loops kept): the power iteration of
+    ``networkx.pagerank`` without weights or personalisation, the matrix step on the GPU.  Once:
+    deg = A.reduce("rows", "count") and, for a directed graph, At = A.transpose() (an undirected A is its own transpose).
+    Per iteration  s = r / deg (0 where deg == 0);  y = At.mxv(s);  r' = alpha (y + dangling / n) + (1 - alpha) / n  with
+    dangling = the sum of r over the vertices of degree 0; it stops when the L1 norm of r' - r is below n tol.  torch
+    touches the length-n vectors only, with one synchronisation per iteration (the stop test).
+
+    Returns (rank numpy[n] of ``dtype``, info): info = iterations, converged, err (the last L1 change), nnz, ms_mxv (a list:
+    device time per iteration), launches (kernels of all mxv calls).  n == 0 and a graph without edges (uniform rank) launch
+    nothing."""
+    ctx, device, dtype, n, A = _pattern_result(rows, cols, n, directed, dtype, ctx)
+    info = {"iterations": 0, "converged": False, "err": 0.0, "nnz": 0, "ms_mxv": [], "launches": 0}
+    if A is None:
+        info["converged"] = True
+        return np.full(n, 1.0 / n if n else 0.0, dtype), info
+    td = _torch_dtype(dtype)
+    At = None
+    try:
+        info["nnz"] = A.nnz
+        deg = torch.empty(n, dtype=td, device=device)
+        _degrees(A, deg, device)
+        At = A.transpose()[0] if directed else A
+        has, zero = deg > 0, torch.zeros((), dtype=td, device=device)
+        r = torch.full((n,), 1.0 / n, dtype=td, device=device)
+        s = torch.where(has, r / deg, zero)
+        y = torch.empty(n, dtype=td, device=device)
+        torch.cuda.synchronize(device)   # the library works on its own stream
+        for _ in range(max_iter):
+            _, st = At.mxv(s, out=y)
+            dangling = r[~has].sum()
+            new = alpha * (y + dangling / n) + (1.0 - alpha) / n
+            s = torch.where(has, new / deg, zero)   # (the next step's input, before the one synchronisation)
+            err = float((new - r).abs().sum().item())
+            r = new
+            info["iterations"] += 1
+            info["err"] = err
+            info["ms_mxv"].append(st["ms_total"])
+            info["launches"] += st["launches"]
+            if err < n * tol:
+                info["converged"] = True
+                break
+        return r.cpu().numpy(), info
+    finally:
+        torch.cuda.synchronize(device)
+        A.close()
+        if At is not None and At is not A:
+            At.close()
+
+
+def connected_components(rows, cols, n=None, *, dtype=np.float64, ctx=None):
+    """The connected components of the undirected graph with edges (rows[e], cols[e]) on vertices [0, n) (any direction,
+    duplicates and self loops allowed): ``labels[v]`` is the smallest vertex id of v's component.  Labels start as the
+    vertices' own ids, held as values of ``dtype``; a ROUND is  y = A.mxv(l, "min", "second")  (the smallest label among a
+    vertex's neighbours; A's values are never read),  l' = minimum(l, y),  and one pointer jump  l' = l'[l'];  it ends with
+    the first round that changes nothing.  float32 holds ids exactly up to 2^24 only: a larger n is refused.
+
+    Returns (labels int64 numpy[n], info): info = rounds, components, ms_mxv (a list: device time per round), launches."""
+    ctx = ctx or _S.default_context()
+    if np.dtype(dtype) == np.float32 and n is not None and int(n) > 1 << 24:
+        raise ValueError("float32 holds vertex ids exactly only up to n = 2^24: use float64")
+    ctx, device, dtype, n, A = _pattern_result(rows, cols, n, False, dtype, ctx)
+    if dtype == np.float32 and n > 1 << 24:
+        if A is not None:
+            A.close()
+        raise ValueError("float32 holds vertex ids exactly only up to n = 2^24: use float64")
+    info = {"rounds": 0, "components": n, "ms_mxv": [], "launches": 0}
+    if A is None:
+        return np.arange(n, dtype=np.int64), info
+    td = _torch_dtype(dtype)
+    try:
+        lab = torch.arange(n, dtype=td, device=device)
+        y = torch.empty(n, dtype=td, device=device)
+        torch.cuda.synchronize(device)   # the library works on its own stream
+        while True:
+            _, st = A.mxv(lab, "min", "second", out=y)
+            new = torch.minimum(lab, y)
+            new = new[new.long()]
+            info["rounds"] += 1
+            info["ms_mxv"].append(st["ms_total"])
+            info["launches"] += st["launches"]
+            same = torch.equal(new, lab)   # (the round's one synchronisation)
+            lab = new
+            if same:
+                break
+        labels = lab.long().cpu().numpy()
+    finally:
+        torch.cuda.synchronize(device)
+        A.close()
+    info["components"] = int((labels == np.arange(n)).sum())
+    return labels, info

@@ -305,6 +305,53 @@ class CsrResult:
         _lib.check(_lib.lib().osp_csr_reduce(self._h, _lib.AXES[axis], _lib.REDUCE_OPS[op], ptr, space, C.byref(stats)))
         return ret, stats.as_dict()
 
+    def mxv(self, x, add="plus", mul="times", out=None, space="device"):
+        """This CSR (M x N) times the dense vector ``x`` (N values) under the semiring ``(add, mul)`` (``osp_csr_mxv``):
+        ``y[i]`` is the reduction, in ``reduce``'s bit-defined order, of ``mul(self[i, j], x[j])`` over row i's entries, in
+        one fused pass -- equal in bits to ``apply_vectors(cols=x, col_op=mul)`` followed by ``reduce("rows", add)``.  ``add``
+        is ``"plus" "min" "max"``, ``mul`` is ``"times" "plus" "min" "max" "first" "second"``; ``"first"`` reads no ``x``
+        (which may be None), ``"second"`` no value of this result.  An empty row gives +0.0, +inf, -inf.  ``x``: a device
+        address / torch tensor (``space="device"``) or an array-like (``space="host"``).  ``out=None``: returns (torch
+        tensor on the context's device, stats dict), or (numpy array, stats dict) with ``space="host"``; ``out`` a device
+        address or torch tensor of M values (a numpy array of this dtype with ``space="host"``): fills and returns it.
+        ``out is x`` is allowed on a square result.  Stats: nnz_in, nnz_out, long_segments, group, launches, ms_total."""
+        if add not in _lib.MXV_ADD_OPS:
+            raise ValueError(f"add must be one of {' '.join(_lib.MXV_ADD_OPS)} (got {add!r})")
+        if mul not in _lib.MXM_MUL_OPS:
+            raise ValueError(f"mul must be one of {' '.join(_lib.MXM_MUL_OPS)} (got {mul!r})")
+        if space not in ("device", "host"):
+            raise ValueError('space must be "device" or "host"')
+        M, N = self.shape
+        if x is None and mul != "first":
+            raise OspError(_lib.ERR_ARG, 'x may be None only when mul is "first"')
+        xp, keep_x = self._vector_arg(x if mul != "first" else None, N, self.dtype, space, "x")
+        if out is None and space == "host":
+            ret = np.empty(M, self.dtype)
+            buf = ret if M else np.empty(1, self.dtype)   # (never a null pointer)
+            yp = C.c_void_p(buf.ctypes.data)
+        elif out is None:
+            import torch
+            buf = torch.empty(max(M, 1), dtype=torch.float32 if self.dtype == np.float32 else torch.float64,
+                              device=f"cuda:{self._ctx.device}")
+            ret = buf[:M]
+            yp = C.c_void_p(buf.data_ptr())
+        elif space == "host":
+            if not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.shape == (M,) and out.flags.c_contiguous):
+                raise OspError(_lib.ERR_ARG, f"out must be a contiguous numpy array of {M} values of {np.dtype(self.dtype)}")
+            ret = out
+            buf = out if M else np.empty(1, self.dtype)
+            yp = C.c_void_p(buf.ctypes.data)
+        else:
+            yp, buf = self._vector_arg(out, M, self.dtype, "device", "out")
+            ret = out
+        sr = _lib.Semiring()
+        sr.add, sr.mul = _lib.MXV_ADD_OPS[add], _lib.MXM_MUL_OPS[mul]
+        stats = _lib.MxvStats()
+        _lib.check(_lib.lib().osp_csr_mxv(self._h, C.byref(sr), xp, yp, _lib.OSP_HOST if space == "host" else _lib.OSP_DEVICE,
+                                          C.byref(stats)))
+        del keep_x, buf
+        return ret, stats.as_dict()
+
     def apply_vectors(self, rows=None, row_op=None, cols=None, col_op=None, space="device"):
         """This CSR's pattern with every value ``col_op(row_op(c, rows[i]), cols[j])`` as a new CSR result on the device
         (``osp_csr_apply_vectors``).  Each op is ``"plus" "times" "minus" "div" "min" "max" "second"`` -- one IEEE operation
