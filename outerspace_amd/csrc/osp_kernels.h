@@ -94,6 +94,16 @@ __device__ __forceinline__ PartWords<T> load_part_words(const Part<T> *p) { retu
 template <class T>
 __device__ __forceinline__ void store_part_words(Part<T> *p, const PartWords<T> &r) { *reinterpret_cast<PartWords<T> *>(p) = r; }
 
+// ... and a record put together in registers
+template <class T>
+__device__ __forceinline__ PartWords<T> part_words(uint32_t col, T val) {
+    PartWords<T> r;
+    r.w[0] = col;
+    if constexpr (sizeof(T) == 8) { r.w[1] = (uint32_t)__double2loint((double)val); r.w[2] = (uint32_t)__double2hiint((double)val); }
+    else r.w[1] = __float_as_uint((float)val);
+    return r;
+}
+
 // Streaming store of one record (written once, read much later by another kernel): non-temporal, so that the staging
 // buffer does not push the operands out of L2.  OSP_NT_STAGE=0 compiles the plain store (A/B measurements: multiply
 // 58 -> 48 ms on the default workload together with the non-temporal stores of the merge output).  The same hint on
@@ -760,42 +770,54 @@ struct ExpandJobs {
         return (U + kExpandJob - 1) / kExpandJob;
     }
 };
-template <class T>
-__global__ __launch_bounds__(kExpandThreads) void expand_rows_kernel(
-    const uint32_t *__restrict__ rows, uint32_t nlong, const uint64_t *__restrict__ jobbase, const uint64_t *__restrict__ row_off, uint64_t base,
-    const uint32_t *__restrict__ rowfirst, const uint64_t *__restrict__ ct_off, const uint32_t *__restrict__ ct_bs, const uint32_t *__restrict__ perm,
-    const T *__restrict__ a_vals, const uint32_t *__restrict__ b_colidx, const T *__restrict__ b_vals, Part<T> *__restrict__ stage) {
-    const uint64_t job = blockIdx.x;
-    if (job >= jobbase[nlong]) return;
-    const unsigned lane = lane_id(), w = threadIdx.x >> 6;
-    const uint32_t h = (uint32_t)(upper_bound_dev(jobbase, 0, (uint64_t)nlong + 1, job) - 1);
-    const uint32_t row = rows[h];
-    const uint64_t rbeg = row_off[row], rend = row_off[row + 1];
-    constexpr uint32_t per = kExpandJob / (kExpandThreads / kWave);
-    const uint64_t p0 = rbeg + (job - jobbase[h]) * kExpandJob + (uint64_t)w * per;   // the wave's slice of the staging span
-    if (p0 >= rend) return;
-    const uint64_t p1 = min(p0 + per, rend);
-    const uint32_t c0 = rowfirst[row], c1 = rowfirst[row + 1];
-    // the chunk that holds product p0 (chunks without entries are never the answer: strictly ascending offsets decide)
-    uint32_t c = (uint32_t)(upper_bound_dev(ct_off, (uint64_t)c0, (uint64_t)c1, p0) - 1);
-    constexpr uint32_t kUnroll = 4;
-    for (; c < c1; c += kWave) {
+// The walk itself, shared with the stretch split (osp_split.h), which reads such rows straight from B: what a wave needs of the
+// chunk table, and the wave's place in the row.  A wave holds 64 chunks at a time -- lane q: chunk q's span, B row and A value
+// -- and hands out the products of BLOCKS of kWalkUnroll * 64 consecutive staging positions, lane l of step u holding position
+// q0 + u * 64 + l: a 6-step shuffle search names the chunk of every position, the loads of one block are in flight together.
+// (Positions are anchored at the block, not at the chunks, so that a caller can keep a block's products in registers by step.)
+template <class T> struct RowSrc {
+    const uint32_t *rowfirst; const uint64_t *ct_off; const uint32_t *ct_bs; const uint32_t *perm; const T *a_vals;
+    const uint32_t *b_colidx; const T *b_vals;   // (perm == nullptr: the values of A are in chunk order)
+};
+constexpr uint32_t kWalkUnroll = 4;
+template <class T, bool VALS> struct RowWalker {
+    const RowSrc<T> &src;
+    const unsigned lane;
+    uint32_t c, c1, nval;    // the 64 chunks held: [c, c + nval) of the row's [c0, c1)
+    uint64_t o0, o1;         // lane q: staging span of chunk c + q (lanes past the end: ~0)
+    uint32_t bsv;            // ... its first entry in B
+    T av;                    // ... its value of A
+    __device__ __forceinline__ void load_group() {
         const uint32_t cq = c + lane;
         const bool cv = cq < c1;
-        const uint64_t o0 = cv ? ct_off[cq] : ~0ull, o1 = cv ? ct_off[cq + 1] : ~0ull;
-        if (wave_bcast(o0, 0u) >= p1) break;   // (wave-uniform)
-        const uint32_t bsv = cv ? ct_bs[cq] : 0u;
-        const T av = cv ? (perm ? a_vals[perm[cq]] : a_vals[cq]) : T(0);   // (perm == nullptr: the values are in chunk order)
-        // the group's products inside the slice
-        const uint64_t g0 = max(wave_bcast(o0, 0u), p0);
-        const uint32_t nval = min((uint32_t)kWave, c1 - c);
-        const uint64_t g1 = min(wave_bcast(o1, nval - 1), p1);
-        for (uint64_t ib = g0; ib < g1; ib += kUnroll * kWave) {
-            uint32_t bc[kUnroll];
-            T bv[kUnroll], cav[kUnroll];
+        o0 = cv ? src.ct_off[cq] : ~0ull;
+        o1 = cv ? src.ct_off[cq + 1] : ~0ull;
+        bsv = cv ? src.ct_bs[cq] : 0u;
+        if constexpr (VALS) av = cv ? (src.perm ? src.a_vals[src.perm[cq]] : src.a_vals[cq]) : T(0);
+        nval = min((uint32_t)kWave, c1 - c);
+    }
+    __device__ __forceinline__ RowWalker(const RowSrc<T> &src_, unsigned lane_, uint32_t c0, uint32_t c1_) : src(src_), lane(lane_), c(c0), c1(c1_) {}
+    // the chunk that holds product p, at or after the chunks held (chunks without entries are never the answer: strictly
+    // ascending offsets decide); p lies inside the row's span
+    __device__ __forceinline__ void seek(uint64_t p) {
+        c = (uint32_t)(wave_upper_bound(src.ct_off, (uint64_t)c, (uint64_t)c1, p) - 1);
+        load_group();
+    }
+    // one block: positions [q0, q1), q1 <= q0 + U * 64, at or after the last seek / block; f(u, position, column, av * b_val)
+    // for every one of them, u a constant once the caller's loops are unrolled
+    template <int U, class F> __device__ __forceinline__ void block(uint64_t q0, uint64_t q1, F &&f) {
+        uint32_t bc[U];
+        T bv[U], cav[U];
 #pragma unroll
-            for (uint32_t u = 0; u < kUnroll; u++) {
-                const uint64_t i = ib + u * kWave + lane;
+        for (int u = 0; u < U; u++) { bc[u] = 0u; bv[u] = T(0); cav[u] = T(0); }
+        for (;;) {
+            const uint64_t gend = wave_bcast(o1, nval - 1);
+            const uint64_t gs = max(wave_bcast(o0, 0u), q0), ge = min(gend, q1);   // the held chunks' products inside the block
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const uint64_t r0 = q0 + (uint64_t)u * kWave;
+                if (!(r0 < ge && r0 + kWave > gs)) continue;   // (wave-uniform)
+                const uint64_t i = r0 + lane;
                 uint32_t lo = 0, hi = kWave;   // last lane whose chunk starts at or before i (lanes past the end hold ~0: never)
 #pragma unroll
                 for (int step = 0; step < 6; step++) {
@@ -805,18 +827,49 @@ __global__ __launch_bounds__(kExpandThreads) void expand_rows_kernel(
                 }
                 const uint64_t cst = (uint64_t)__shfl((long long)o0, (int)lo);
                 const uint32_t cbs = (uint32_t)__shfl((int)bsv, (int)lo);
-                cav[u] = __shfl(av, (int)lo);
-                const uint32_t b = i < g1 ? cbs + (uint32_t)(i - cst) : 0u;   // clamped, branch-free: the loads stay in flight
-                bc[u] = b_colidx[b];
-                bv[u] = b_vals[b];
+                T ca = T(0);
+                if constexpr (VALS) ca = __shfl(av, (int)lo);
+                if (i >= gs && i < ge) {   // predicated loads, no branch around a wait: the block's loads stay in flight
+                    const uint32_t b = cbs + (uint32_t)(i - cst);
+                    bc[u] = src.b_colidx[b];
+                    if constexpr (VALS) { bv[u] = src.b_vals[b]; cav[u] = ca; }
+                }
             }
+            if (gend >= q1 || c + kWave >= c1) break;
+            c += kWave;
+            load_group();
+        }
 #pragma unroll
-            for (uint32_t u = 0; u < kUnroll; u++) {
-                const uint64_t i = ib + u * kWave + lane;
-                if (i < g1) stream_store_part(&stage[i - base], bc[u], cav[u] * bv[u]);
-            }
+        for (int u = 0; u < U; u++) {
+            const uint64_t i = q0 + (uint64_t)u * kWave + lane;
+            if (i < q1) f(u, i, bc[u], cav[u] * bv[u]);
         }
     }
+};
+// a wave's slice [p0, p1) of the staging span of the row with chunks [c0, c1): f(position, column, av * b_val) for every product
+// (VALS == false: columns only, the value handed over is 0)
+template <class T, bool VALS, class F>
+__device__ __forceinline__ void walk_row_slice(const RowSrc<T> &src, unsigned lane, uint32_t c0, uint32_t c1, uint64_t p0, uint64_t p1, F &&f) {
+    RowWalker<T, VALS> wk(src, lane, c0, c1);
+    wk.seek(p0);
+    for (uint64_t q0 = p0; q0 < p1; q0 += kWalkUnroll * kWave)
+        wk.template block<(int)kWalkUnroll>(q0, min(q0 + kWalkUnroll * kWave, p1), [&](int, uint64_t i, uint32_t col, T val) { f(i, col, val); });
+}
+template <class T>
+__global__ __launch_bounds__(kExpandThreads) void expand_rows_kernel(
+    const uint32_t *__restrict__ rows, uint32_t nlong, const uint64_t *__restrict__ jobbase, const uint64_t *__restrict__ row_off, uint64_t base,
+    const RowSrc<T> src, Part<T> *__restrict__ stage) {
+    const uint64_t job = blockIdx.x;
+    if (job >= jobbase[nlong]) return;
+    const unsigned lane = lane_id(), w = threadIdx.x >> 6;
+    const uint32_t h = (uint32_t)(upper_bound_dev(jobbase, 0, (uint64_t)nlong + 1, job) - 1);
+    const uint32_t row = rows[h];
+    const uint64_t rbeg = row_off[row], rend = row_off[row + 1];
+    constexpr uint32_t per = kExpandJob / (kExpandThreads / kWave);
+    const uint64_t p0 = rbeg + (job - jobbase[h]) * kExpandJob + (uint64_t)w * per;   // the wave's slice of the staging span
+    if (p0 >= rend) return;
+    walk_row_slice<T, true>(src, lane, src.rowfirst[row], src.rowfirst[row + 1], p0, min(p0 + per, rend),
+                            [&](uint64_t i, uint32_t col, T val) { stream_store_part(&stage[i - base], col, val); });
 }
 
 // ---- tile planning -----------------------------------------------------------------------------

@@ -140,6 +140,8 @@ template <class T> struct PanelPlan {
     uint64_t xjobs_bound = 0, xpartials = 0;
     bool expand_ok = false;           // the panel's plainly staged long rows (if any) have jobs: the column-major multiply need not stage them
     bool may_write = false;           // some planned rows of the panel may have been written through cells (OSP_GATHER_OVER=0)
+    const DirectSrc *split_from_b = nullptr;   // set: the stretch rows are split straight from B (split_stretch_from_b), nobody stages them ...
+    bool split_beside = false;        // ... beside the next panel's plan: merge_panel finds them split
     explicit PanelPlan(Context *c) : sc(c) {}
 };
 
@@ -424,20 +426,59 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
         }
         dbg_sync(s, "plan of the hub rows");
     }
-    // With the short rows gathered, the long rows that are staged plainly -- split rows, stretch rows unless they are hub rows -- are
-    // expanded row by row (expand_rows_kernel) instead of column by column: their jobs.
+    // With the short rows gathered, the long rows that are staged plainly -- the split rows -- are expanded row by row
+    // (expand_rows_kernel) instead of column by column: their jobs.  The stretch rows, unless they are hub rows, are not staged
+    // at all: the stretch split forms their products from B itself (split_stretch_from_b).  OSP_SPLIT_FROM_B=0 stages them
+    // with the split rows and splits the records after the multiply, as until round 7 (A/B timing, tests).
+    // (The headline -- R-MAT-22 "mild" -- has no split rows: every long row is planned or a stretch row.  Its panels make no
+    // expand launch any more, and expand_launches / expand_partials are 0 there.)
     if (ds && ds->expand_rows) {
         pl.expand_ok = true;
         const bool hubs = pl.hub.cells != nullptr;
-        const uint64_t rows_x = pl.mode_rows[kModeSplitRow] + (hubs ? 0 : pl.mode_rows[kModeStretch]);
-        pl.xpartials = pl.mode_partials[kModeSplitRow] + (hubs ? 0 : pl.mode_partials[kModeStretch]);
+        const int from_b_env = getenv("OSP_SPLIT_FROM_B") ? atoi(getenv("OSP_SPLIT_FROM_B")) : 1;
+        if (!hubs && pl.nblocks != 0 && from_b_env != 0) pl.split_from_b = ds;
+        // (2: from B, but where the split of records runs -- in merge_panel, after the join.  Kept, like OSP_PLAN_OVERLAP=0, as the
+        // A/B switch of the placement alone: what the overlap gains depends on how full the next panel's plan keeps the CUs, which
+        // was measured on the headline only -- MEASUREMENTS 0n)
+        pl.split_beside = from_b_env != 2;
+        const bool stretch_x = !hubs && !pl.split_from_b;   // the stretch rows are expanded too
+        const uint64_t rows_x = pl.mode_rows[kModeSplitRow] + (stretch_x ? pl.mode_rows[kModeStretch] : 0);
+        pl.xpartials = pl.mode_partials[kModeSplitRow] + (stretch_x ? pl.mode_partials[kModeStretch] : 0);
+        if (getenv("OSP_VERBOSE") && pl.nblocks && !hubs)
+            fprintf(stderr, "[osp]   stretch rows: %llu rows, %llu partial products split %s\n", (unsigned long long)pl.mode_rows[kModeStretch],
+                    (unsigned long long)pl.mode_partials[kModeStretch], pl.split_from_b ? (pl.split_beside ? "from B" : "from B, after the join") : "from staged records");
         if (rows_x) {
             pl.xjobbase = sc.get<uint64_t>((uint64_t)nlong + 1);
-            device_exclusive_scan<ExpandJobs, uint64_t>(ExpandJobs{pl.p0.long_rows, row_off, pl.hmode, kModeSplitRow, hubs ? kModeSplitRow : kModeStretch},
+            device_exclusive_scan<ExpandJobs, uint64_t>(ExpandJobs{pl.p0.long_rows, row_off, pl.hmode, kModeSplitRow, stretch_x ? kModeStretch : kModeSplitRow},
                                                         nlong, pl.xjobbase, pl.hscan_tmp, s);
             pl.xjobs_bound = pl.xpartials / kExpandJob + rows_x;
         }
     }
+}
+
+// The stretch split of a panel whose stretch rows are read straight from B (PanelPlan::split_from_b): histogram, ONE scan, stable
+// scatter into the second buffer, segment offsets.  It reads B, the chunk table and the plan's own buffers and writes the second
+// buffer and the plan's tables -- neither the staging buffer nor the pool -- so it can be queued on the first stream right
+// after the fork of the second, where the expansion of these rows used to be, and then shares the CUs with the plan of the
+// next panel.  Nothing is allocated here: every buffer is the plan's.  Measured on the headline (MEASUREMENTS 0n): beside the
+// plan the scatter of the first panel takes 11 ms instead of 3.5 and that plan 1.5 ms longer, and the product is 1.1 ms
+// shorter than with the same split after the join (OSP_SPLIT_FROM_B=2: merge_panel calls this where the split of records runs).
+template <class T>
+static void split_stretch_from_b(Context *ctx, hipStream_t s, const PanelPlan<T> &pl, const uint64_t *row_off, uint64_t base, int colbits) {
+    const DirectSrc *ds = pl.split_from_b;
+    const TilePlan &p0 = pl.p0;
+    const uint32_t nlong = p0.nlong;
+    const uint32_t *perm = ds->av_in_order ? nullptr : ds->perm;
+    const RowSrc<float> cols{ds->rowfirst, ds->off, ds->bs, nullptr, nullptr, ds->b_colidx, nullptr};
+    const RowSrc<T> src{ds->rowfirst, ds->off, ds->bs, perm, (const T *)ds->a_vals, ds->b_colidx, (const T *)ds->b_vals};
+    split_count_kernel<true><<<(unsigned)pl.nblocks, kSplitThreads, 0, s>>>(p0.long_rows, nlong, pl.blkbase, pl.hbase, pl.hbits, pl.nstretch, row_off, base, colbits,
+                                                                          nullptr, 0u, pl.ghist, cols);
+    device_exclusive_scan<LoadU32, uint32_t>(LoadU32{pl.ghist}, pl.ncell, pl.ghist, pl.ghist_tmp, s);
+    OSP_WITH_RA(ctx, split_scatter_kernel<T, RA, true><<<(unsigned)pl.nblocks, kSplitThreads, 0, s>>>(
+                         p0.long_rows, nlong, pl.blkbase, pl.hbase, pl.hbits, pl.nstretch, row_off, base, colbits, nullptr, pl.ghist, pl.hoff, pl.qstage, src));
+    split_vrows_kernel<<<grid_for(pl.nvirt + 1, 256), 256, 0, s>>>(nlong, pl.vbase, pl.hbase, pl.nstretch, pl.hbits, pl.hmode, colbits, pl.ghist, pl.hoff, pl.nvirt,
+                                                                  pl.nh, pl.vrow_off, pl.vfirst, pl.vcol0, pl.vcol1);
+    OSP_HIP(hipGetLastError());
 }
 
 // One panel after the multiply: long rows that are not direct are split into column-range segments; the tiles of all
@@ -485,7 +526,9 @@ static void merge_panel(Context *ctx, Result *res, PhaseTimer &tm, const MergeIO
             res->info.split_partials += pl.mode_partials[kModeSplitRow];
             dbg_sync(s, "split: one-workgroup rows");
         }
-        if (nblocks && !pl.hub.cells) {  // longer rows: one workgroup per 4096-entry stretch, offsets from a device-wide scan
+        // (rows split from B: done beside the plan of the next panel, segment offsets included -- split_stretch_from_b)
+        if (pl.split_from_b && !pl.split_beside) split_stretch_from_b<T>(ctx, s, pl, io.row_off, base, colbits);
+        if (nblocks && !pl.hub.cells && !pl.split_from_b) {  // longer rows: one workgroup per 4096-entry stretch, offsets from a device-wide scan
             split_count_kernel<<<(unsigned)nblocks, kSplitThreads, 0, s>>>(p0.long_rows, nlong, blkbase, hbase, hbits, nstretch, io.row_off,
                                                                          base, colbits, (const char *)io.stage, (uint32_t)sizeof(Part<T>), ghist);
             device_exclusive_scan<LoadU32, uint32_t>(LoadU32{ghist}, ncell, ghist, ghist_tmp, s);
@@ -493,8 +536,9 @@ static void merge_panel(Context *ctx, Result *res, PhaseTimer &tm, const MergeIO
                                  p0.long_rows, nlong, blkbase, hbase, hbits, nstretch, io.row_off, base, colbits, io.stage, ghist, hoff, qstage));
         }
         dbg_sync(s, "split: stretch rows");
-        split_vrows_kernel<<<grid_for(nvirt + 1, 256), 256, 0, s>>>(nlong, vbase, hbase, nstretch, hbits, pl.hmode, colbits, ghist, hoff, nvirt, nh,
-                                                                   vrow_off, vfirst, pl.vcol0, pl.vcol1);
+        if (!pl.split_from_b)
+            split_vrows_kernel<<<grid_for(nvirt + 1, 256), 256, 0, s>>>(nlong, vbase, hbase, nstretch, hbits, pl.hmode, colbits, ghist, hoff, nvirt, nh,
+                                                                       vrow_off, vfirst, pl.vcol0, pl.vcol1);
         OSP_HIP(hipGetLastError());
         dbg_sync(s, "split: segment offsets");
         // ---- tiles over the segments; a tile never spans two long rows ----
@@ -617,8 +661,8 @@ static void merge_panel(Context *ctx, Result *res, PhaseTimer &tm, const MergeIO
                                                                            nullptr, 0u, nullptr, nullptr, nullptr, desc, nullptr, nullptr, io.rowfirst0);
     }
     uint64_t *tile_status = sc.get<uint64_t>(ntot);
-    // ticket counters: one word (the kernel also takes several plus an arrival counter -- osp_kernels.h, take_ticket; measured in
-    // round 3: no gain while the look-back is on -- the chain and the hash count bound the kernel, not the word; the switch is gone)
+    // ticket counters: one word (the kernel can also take several plus an arrival counter -- osp_kernels.h, take_ticket; measured in
+    // round 3: no gain while the look-back is on -- the chain and the hash count bound the kernel, not the word -- so nothing asks for more)
     const uint32_t nshards = 1u;
     uint32_t *ticket = sc.get<uint32_t>((uint64_t)(nshards + 1) * kTicketStride);
     zero_async(s, {{tile_status, (uint64_t)ntot * sizeof(uint64_t)}, {ticket, (uint64_t)(nshards + 1) * kTicketStride * sizeof(uint32_t)}});
@@ -889,12 +933,18 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
         bool column_major = count != 0 && !(sr && plan.p0.nlong == 0), desc_only = false;   // (short rows gathered, no long row: nothing is staged)
         if (count && plan.xjobbase && plan.xjobs_bound) {
             tm.begin(PH_EXPAND_K);
-            expand_rows_kernel<T><<<(unsigned)plan.xjobs_bound, kExpandThreads, 0, s>>>(plan.p0.long_rows, plan.p0.nlong, plan.xjobbase, d_row_off, base, ds->rowfirst,
-                                                                                     ds->off, ds->bs, ds->av_in_order ? nullptr : ds->perm, (const T *)ds->a_vals,
-                                                                                     ds->b_colidx, (const T *)ds->b_vals, stage);
+            const RowSrc<T> src{ds->rowfirst, ds->off, ds->bs, ds->av_in_order ? nullptr : ds->perm, (const T *)ds->a_vals, ds->b_colidx, (const T *)ds->b_vals};
+            expand_rows_kernel<T><<<(unsigned)plan.xjobs_bound, kExpandThreads, 0, s>>>(plan.p0.long_rows, plan.p0.nlong, plan.xjobbase, d_row_off, base, src, stage);
             tm.end(PH_EXPAND_K);
             res->info.expand_launches++;
             res->info.expand_partials += plan.xpartials;
+        }
+        // (inside the PH_MUL bracket, like the expansion it replaces: ms_multiply counts the stretch split of such panels --
+        // stretched by the plan it shares the CUs with: 16 ms of the headline's three panels against 2 before -- and ms_merge
+        // no longer does; no kernel phase of its own, as the split of records has none)
+        if (count && plan.split_from_b && plan.split_beside) {
+            split_stretch_from_b<T>(ctx, s, plan, d_row_off, base, colbits);
+            dbg_sync(s, "split: stretch rows, from B");
         }
         if (count && plan.expand_ok) {
             // what is left for the column-major multiply: rows written through cells -- hub rows, direct rows with an over-long range

@@ -12,7 +12,11 @@
 //   split    one workgroup moves the row with ONE stable segmented counting-sort pass on the top b
 //            bits of the column (split_row_kernel; rows without a chunk table: the parts-merging
 //            entry points, or OSP_DIRECT=0);
-//   stretch  rows too long for one workgroup: one workgroup per stretch, device-wide scan.
+//   stretch  rows too long for one workgroup: one workgroup per stretch, device-wide scan.  Where the symbolic phase left a
+//            chunk table, these rows are not staged first: count and scatter walk B themselves (FROM_B: the row walker of
+//            expand_rows_kernel, osp_kernels.h) and form the products they move, so such a record is written once -- into
+//            its segment -- like every planned row's.  Callers without a chunk table (the parts-merging entry points,
+//            OSP_DIRECT=0, the multi-GPU final merge) split the staged records.
 // (Reference for the operation being implemented: deduplicateCOO, SimSpGEMM.cpp:519-535.  The
 // reference simply sorts everything; there is no counterpart of this file.)
 #pragma once
@@ -175,18 +179,30 @@ __device__ __forceinline__ SplitJob split_job(const uint32_t *rows, uint32_t nhe
 }
 
 // histogram of one stretch over the row's segments -> ghist[hbase + seg * nst + st]
+// FROM_B: the columns come from B's own column array (4 bytes per product instead of a 12-byte record's first word, and
+// no staged copy needed): the job's four waves walk a quarter of its staging span each
+template <bool FROM_B = false>
 __global__ __launch_bounds__(kSplitThreads) void split_count_kernel(
     const uint32_t *rows, uint32_t nheavy, const uint64_t *blkbase, const uint64_t *hbase, const uint8_t *hbits,
     const uint32_t *nstretch, const uint64_t *row_off, uint64_t base, int colbits, const char *stage, uint32_t rec_bytes,
-    uint32_t *ghist) {
+    uint32_t *ghist, const RowSrc<float> src = RowSrc<float>{}) {
     __shared__ uint32_t hist[1 << kSplitMaxBits];
     const SplitJob j = split_job(rows, nheavy, blkbase, hbase, hbits, nstretch, row_off, base);
     const uint32_t nseg = 1u << j.b;
     for (uint32_t d = threadIdx.x; d < nseg; d += kSplitThreads) hist[d] = 0;
     __syncthreads();
     const int sh = colbits - (int)j.b;
-    for (uint64_t i = j.beg + threadIdx.x; i < j.end; i += kSplitThreads)
-        atomicAdd(&hist[*(const uint32_t *)(stage + i * rec_bytes) >> sh], 1u);
+    if constexpr (FROM_B) {
+        constexpr uint32_t per = kSplitJob / (kSplitThreads / kWave);
+        const uint32_t row = rows[j.h];
+        const uint64_t p0 = j.beg + (uint64_t)(threadIdx.x >> 6) * per, p1 = min(p0 + per, j.end);   // (wave-uniform)
+        if (p0 < p1)
+            walk_row_slice<float, false>(src, lane_id(), src.rowfirst[row], src.rowfirst[row + 1], base + p0, base + p1,
+                                         [&](uint64_t, uint32_t col, float) { atomicAdd(&hist[col >> sh], 1u); });
+    } else {
+        for (uint64_t i = j.beg + threadIdx.x; i < j.end; i += kSplitThreads)
+            atomicAdd(&hist[*(const uint32_t *)(stage + i * rec_bytes) >> sh], 1u);
+    }
     __syncthreads();
     for (uint32_t d = threadIdx.x; d < nseg; d += kSplitThreads) ghist[j.hbase + (uint64_t)d * j.nst + j.st] = hist[d];
 }
@@ -210,11 +226,13 @@ __device__ __forceinline__ void wave_match_bits(unsigned digit, int bits, bool v
 // (Measured and not kept: the per-segment bookkeeping through 8- and 16-byte LDS accesses, four segments per thread -- a
 // quarter of its LDS instructions: no change at 512 or 2048 segments per row (500.4 against 500.5 ms, 4.02 against 4.03 s).
 // The kernel waits for its scattered 24..96-byte writes, not for LDS.)
-template <class T, bool RA>
+// FROM_B: the round's records are not loaded from the staging buffer but formed from B (column, av * b_val) by the row
+// walker, for exactly the positions the loads would read -- the same ranks, the same places in the second buffer.
+template <class T, bool RA, bool FROM_B = false>
 __global__ __launch_bounds__(kSplitThreads) void split_scatter_kernel(
     const uint32_t *rows, uint32_t nheavy, const uint64_t *blkbase, const uint64_t *hbase, const uint8_t *hbits,
     const uint32_t *nstretch, const uint64_t *row_off, uint64_t base, int colbits, const Part<T> *stage,
-    const uint32_t *goffs, const uint64_t *hoff, Part<T> *qstage) {
+    const uint32_t *goffs, const uint64_t *hoff, Part<T> *qstage, const RowSrc<T> src = RowSrc<T>{}) {
     constexpr int NW = kSplitThreads / kWave;
     constexpr int ITERS = kSplitStretch / kSplitThreads;  // 16 wave iterations per wave span
     __shared__ alignas(8) uint16_t cnt[NW][1 << kSplitMaxBits];  // (pairs of counters are also addressed as 32-bit words)
@@ -230,6 +248,8 @@ __global__ __launch_bounds__(kSplitThreads) void split_scatter_kernel(
     }
     __syncthreads();
     const int sh = colbits - (int)j.b;
+    const uint32_t wrow = FROM_B ? rows[j.h] : 0u;
+    RowWalker<T, true> walker(src, lane, FROM_B ? src.rowfirst[wrow] : 0u, FROM_B ? src.rowfirst[wrow + 1] : 0u);   // (FROM_B only)
     // the job's entries in rounds of kSplitStretch; boff[d] runs along (it always points behind what the earlier rounds
     // put into segment d)
     for (uint64_t sb = j.beg; sb < j.end; sb += kSplitStretch) {
@@ -238,10 +258,27 @@ __global__ __launch_bounds__(kSplitThreads) void split_scatter_kernel(
         const uint64_t wbeg = sb + (uint64_t)w * (kSplitStretch / NW);
         uint32_t rk[ITERS];
         PartWords<T> rec[ITERS];  // raw records: all loads in flight together
+        if constexpr (FROM_B) {
+            static_assert(ITERS % (int)kWalkUnroll == 0, "a wave span is whole blocks of the row walker");
 #pragma unroll
-        for (int it = 0; it < ITERS; it++) {
-            const uint64_t i = wbeg + (uint64_t)it * kWave + lane;
-            rec[it] = load_part_words(&stage[i < se ? i : sb]);  // branch-free: lanes past the end re-read the first record
+            for (int it = 0; it < ITERS; it++) rec[it] = PartWords<T>{};   // (lanes past the end: column 0, never ranked or stored)
+            if (wbeg < se) {   // (wave-uniform)
+                const uint64_t wend = min(wbeg + (uint64_t)(kSplitStretch / NW), se);
+                walker.seek(base + wbeg);
+#pragma unroll
+                for (int blk = 0; blk < ITERS / (int)kWalkUnroll; blk++) {
+                    const uint64_t q0 = wbeg + (uint64_t)blk * kWalkUnroll * kWave;
+                    if (q0 < wend)
+                        walker.template block<(int)kWalkUnroll>(base + q0, base + min(q0 + kWalkUnroll * kWave, wend),
+                                                                [&](int u, uint64_t, uint32_t col, T val) { rec[blk * (int)kWalkUnroll + u] = part_words(col, val); });
+                }
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < ITERS; it++) {
+                const uint64_t i = wbeg + (uint64_t)it * kWave + lane;
+                rec[it] = load_part_words(&stage[i < se ? i : sb]);  // branch-free: lanes past the end re-read the first record
+            }
         }
 #pragma unroll
         for (int it = 0; it < ITERS; it++) {
