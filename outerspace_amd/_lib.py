@@ -205,6 +205,21 @@ class TransposeStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class Extract(C.Structure):
+    """osp_extract_t"""
+    _fields_ = [("rows", C.c_void_p), ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("n_cols", C.c_uint64), ("space", C.c_int32),
+                ("reserved", C.c_uint32 * 7)]
+
+
+class ExtractStats(C.Structure):
+    """osp_extract_stats_t"""
+    _fields_ = [("nnz_in", C.c_uint64), ("nnz_gathered", C.c_uint64), ("nnz_out", C.c_uint64), ("ms_total", C.c_float),
+                ("launches", C.c_uint32), ("readbacks", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -272,6 +287,9 @@ TRANSPOSE_EXPORTS = ["osp_csr_transpose"]
 
 # every symbol include/outerspace_spgemm_mxv.h declares
 MXV_EXPORTS = ["osp_csr_mxv"]
+
+# every symbol include/outerspace_spgemm_extract.h declares
+EXTRACT_EXPORTS = ["osp_csr_extract"]
 
 _lib = None
 
@@ -360,6 +378,7 @@ def lib():
     L.osp_csr_mxm.argtypes = [vp, vp, C.POINTER(Semiring), C.POINTER(vp), C.POINTER(MxmStats)]
     L.osp_csr_transpose.argtypes = [vp, C.POINTER(Transpose), C.POINTER(vp), C.POINTER(TransposeStats)]
     L.osp_csr_mxv.argtypes = [vp, C.POINTER(Semiring), vp, vp, i32, C.POINTER(MxvStats)]
+    L.osp_csr_extract.argtypes = [vp, C.POINTER(Extract), C.POINTER(vp), C.POINTER(ExtractStats)]
     _lib = L
     return L
 

@@ -30,6 +30,7 @@
 #include "../../include/outerspace_spgemm_mxm.h"
 #include "../../include/outerspace_spgemm_transpose.h"
 #include "../../include/outerspace_spgemm_mxv.h"
+#include "../../include/outerspace_spgemm_extract.h"
 #include "osp_internal.h"
 #include "osp_kernels.h"
 #include "osp_split.h"
@@ -45,6 +46,7 @@
 #include "osp_mxm.h"
 #include "osp_transpose.h"
 #include "osp_mxv.h"
+#include "osp_extract.h"
 
 namespace osp {
 
@@ -1894,6 +1896,122 @@ static void select_vertices_impl(Context *ctx, const Result *in, Result *res, co
                 (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)c.nnz, c.launches, st->ms_total);
 }
 
+// ---- the submatrix in(rows, cols), renumbered (osp_extract.h) ----
+static void check_extract_lists(uint32_t bad) {
+    if (bad & kExtractBadRow) throw Error(OSP_ERR_ARG, "extract: a row index is not below the rows of in");
+    if (bad & kExtractBadCol) throw Error(OSP_ERR_ARG, "extract: the columns are not strictly ascending and below the columns of in");
+}
+
+template <class T>
+static void extract_impl(Context *ctx, const Result *in, Result *res, const osp_extract_t &ex, osp_extract_stats_t *st) {
+    typedef ValueBits<T> V;
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint64_t M = in->info.M, N = in->info.N, nnz_in = in->info.nnz_c;
+    const bool has_rows = ex.rows != nullptr, has_cols = ex.cols != nullptr;
+    const uint64_t m = has_rows ? ex.n_rows : M, n = has_cols ? ex.n_cols : N;
+    const osp_memspace_t space = (osp_memspace_t)ex.space;
+    res->info = in->info;
+    res->info.M = m; res->info.N = n;
+    res->info.row_begin = 0; res->info.row_end = m;
+    uint64_t nnz_g = has_rows ? 0 : nnz_in, nnz_out = 0;
+    uint32_t launches = 0, readbacks = 0;
+    if (nnz_in == 0 || m == 0 || n == 0) {
+        if (has_rows) nnz_g = 0;
+        empty_result<T>(res, m, s);
+    } else if (!has_rows && !has_cols) {
+        copy_csr<T>(in, res, s);
+        nnz_out = nnz_in;
+    } else {
+        // (pool buffers are recycled, and OSP_POISON fills them: the error word and the bitmap are zeroed on every call)
+        const uint64_t nwc = (N + 63) / 64;
+        uint32_t *err = sc.get<uint32_t>(1);
+        uint64_t *colbits = has_cols ? sc.get<uint64_t>(nwc) : nullptr;
+        uint32_t *cpos = has_cols ? sc.get<uint32_t>(nwc + 1) : nullptr;   // (ranks of columns: below n <= 2^32 - 1)
+        zero_async(s, {{err, sizeof(uint32_t)}, {colbits, has_cols ? nwc * sizeof(uint64_t) : 0}});
+        launches++;
+        const uint32_t *rows = nullptr;
+        uint32_t *dense = nullptr;
+        uint64_t *g = nullptr;   // the gathered row pointer; without a column list it IS out's row pointer
+        if (has_rows) {
+            rows = to_device(sc, ex.rows, m, space, s);
+            uint32_t *len = sc.get<uint32_t>(m);
+            uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(m));
+            if (has_cols) g = sc.get<uint64_t>(m + 1);
+            else { alloc_rowptr(res, m); g = (uint64_t *)res->rowptr; }
+            extract_len_kernel<<<grid_for(m, 256), 256, 0, s>>>(rows, m, in->rowptr, M, len, err);
+            launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{len}, m, g, tmp, s);
+        }
+        if (has_cols) {
+            const uint32_t *cols = to_device(sc, ex.cols, n, space, s);
+            uint32_t *tmp = sc.get<uint32_t>(scan_scratch_entries(nwc));
+            if (env_is("OSP_EXTRACT_DENSE_MAP", "1")) dense = sc.get<uint32_t>(N);
+            extract_colmap_kernel<<<grid_for(n, 256), 256, 0, s>>>(cols, n, N, (unsigned long long *)colbits, dense, err);
+            launches += 1 + device_exclusive_scan<LoadPopc64, uint32_t>(LoadPopc64{colbits}, nwc, cpos, tmp, s);
+        }
+        uint32_t bad = 0;
+        if (has_rows) {   // the first read-back: nothing an index decides is launched before the lists are known to be good
+            Gather first(s);
+            first.add(&bad, (const uint32_t *)err);
+            first.add(&nnz_g, (const uint64_t *)g + m);
+            first.wait();
+            readbacks++;
+            check_extract_lists(bad);
+            if (nnz_g >= 0xffffffffull) throw Error(OSP_ERR_ARG, "extract: gathered rows of >= 2^32 - 1 non-zeros are not supported");
+        }
+        const int64_t *gp = has_rows ? (const int64_t *)g : in->rowptr;
+        const unsigned nchunks = grid_for(nnz_g, (unsigned)kCompactChunk);
+        if (nnz_g == 0) {
+            if (has_cols) empty_result<T>(res, m, s);
+            else alloc_entries<T>(res, 0);   // (g, all zeros, is the row pointer)
+        } else if (!has_cols) {
+            nnz_out = nnz_g;
+            alloc_entries<T>(res, nnz_out);
+            extract_write_kernel<V, true, false><<<nchunks, kCompactThreads, 0, s>>>(gp, rows, in->rowptr, in->colidx, (const V *)in->vals, m, nnz_g, nullptr,
+                                                                                      nullptr, nullptr, nullptr, nullptr, res->colidx, (V *)res->vals);
+            launches++;
+        } else {
+            alloc_rowptr(res, m);
+            // (without a row list the verdicts need no index of the caller's as an address -- a bad column set no bit -- so the
+            // error word travels with the one read-back of the scan)
+            std::function<void(Gather &)> more;
+            if (!has_rows) more = [&](Gather &ga) { ga.add(&bad, (const uint32_t *)err); };
+            const BitScan b = flag_and_scan(sc, nnz_g, s, [&](unsigned grid, uint64_t *bits) {
+                const auto flag = has_rows ? extract_flag_kernel<true> : extract_flag_kernel<false>;
+                flag<<<grid, kCompactThreads, 0, s>>>(gp, rows, in->rowptr, in->colidx, m, nnz_g, colbits, bits);
+            }, more);
+            readbacks++;
+            check_extract_lists(bad);
+            launches += b.launches;
+            nnz_out = b.count;
+            alloc_entries<T>(res, nnz_out);
+            compact_rowptr_kernel<<<grid_for(m + 1, 256), 256, 0, s>>>(gp, m, b.bits, b.pos, res->rowptr);
+            launches++;
+            if (nnz_out) {
+                const auto write = has_rows ? extract_write_kernel<V, true, true> : extract_write_kernel<V, false, true>;
+                write<<<nchunks, kCompactThreads, 0, s>>>(gp, rows, in->rowptr, in->colidx, (const V *)in->vals, m, nnz_g, b.bits, b.pos, colbits, cpos,
+                                                          dense, res->colidx, (V *)res->vals);
+                launches++;
+            }
+        }
+    }
+    finish_csr(res, ev, nnz_out, s);
+    *st = osp_extract_stats_t{};
+    st->nnz_in = nnz_in;
+    st->nnz_gathered = nnz_g;
+    st->nnz_out = nnz_out;
+    st->ms_total = res->info.ms_total;
+    st->launches = launches;
+    st->readbacks = readbacks;
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] extract rows=%d cols=%d %llu x %llu of %llu x %llu nnz %llu -> %llu -> %llu launches=%u readbacks=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
+                has_rows, has_cols, (unsigned long long)m, (unsigned long long)n, (unsigned long long)M, (unsigned long long)N,
+                (unsigned long long)nnz_in, (unsigned long long)nnz_g, (unsigned long long)nnz_out, launches, readbacks, st->ms_total,
+                (unsigned long long)ctx->malloc_calls);
+}
+
 static void destroy_result(Result *r) {
     if (!r) return;
     if (r->ctx) {
@@ -2310,6 +2428,25 @@ int osp_csr_select_vertices(osp_result_t in_, const uint8_t *keep_rows, const ui
         osp_vector_stats_t st{};
         const int rc = new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {
             select_vertices_impl<decltype(tag)>(in->ctx, in, res, keep_rows, keep_cols, space, &st);
+        });
+        if (stats) *stats = st;
+        return rc;
+    });
+}
+
+int osp_csr_extract(osp_result_t in_, const osp_extract_t *ex, osp_result_t *out, osp_extract_stats_t *stats) {
+    Result *in = (Result *)in_;
+    if (!in || !ex || !out) return fail(OSP_ERR_ARG, "null argument");
+    if (in->partials) return fail(OSP_ERR_ARG, "a result of osp_spgemm_partials holds records, not a CSR");
+    return guard([&] {
+        check_space(ex->space);
+        for (uint32_t w : ex->reserved)
+            if (w) throw Error(OSP_ERR_ARG, "extract: reserved words must be 0");
+        check_dims(ex->rows ? ex->n_rows : 0, 0, ex->cols ? ex->n_cols : 0);
+        if (in->info.nnz_c >= 0xffffffffull) throw Error(OSP_ERR_ARG, "extract: results with >= 2^32 - 1 non-zeros are not supported");
+        osp_extract_stats_t st{};
+        const int rc = new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {
+            extract_impl<decltype(tag)>(in->ctx, in, res, *ex, &st);
         });
         if (stats) *stats = st;
         return rc;

@@ -9,7 +9,8 @@ clustering coefficient on ``osp_csr_reduce`` / ``osp_csr_apply_vectors`` / ``osp
 ``osp_csr_mxm`` (``shortest_paths``, ``widest_paths``, ``min_plus_closure``), and the first functions on a DIRECTED graph,
 which need the transpose of a result ``osp_csr_transpose`` (``strongly_connected``, ``cocitation``,
 ``bibliographic_coupling``), and global PageRank and connected components on the product of a result with a dense vector
-``osp_csr_mxv`` (``pagerank``, ``connected_components``, at the end).
+``osp_csr_mxv`` (``pagerank``, ``connected_components``), and subgraphs as matrices of their own on the submatrix of a result
+``osp_csr_extract`` (``induced_subgraph``, ``ego_network``, ``largest_component``, at the end).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -1323,3 +1324,82 @@ def connected_components(rows, cols, n=None, *, dtype=np.float64, ctx=None):
         A.close()
     info["components"] = int((labels == np.arange(n)).sum())
     return labels, info
+
+
+# ---- the submatrix of a result (osp_csr_extract): induced subgraphs as matrices of their own ---------------------------------------
+def _check_vertices(vertices, n):
+    vs = np.atleast_1d(np.asarray(vertices.cpu() if torch.is_tensor(vertices) else vertices)).astype(np.int64).ravel()
+    if vs.size and (vs.min() < 0 or vs.max() >= n):
+        raise ValueError(f"vertices must lie in [0, {n})")
+    if np.unique(vs).size != vs.size:
+        raise ValueError("vertices must be distinct")
+    return vs
+
+
+def induced_subgraph(rows, cols, n=None, vertices=(), *, directed=False, dtype=np.float64, ctx=None):
+    """The subgraph that ``vertices`` induce in the graph with edges (rows[e], cols[e]) on vertices [0, n), renumbered by
+    position in ``vertices``: vertex ``vertices[i]`` is vertex i of the subgraph.  ``vertices`` must be distinct (a duplicate
+    is a ValueError) and may come in any order.  The pattern is built as ``pagerank`` builds it (``directed=False``: a simple
+    graph, any direction, self loops dropped; ``directed=True``: self loops kept) and cut out on the GPU by
+    ``A.extract(vertices, vertices)``: a small matrix of its own, not ``select_vertices``' empty rows and columns.
+
+    Returns (u, v, info): the subgraph's edges in the new numbering, int64, ascending by (u, v) -- once each with u < v for
+    an undirected graph, every edge u -> v for a directed one; info = the extract's stats (nnz_in, nnz_gathered, nnz_out,
+    ms_total, launches, readbacks, composed) and n (the number of vertices of the subgraph)."""
+    ctx, device, dtype, n, A = _pattern_result(rows, cols, n, directed, dtype, ctx)
+    try:
+        vs = _check_vertices(vertices, n)
+        info = dict(_S._lib.ExtractStats().as_dict(), composed=False, n=int(vs.size))
+        none = np.zeros(0, np.int64)
+        if A is None:
+            return none, none.copy(), info
+        sub, st = A.extract(vs, vs, space="host")
+        info.update(st)
+        try:
+            if not directed:
+                u, v, _ = _upper_entries(sub)
+                return u, v, info
+            rowptr, colidx, _ = sub.to_host()
+            return np.repeat(np.arange(sub.shape[0], dtype=np.int64), np.diff(rowptr)), colidx.astype(np.int64), info
+        finally:
+            sub.close()
+    finally:
+        if A is not None:
+            A.close()
+
+
+def ego_network(rows, cols, n=None, center=0, radius=1, *, ctx=None):
+    """The ego network of ``center`` in the undirected graph with edges (rows[e], cols[e]) on vertices [0, n)
+    (``networkx.ego_graph``): the vertices within ``radius`` steps of ``center`` -- from ``bfs_levels(...,
+    max_levels=radius)`` -- ascending, and the subgraph they induce, by ``induced_subgraph``.
+
+    Returns (vertices int64, u, v, info): the edges in the numbering of ``vertices`` (vertex ``vertices[i]`` is i), u < v,
+    ascending; info = ``induced_subgraph``'s and levels (the deepest level the search reached)."""
+    radius = int(radius)
+    if radius < 0:
+        raise ValueError("radius must be at least 0")
+    level, _, binfo = bfs_levels(rows, cols, n, [center], max_levels=radius, ctx=ctx)
+    vertices = np.flatnonzero(level[0] >= 0).astype(np.int64)
+    u, v, info = induced_subgraph(rows, cols, level.shape[1], vertices, ctx=ctx)
+    info["levels"] = binfo["levels"]
+    return vertices, u, v, info
+
+
+def largest_component(rows, cols, n=None, *, dtype=np.float64, ctx=None):
+    """The largest connected component of the undirected graph with edges (rows[e], cols[e]) on vertices [0, n) as a graph
+    of its own: the labels of ``connected_components``, the most frequent label (the smallest on a tie) counted with torch,
+    and the subgraph its vertices induce, by ``induced_subgraph``.
+
+    Returns (vertices int64 ascending, u, v, info): the edges in the numbering of ``vertices``, u < v, ascending; info =
+    ``induced_subgraph``'s, components and rounds (of ``connected_components``)."""
+    labels, cinfo = connected_components(rows, cols, n, dtype=dtype, ctx=ctx)
+    nn = len(labels)
+    if nn:
+        counts = torch.bincount(torch.as_tensor(labels))
+        best = int((counts == counts.max()).nonzero()[0].item())   # (the first of the most frequent: the smallest label)
+        vertices = np.flatnonzero(labels == best).astype(np.int64)
+    else:
+        vertices = np.zeros(0, np.int64)
+    u, v, info = induced_subgraph(rows, cols, nn, vertices, dtype=dtype, ctx=ctx)
+    info["components"], info["rounds"] = cinfo["components"], cinfo["rounds"]
+    return vertices, u, v, info

@@ -390,6 +390,92 @@ class CsrResult:
         del keep_r, keep_c
         return CsrResult(self._ctx, h), stats.as_dict()
 
+    @staticmethod
+    def _index_arg(v, space, what):
+        """An index list of ``extract``: (pointer, count, keep-alive, ascending).  ``space="host"``: an array-like of integers
+        in [0, 2^32); ``space="device"``: a torch tensor of 4-byte integers (the caller has synchronised its stream) or an
+        ``(address, count)`` pair.  ``ascending`` says whether the list is strictly ascending -- numpy on the host, one torch
+        comparison on the device -- and is None for a bare address, which nothing here can read."""
+        if space not in ("device", "host"):
+            raise ValueError('space must be "device" or "host"')
+        if v is None:
+            return None, 0, None, True
+        if space == "host":
+            a = np.atleast_1d(np.asarray(v))
+            if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+                raise OspError(_lib.ERR_ARG, f"{what} must be a one-dimensional list of integers")
+            a = a.astype(np.int64) if a.size else np.zeros(0, np.int64)
+            if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+                raise OspError(_lib.ERR_ARG, f"{what} holds an index outside [0, 2^32)")
+            ascending = bool(np.all(a[1:] > a[:-1]))
+            a = np.ascontiguousarray(a, np.uint32)
+            keep = a if a.size else np.zeros(1, np.uint32)   # (an empty list: never a null pointer, NULL means "all")
+            return C.c_void_p(keep.ctypes.data), int(a.size), keep, ascending
+        if hasattr(v, "data_ptr"):
+            if v.dim() != 1 or v.element_size() != 4 or v.is_floating_point() or not v.is_contiguous():
+                raise OspError(_lib.ERR_ARG, f"{what} must be a contiguous one-dimensional tensor of 4-byte integers")
+            addr, n = v.data_ptr(), int(v.numel())
+        else:
+            addr, n = int(v[0]), int(v[1])
+        if n == 0:   # (nothing is read: any non-null pointer says "an empty list")
+            keep = np.zeros(1, np.uint32)
+            return C.c_void_p(keep.ctypes.data), 0, keep, True
+        if not hasattr(v, "data_ptr"):
+            return C.c_void_p(addr), n, None, None
+        w = v.long() & 0xffffffff   # (an int32 tensor holds a uint32 list's bits)
+        return C.c_void_p(addr), n, v, bool((w[1:] > w[:-1]).all().item())
+
+    def extract(self, rows=None, cols=None, space="device"):
+        """The submatrix ``out[i, k] = self[rows[i], cols[k]]``, renumbered, as a new ``len(rows) x len(cols)`` CSR result
+        on the device (``osp_csr_extract``); a list given as None takes every row / column.  ``rows``: any order, duplicates
+        allowed.  ``cols``: None or strictly ascending lists go to the library directly; any other list (a permutation,
+        duplicates) is computed by composition -- ``T = self.transpose(); Y = T.extract(rows=cols); Z = Y.transpose();
+        out = Z.extract(rows=rows)`` (with ``rows`` None, Z itself) -- a row gather keeps the order inside a row and the
+        transpose sorts stably, so the result has ascending columns, the copies of a repeated column next to each other in
+        list order.  Lists are torch
+        tensors of 4-byte integers or ``(device address, count)`` pairs (``space="device"``: the caller has synchronised; a
+        bare address is taken as ascending) or array-likes (``space="host"``).  An index beyond its dimension is
+        ``OspError(ERR_ARG)`` on either path.  Values keep their bits.  Returns (result, stats dict): nnz_in, nnz_gathered,
+        nnz_out, ms_total, launches, readbacks, composed (the composed path: the sums over its calls)."""
+        rp, nr, keep_r, _ = self._index_arg(rows, space, "rows")
+        cp, nc, keep_c, ascending = self._index_arg(cols, space, "cols")
+        if ascending is False:
+            made = []
+            try:
+                T, st_t = self.transpose()
+                made.append(T)
+                Y, st_y = T.extract(rows=cols, space=space)
+                made.append(Y)
+                Z, st_z = Y.transpose()
+                parts = [st_t, st_y, st_z]
+                if rows is None:   # (every row: Z is the result, a fourth call would only copy it)
+                    out = Z
+                else:
+                    made.append(Z)
+                    out, st = Z.extract(rows=rows, space=space)
+                    parts.append(st)
+            finally:
+                for t in made:
+                    t.close()
+            stats = {"nnz_in": self.nnz, "nnz_gathered": out.nnz if rows is None else st["nnz_gathered"], "nnz_out": out.nnz,
+                     "ms_total": sum(p["ms_total"] for p in parts), "launches": sum(p["launches"] for p in parts),
+                     "readbacks": st_y["readbacks"] + (0 if rows is None else st["readbacks"]), "composed": True}
+            return out, stats
+        ex = _lib.Extract()
+        ex.rows, ex.n_rows, ex.cols, ex.n_cols = rp, nr, cp, nc
+        ex.space = _lib.OSP_HOST if space == "host" else _lib.OSP_DEVICE
+        stats = _lib.ExtractStats()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_csr_extract(self._h, C.byref(ex), C.byref(h), C.byref(stats)))
+        del keep_r, keep_c
+        return CsrResult(self._ctx, h), dict(stats.as_dict(), composed=False)
+
+    def permute(self, perm, space="device"):
+        """``extract(perm, perm)`` on a square result: vertex ``perm[i]`` becomes vertex i."""
+        if self.shape[0] != self.shape[1]:
+            raise OspError(_lib.ERR_DIM, f"permute needs a square result (got {self.shape[0]} x {self.shape[1]})")
+        return self.extract(perm, perm, space)
+
     def coo_rows_into(self, rows_device_ptr):
         """Row index of every entry into caller-owned DEVICE memory (nnz u32 values): with ``device_ptrs()[1:]`` the COO
         form ``Context.spgemm_coo_device`` takes (``osp_result_coo_rows``)."""
