@@ -220,6 +220,24 @@ class ExtractStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+DUP_OPS = {"error": 0, "plus": 1, "min": 2, "max": 3, "first": 4, "last": 5, "count": 6}  # osp_dup_op_t
+
+
+class Build(C.Structure):
+    """osp_build_t"""
+    _fields_ = [("M", C.c_uint64), ("N", C.c_uint64), ("nnz", C.c_uint64), ("rows", C.c_void_p), ("cols", C.c_void_p), ("vals", C.c_void_p),
+                ("dtype", C.c_int32), ("space", C.c_int32), ("dup", C.c_int32), ("reserved", C.c_uint32 * 7)]
+
+
+class BuildStats(C.Structure):
+    """osp_build_stats_t"""
+    _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("long_runs", C.c_uint64), ("ms_total", C.c_float),
+                ("launches", C.c_uint32), ("readbacks", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -290,6 +308,9 @@ MXV_EXPORTS = ["osp_csr_mxv"]
 
 # every symbol include/outerspace_spgemm_extract.h declares
 EXTRACT_EXPORTS = ["osp_csr_extract"]
+
+# every symbol include/outerspace_spgemm_build.h declares
+BUILD_EXPORTS = ["osp_csr_build"]
 
 _lib = None
 
@@ -379,6 +400,7 @@ def lib():
     L.osp_csr_transpose.argtypes = [vp, C.POINTER(Transpose), C.POINTER(vp), C.POINTER(TransposeStats)]
     L.osp_csr_mxv.argtypes = [vp, C.POINTER(Semiring), vp, vp, i32, C.POINTER(MxvStats)]
     L.osp_csr_extract.argtypes = [vp, C.POINTER(Extract), C.POINTER(vp), C.POINTER(ExtractStats)]
+    L.osp_csr_build.argtypes = [vp, C.POINTER(Build), C.POINTER(vp), C.POINTER(BuildStats)]
     _lib = L
     return L
 

@@ -31,6 +31,7 @@
 #include "../../include/outerspace_spgemm_transpose.h"
 #include "../../include/outerspace_spgemm_mxv.h"
 #include "../../include/outerspace_spgemm_extract.h"
+#include "../../include/outerspace_spgemm_build.h"
 #include "osp_internal.h"
 #include "osp_kernels.h"
 #include "osp_split.h"
@@ -47,6 +48,7 @@
 #include "osp_transpose.h"
 #include "osp_mxv.h"
 #include "osp_extract.h"
+#include "osp_build.h"
 
 namespace osp {
 
@@ -2012,6 +2014,109 @@ static void extract_impl(Context *ctx, const Result *in, Result *res, const osp_
                 (unsigned long long)ctx->malloc_calls);
 }
 
+// ---- a CSR result from a COO list, repeats combined in list order (osp_build.h) ----
+template <class T, int OP, bool VALS>
+static void launch_build_write(unsigned grid, hipStream_t s, const uint32_t *col, const uint32_t *perm, const ValueBits<T> *vals, uint64_t nnz,
+                               const BitScan &h, Result *res, unsigned long long *n_long) {
+    build_write_kernel<T, OP, VALS><<<grid, kCompactThreads, 0, s>>>(col, perm, vals, nnz, h.count, h.bits, h.pos, res->colidx, (ValueBits<T> *)res->vals,
+                                                                     n_long);
+}
+
+template <class T>
+static void build_impl(Context *ctx, Result *res, const osp_build_t &b, osp_build_stats_t *st) {
+    typedef ValueBits<T> V;
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    EventPair ev;
+    OSP_HIP(hipEventRecord(ev.a, s));
+    const uint64_t M = b.M, N = b.N, nnz = b.nnz;
+    const osp_memspace_t space = (osp_memspace_t)b.space;
+    const int dup = b.dup;
+    res->info = osp_result_info_t{};   // every field the build does not name stays 0
+    res->info.dtype = res->dtype;
+    note_variants(ctx, res);
+    res->info.M = M; res->info.N = N;
+    res->info.row_begin = 0; res->info.row_end = M;
+    uint64_t nnz_out = 0, long_runs = 0;
+    uint32_t launches = 0, readbacks = 0;
+    if (nnz == 0 || M == 0 || N == 0) {
+        empty_result<T>(res, M, s);
+    } else {
+        const bool has_vals = b.vals != nullptr && dup != DUP_COUNT;   // (COUNT reads no value: none is copied either)
+        const bool folds = has_vals && (dup == DUP_PLUS || dup == DUP_MIN || dup == DUP_MAX);
+        const uint32_t *rows = to_device(sc, b.rows, nnz, space, s), *cols = to_device(sc, b.cols, nnz, space, s);
+        const V *vals = has_vals ? to_device(sc, (const V *)b.vals, nnz, space, s) : nullptr;
+        uint32_t *ka = sc.get<uint32_t>(nnz), *pa = sc.get<uint32_t>(nnz), *kb = sc.get<uint32_t>(nnz), *pb = sc.get<uint32_t>(nnz);
+        uint32_t *k1 = sc.get<uint32_t>(nnz), *perm1 = sc.get<uint32_t>(nnz), *k2 = sc.get<uint32_t>(nnz);
+        uint32_t *row_sorted = sc.get<uint32_t>(nnz), *perm = sc.get<uint32_t>(nnz), *col_sorted = k1;   // (k1 is free after the second sort)
+        uint32_t *hist = sc.get<uint32_t>(rs_hist_entries(nnz));
+        uint32_t *hist_tmp = sc.get<uint32_t>(scan_scratch_entries(rs_hist_entries(nnz)));
+        int64_t *sptr = sc.get<int64_t>(M + 1);   // the sorted list's row pointer
+        // (pool buffers are recycled, and OSP_POISON fills them: the error word and the counter are zeroed on every call)
+        uint32_t *err = sc.get<uint32_t>(2);
+        unsigned long long *n_long = sc.get<unsigned long long>(1);
+        zero_async(s, {{err, sizeof(uint32_t)}, {n_long, sizeof(unsigned long long)}});
+        launches++;
+        // stable LSD, as coo_to_compressed_device: by column first, then by row
+        const int cbits = std::max(1, bits_for(N)), rbits = std::max(1, bits_for(M));
+        device_sort_rows<RsStoreEpilogue>(cols, nnz, cbits, ka, pa, kb, pb, hist, hist_tmp, RsStoreEpilogue{k1, perm1}, s, ctx->rank_atomic);
+        ingest_gather_u32_kernel<<<grid_for(nnz, 256), 256, 0, s>>>(rows, perm1, nnz, k2);
+        device_sort_rows<RsStoreEpilogue>(k2, nnz, rbits, ka, pa, kb, pb, hist, hist_tmp, RsStoreEpilogue{row_sorted, perm}, s, ctx->rank_atomic,
+                                          perm1);
+        ingest_gather_u32_kernel<<<grid_for(nnz, 256), 256, 0, s>>>(cols, perm, nnz, col_sorted);
+        ingest_ptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(row_sorted, nnz, M, sptr);
+        launches += (uint32_t)((cbits + 7) / 8 + (rbits + 7) / 8) * (2 + scan_launches((uint64_t)rs_blocks(nnz) * kRadix)) + 3;
+        // the call's read-back: the number of runs, with the error word -- nothing of out exists before the list is known to be good
+        uint32_t bad = 0;
+        const BitScan h = flag_and_scan(sc, nnz, s, [&](unsigned grid, uint64_t *bits) {
+            build_heads_kernel<<<grid, kCompactThreads, 0, s>>>(row_sorted, col_sorted, nnz, M, N, bits, err);
+        }, [&](Gather &ga) { ga.add(&bad, (const uint32_t *)err); });
+        readbacks++;
+        launches += h.launches;
+        if (bad) throw Error(OSP_ERR_RANGE, "build: an index of the list is outside its dimension");
+        if (dup == DUP_ERROR && h.count < nnz) throw Error(OSP_ERR_DUPLICATE, "build: duplicate coordinate (dup = OSP_DUP_ERROR)");
+        nnz_out = h.count;
+        alloc_rowptr(res, M);
+        alloc_entries<T>(res, nnz_out);
+        compact_rowptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(sptr, M, h.bits, h.pos, res->rowptr);
+        const unsigned grid = grid_for(nnz, (unsigned)kCompactChunk);
+        if (has_vals) {
+            switch (dup) {
+                case DUP_PLUS: launch_build_write<T, DUP_PLUS, true>(grid, s, col_sorted, perm, vals, nnz, h, res, n_long); break;
+                case DUP_MIN: launch_build_write<T, DUP_MIN, true>(grid, s, col_sorted, perm, vals, nnz, h, res, n_long); break;
+                case DUP_MAX: launch_build_write<T, DUP_MAX, true>(grid, s, col_sorted, perm, vals, nnz, h, res, n_long); break;
+                case DUP_LAST: launch_build_write<T, DUP_LAST, true>(grid, s, col_sorted, perm, vals, nnz, h, res, n_long); break;
+                default: launch_build_write<T, DUP_FIRST, true>(grid, s, col_sorted, perm, vals, nnz, h, res, n_long); break;   // FIRST, ERROR
+            }
+        } else {
+            switch (dup) {
+                case DUP_PLUS: launch_build_write<T, DUP_PLUS, false>(grid, s, col_sorted, perm, vals, nnz, h, res, n_long); break;
+                case DUP_COUNT: launch_build_write<T, DUP_COUNT, false>(grid, s, col_sorted, perm, vals, nnz, h, res, n_long); break;
+                default: launch_build_write<T, DUP_FIRST, false>(grid, s, col_sorted, perm, vals, nnz, h, res, n_long); break;   // every value is 1
+            }
+        }
+        launches += 2;
+        if (folds && nnz_out < nnz) {   // only then can a wave have folded a run
+            Gather last(s);
+            last.add(&long_runs, (const uint64_t *)n_long);
+            last.wait();
+            readbacks++;
+        }
+    }
+    finish_csr(res, ev, nnz_out, s);
+    *st = osp_build_stats_t{};
+    st->nnz_in = nnz;
+    st->nnz_out = nnz_out;
+    st->long_runs = long_runs;
+    st->ms_total = res->info.ms_total;
+    st->launches = launches;
+    st->readbacks = readbacks;
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] build dup=%d vals=%d %llu x %llu nnz %llu -> %llu long_runs=%llu launches=%u readbacks=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
+                dup, b.vals != nullptr, (unsigned long long)M, (unsigned long long)N, (unsigned long long)nnz, (unsigned long long)nnz_out,
+                (unsigned long long)long_runs, launches, readbacks, st->ms_total, (unsigned long long)ctx->malloc_calls);
+}
+
 static void destroy_result(Result *r) {
     if (!r) return;
     if (r->ctx) {
@@ -2447,6 +2552,26 @@ int osp_csr_extract(osp_result_t in_, const osp_extract_t *ex, osp_result_t *out
         osp_extract_stats_t st{};
         const int rc = new_result(in->ctx, in->dtype, out, [&](auto tag, Result *res) {
             extract_impl<decltype(tag)>(in->ctx, in, res, *ex, &st);
+        });
+        if (stats) *stats = st;
+        return rc;
+    });
+}
+
+int osp_csr_build(osp_context_t ctx_, const osp_build_t *b, osp_result_t *out, osp_build_stats_t *stats) {
+    Context *ctx = (Context *)ctx_;
+    if (!ctx || !b || !out) return fail(OSP_ERR_ARG, "null argument");
+    if (b->nnz && (!b->rows || !b->cols)) return fail(OSP_ERR_ARG, "build: null index list");
+    return guard([&] {
+        check_dtype(b->dtype); check_space(b->space);
+        if (b->dup < 0 || b->dup >= DUP_OPS) throw Error(OSP_ERR_ARG, "build: dup must be an osp_dup_op_t");
+        for (uint32_t w : b->reserved)
+            if (w) throw Error(OSP_ERR_ARG, "build: reserved words must be 0");
+        check_dims(b->M, 0, b->N);
+        if (b->nnz >= 0xffffffffull) throw Error(OSP_ERR_ARG, "build: lists of >= 2^32 - 1 entries are not supported");
+        osp_build_stats_t st{};
+        const int rc = new_result(ctx, b->dtype, out, [&](auto tag, Result *res) {
+            build_impl<decltype(tag)>(ctx, res, *b, &st);
         });
         if (stats) *stats = st;
         return rc;

@@ -10,7 +10,8 @@ clustering coefficient on ``osp_csr_reduce`` / ``osp_csr_apply_vectors`` / ``osp
 which need the transpose of a result ``osp_csr_transpose`` (``strongly_connected``, ``cocitation``,
 ``bibliographic_coupling``), and global PageRank and connected components on the product of a result with a dense vector
 ``osp_csr_mxv`` (``pagerank``, ``connected_components``), and subgraphs as matrices of their own on the submatrix of a result
-``osp_csr_extract`` (``induced_subgraph``, ``ego_network``, ``largest_component``, at the end).
+``osp_csr_extract`` (``induced_subgraph``, ``ego_network``, ``largest_component``), and matrices made from an edge list in
+one ``osp_csr_build`` (``adjacency_matrix``, ``laplacian``, ``incidence_matrix``, ``line_graph``, at the end).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -1403,3 +1404,99 @@ def largest_component(rows, cols, n=None, *, dtype=np.float64, ctx=None):
     u, v, info = induced_subgraph(rows, cols, nn, vertices, dtype=dtype, ctx=ctx)
     info["components"], info["rounds"] = cinfo["components"], cinfo["rounds"]
     return vertices, u, v, info
+
+
+# ---- a result from an edge list (osp_csr_build): adjacency, Laplacian, incidence matrix, line graph --------------------------------
+def _edge_list(rows, cols, n, weights, dtype, ctx):
+    """What the builders share: the context first (without a GPU this is where they fail), the checked edge list on its
+    device.  Returns (ctx, device, dtype, n, r, c, w): r, c int64 tensors, w a tensor of ``dtype`` or None."""
+    ctx = ctx or _S.default_context()
+    device = torch.device("cuda", ctx.device)
+    dtype = np.dtype(dtype).type
+    if dtype not in (np.float32, np.float64):
+        raise TypeError("dtype must be float32 or float64")
+    r, c = _as_index(rows, device), _as_index(cols, device)
+    if r.shape != c.shape or r.dim() != 1:
+        raise ValueError("rows and cols must be lists of the same length")
+    if n is None:
+        n = int(torch.maximum(r.max(), c.max()).item()) + 1 if r.numel() else 0
+    n = int(n)
+    if r.numel() and (int(torch.minimum(r.min(), c.min()).item()) < 0 or int(torch.maximum(r.max(), c.max()).item()) >= n):
+        raise ValueError(f"vertex ids must lie in [0, {n})")
+    w = None
+    if weights is not None:
+        w = torch.as_tensor(np.asarray(weights, dtype) if not torch.is_tensor(weights) else weights).to(device=device, dtype=_torch_dtype(dtype))
+        if w.shape != r.shape:
+            raise ValueError("weights must have one entry per edge")
+    return ctx, device, dtype, n, r, c, w
+
+
+def _build_device(ctx, device, n_rows, n_cols, r, c, w, dup, dtype):
+    """``ctx.build`` of int64 index tensors (and a value tensor or None) that live on the device."""
+    r32, c32 = r.to(torch.int32).contiguous(), c.to(torch.int32).contiguous()   # (the low 32 bits: a uint32 list's bits)
+    w = w.contiguous() if w is not None else None
+    torch.cuda.synchronize(device)   # the library works on its own stream
+    return ctx.build(n_rows, n_cols, r32, c32, w, dup=dup, dtype=dtype, space="device")[0]
+
+
+def adjacency_matrix(rows, cols, n=None, weights=None, *, directed=False, loops=False, dup="min", dtype=np.float64, ctx=None):
+    """The n x n adjacency matrix of the graph with edges (rows[e], cols[e]) on vertices [0, n) as a CSR result, in ONE
+    ``osp_csr_build``: the edge list -- for an undirected graph (``directed=False``) followed by its mirrored copy -- with
+    parallel edges combined by ``dup`` in list order (``Context.build``'s operators; ``"count"`` gives multiplicities).
+    ``weights=None`` means 1 for every edge.  Self loops are masked out unless ``loops`` (an undirected loop is then listed
+    twice, as every edge is).  An edgeless graph gives an empty n x n result.  The caller closes the result."""
+    ctx, device, dtype, n, r, c, w = _edge_list(rows, cols, n, weights, dtype, ctx)
+    if not loops:
+        keep = r != c
+        r, c = r[keep], c[keep]
+        w = w[keep] if w is not None else None
+    if not directed:
+        r, c = torch.cat([r, c]), torch.cat([c, r])
+        w = torch.cat([w, w]) if w is not None else None
+    return _build_device(ctx, device, n, n, r, c, w, dup, dtype)
+
+
+def laplacian(rows, cols, n=None, weights=None, *, dtype=np.float64, ctx=None):
+    """The Laplacian L = D - A of the UNDIRECTED graph with edges (rows[e], cols[e]) on vertices [0, n) as a CSR result:
+    self loops are dropped, parallel edges add.  ONE ``osp_csr_build`` with ``dup="plus"`` of the four blocks (u, v, -w),
+    (v, u, -w), (u, u, w), (v, v, w) concatenated in that order, which fixes every sum's order and with it its bits.  A
+    vertex without an edge has an empty row.  The caller closes the result."""
+    ctx, device, dtype, n, r, c, w = _edge_list(rows, cols, n, weights, dtype, ctx)
+    keep = r != c
+    u, v = r[keep], c[keep]
+    w = w[keep] if w is not None else torch.ones(u.numel(), dtype=_torch_dtype(dtype), device=device)
+    return _build_device(ctx, device, n, n, torch.cat([u, v, u, v]), torch.cat([v, u, u, v]), torch.cat([-w, -w, w, w]), "plus", dtype)
+
+
+def incidence_matrix(rows, cols, n=None, *, dtype=np.float64, ctx=None):
+    """The unoriented incidence matrix of the UNDIRECTED simple graph of an edge list (self loops dropped, parallel edges
+    one): the distinct edges {u, v}, u < v, ascending by (u, v), are the edge ids, and B is n x m with B[u, e] = B[v, e] = 1.
+    ``adjacency_matrix``, its entries above the diagonal (``select("triu", diag=1)``), then one build.  Returns (B, u, v):
+    the CsrResult (the caller closes it) and the edges' ends as int64 arrays on the host."""
+    A = adjacency_matrix(rows, cols, n, dtype=dtype, ctx=ctx)
+    try:
+        u, v, _ = _upper_entries(A)
+        n, ctx = A.shape[0], A._ctx
+    finally:
+        A.close()
+    e = np.arange(u.size, dtype=np.int64)
+    B, _ = ctx.build(n, u.size, np.concatenate([u, v]), np.concatenate([e, e]), None, dup="error", dtype=A.dtype, space="host")
+    return B, u, v
+
+
+def line_graph(rows, cols, n=None, *, dtype=np.float64, ctx=None):
+    """The line graph of the UNDIRECTED simple graph of an edge list: vertex e is edge e of ``incidence_matrix``, and two are
+    adjacent when the edges share an end.  ``B.matmul(B, self_transposed=True)`` -- B^T B: the number of shared ends -- then
+    ``select("offdiag")``, as ``cocitation`` does.  Returns (L, u, v): the m x m CsrResult with unit values (the caller closes
+    it) and the edges' ends."""
+    B, u, v = incidence_matrix(rows, cols, n, dtype=dtype, ctx=ctx)
+    try:
+        if u.size == 0:   # (no edge: nothing to multiply)
+            return B._ctx.build(0, 0, [], [], dtype=B.dtype)[0], u, v
+        P = B.matmul(B, self_transposed=True)
+    finally:
+        B.close()
+    try:
+        return P.select("offdiag")[0], u, v
+    finally:
+        P.close()

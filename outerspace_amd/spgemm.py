@@ -783,6 +783,69 @@ class Context:
                                                   _lib.OSP_DEVICE, C.byref(cfg), C.byref(h)))
         return CsrResult(self, h)
 
+    @staticmethod
+    def _coo_index_arg(v, space, what):
+        """An index list of ``build``: (address, count, keep-alive), taken as ``CsrResult.extract`` takes its lists.
+        ``space="host"``: an array-like of integers in [0, 2^32); ``space="device"``: a torch tensor of 4-byte integers (the
+        caller has synchronised its stream) or an ``(address, count)`` pair."""
+        if space == "host":
+            a = np.atleast_1d(np.asarray(v))
+            if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+                raise OspError(_lib.ERR_ARG, f"{what} must be a one-dimensional list of integers")
+            a = a.astype(np.int64) if a.size else np.zeros(0, np.int64)
+            if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+                raise OspError(_lib.ERR_ARG, f"{what} holds an index outside [0, 2^32)")
+            a = np.ascontiguousarray(a, np.uint32)
+            return (a.ctypes.data if a.size else 0), int(a.size), a
+        if hasattr(v, "data_ptr"):
+            if v.dim() != 1 or v.element_size() != 4 or v.is_floating_point() or not v.is_contiguous():
+                raise OspError(_lib.ERR_ARG, f"{what} must be a contiguous one-dimensional tensor of 4-byte integers")
+            return (v.data_ptr() if v.numel() else 0), int(v.numel()), v
+        return int(v[0]), int(v[1]), None
+
+    def build(self, M, N, rows, cols, vals=None, *, dup="plus", dtype=np.float64, space="host"):
+        """An M x N CSR result from the COO list (rows[t], cols[t], vals[t]) (``osp_csr_build``): any order, a coordinate may
+        repeat, and the repeats are combined in LIST order by ``dup``: ``"plus"`` (acc + v), ``"min"``, ``"max"`` (``ewise``'s
+        expressions), ``"first"``, ``"last"``, ``"count"`` (how many, as a value; reads no value) or ``"error"`` (a repeat is
+        ``OspError(ERR_DUPLICATE)``).  A coordinate given once keeps its value's bits.  ``vals=None``: every value is 1.
+        Lists are array-likes (``space="host"``; ``vals`` is converted to ``dtype``) or torch tensors of 4-byte integers /
+        ``(device address, count)`` pairs, with ``vals`` a tensor of ``dtype`` or a device address (``space="device"``: the
+        caller has synchronised).  An index beyond its dimension is ``OspError(ERR_RANGE)`` on either path.  Returns
+        (result, stats dict): nnz_in, nnz_out, long_runs, ms_total, launches, readbacks."""
+        if space not in ("device", "host"):
+            raise ValueError('space must be "device" or "host"')
+        if dup not in _lib.DUP_OPS:
+            raise ValueError(f"dup must be one of {' '.join(_lib.DUP_OPS)} (got {dup!r})")
+        dt = np.dtype(dtype)
+        if dt not in _DT:
+            raise TypeError("dtype must be float32 or float64")
+        rp, nr, keep_r = self._coo_index_arg(rows, space, "rows")
+        cp, nc, keep_c = self._coo_index_arg(cols, space, "cols")
+        if nr != nc:
+            raise OspError(_lib.ERR_ARG, f"rows and cols must have the same length (got {nr} and {nc})")
+        vp, keep_v = None, None
+        if vals is not None:
+            if space == "host":
+                keep_v = np.ascontiguousarray(vals, dt)
+                if keep_v.shape != (nr,):
+                    raise OspError(_lib.ERR_ARG, f"vals must have {nr} entries (got shape {keep_v.shape})")
+                vp = keep_v.ctypes.data if nr else None
+            elif hasattr(vals, "data_ptr"):
+                if vals.numel() != nr or vals.element_size() != dt.itemsize or not vals.is_floating_point() or not vals.is_contiguous():
+                    raise OspError(_lib.ERR_ARG, f"vals must be a contiguous tensor of {nr} values of {dt}")
+                keep_v, vp = vals, (vals.data_ptr() if nr else None)
+            else:
+                vp = int(vals)
+        b = _lib.Build()
+        b.M, b.N, b.nnz = int(M), int(N), nr
+        b.rows, b.cols, b.vals = rp or None, cp or None, vp
+        b.dtype, b.space, b.dup = _DT[dt], (_lib.OSP_HOST if space == "host" else _lib.OSP_DEVICE), _lib.DUP_OPS[dup]
+        stats = _lib.BuildStats()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().osp_csr_build(self._h, C.byref(b), C.byref(h), C.byref(stats)))
+        del keep_r, keep_c, keep_v
+        return CsrResult(self, h), stats.as_dict()
+
     def spgemm_mtx(self, path_a, path_b, transpose_b=True, dtype=np.float32, *, validate=True, partial_capacity=0):
         """The reference CLI's data flow: two .mtx files in, A * B^T (default) out."""
         cfg = self._config(validate, partial_capacity, None)
