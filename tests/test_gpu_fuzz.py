@@ -1,12 +1,14 @@
 """Randomised differential test: the HIP path against the CPU oracle on shapes, densities and skews drawn at
 random (seeded), through the code paths a fixed test list never combines: panels of random capacity, row shards,
-k ranges, streamed panels, both value types, both long-row split kernels.  Everything bit-exact."""
+k ranges, streamed panels, both value types, both long-row split kernels.  Everything bit-exact: values are compared by
+their bits (tests/ieee_model.py, assert_same_bits), not with ==."""
 import os
 
 import numpy as np
 import pytest
 
 from outerspace_amd import generators as gen
+from tests.ieee_model import assert_same_bits
 
 pytestmark = pytest.mark.gpu
 SEEN = {"cases": 0, "long_rows": 0, "piles": 0, "panels": 0}
@@ -66,7 +68,7 @@ def test_random_products_match_the_oracle(ctx, port, monkeypatch, seed):
         o0, o1 = want["rowptr"][lo], want["rowptr"][hi]
         assert np.array_equal(got.rowptr, want["rowptr"][lo:hi + 1] - o0)
         assert np.array_equal(got.colidx, want["colidx"][o0:o1])
-        assert np.array_equal(got.vals, want["vals"][o0:o1])
+        assert_same_bits(got.vals, want["vals"][o0:o1])
 
     res = ctx.spgemm_csc_csr(M, K, N, *acsc, *bcsr, partial_capacity=cap)
     assert res.info["partials"] == P
@@ -91,7 +93,7 @@ def test_random_products_match_the_oracle(ctx, port, monkeypatch, seed):
         wk = port.spgemm(M, K, N, *acsc, *bcsr, k0, k1)
         rk = ctx.spgemm_csc_csr(M, K, N, *acsc, *bcsr, k_range=(k0, k1))
         assert np.array_equal(rk.rowptr, wk["rowptr"]) and np.array_equal(rk.colidx, wk["colidx"])
-        assert np.array_equal(rk.vals, wk["vals"])
+        assert_same_bits(rk.vals, wk["vals"])
 
 
 def test_the_random_cases_reached_the_hard_paths():

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from outerspace_amd import generators as gen
+from tests.ieee_model import assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +31,7 @@ def test_multi_gpu_product_is_bit_identical(port, nranks, preset, scale, dt):
         info, (rowptr, colidx, v) = mg.spgemm_csc_csr(n, n, n, *acsc, *bcsr, validate=True)
         assert info["nranks"] == nranks and info["partials"] == want["partials"] and info["nnz_c"] == len(want["colidx"])
         assert np.array_equal(rowptr, want["rowptr"]) and np.array_equal(colidx, want["colidx"])
-        assert np.array_equal(v, want["vals"])     # parts merged in rank order = ascending k: the single-GPU bits
+        assert_same_bits(v, want["vals"])          # parts merged in rank order = ascending k: the single-GPU bits
         ranks = info["ranks"]
         assert ranks[0]["k_begin"] == 0 and ranks[-1]["k_end"] == n and ranks[0]["row_begin"] == 0 and ranks[-1]["row_end"] == n
         assert all(a["k_end"] == b["k_begin"] and a["row_end"] == b["row_begin"] for a, b in zip(ranks, ranks[1:]))
@@ -97,7 +98,8 @@ def test_multi_gpu_pipeline_granularity_and_panels(port, monkeypatch, subpanels)
     with S.MultiGpu(_devices(3)) as mg:
         for cap in (0, 4096):
             info, (rowptr, colidx, v) = mg.spgemm_csc_csr(M, K, N, *acsc, *bcsr, partial_capacity=cap)
-            assert np.array_equal(rowptr, want["rowptr"]) and np.array_equal(colidx, want["colidx"]) and np.array_equal(v, want["vals"])
+            assert np.array_equal(rowptr, want["rowptr"]) and np.array_equal(colidx, want["colidx"])
+            assert_same_bits(v, want["vals"])
     # all of k in one column: two of three slabs are empty
     a1 = (np.arange(50, dtype=np.uint32), np.full(50, 4, np.uint32), rng.uniform(1, 2, 50))
     b1 = (np.full(60, 4, np.uint32), np.arange(60, dtype=np.uint32), rng.uniform(1, 2, 60))
@@ -105,7 +107,8 @@ def test_multi_gpu_pipeline_granularity_and_panels(port, monkeypatch, subpanels)
     want = port.spgemm(50, 8, 60, *acsc, *bcsr)
     with S.MultiGpu(_devices(3)) as mg:
         info, (rowptr, colidx, v) = mg.spgemm_csc_csr(50, 8, 60, *acsc, *bcsr)
-        assert np.array_equal(rowptr, want["rowptr"]) and np.array_equal(colidx, want["colidx"]) and np.array_equal(v, want["vals"])
+        assert np.array_equal(rowptr, want["rowptr"]) and np.array_equal(colidx, want["colidx"])
+        assert_same_bits(v, want["vals"])
 
 
 def test_multi_gpu_errors(port):

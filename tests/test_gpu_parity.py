@@ -1,7 +1,8 @@
 """GPU parity: the HIP path (through the C ABI) against the CPU oracle and the golden fixtures.
 
 Bar: rowptr / colidx bit-exact.  Values: the merge sums equal keys in staging order (ascending k),
-the same order the oracle's stable sort yields, so values are compared BIT-EXACT against the oracle,
+the same order the oracle's stable sort yields, so values are compared BIT-EXACT against the oracle
+(as unsigned integers of their width, NaNs by position: tests/ieee_model.py, assert_same_bits),
 and within 1e-6 (f64) / 1e-5 (f32) relative against the reference's goldens (whose std::sort is
 unstable, so its summation order is unspecified).
 """
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 from outerspace_amd import generators as gen
+from tests.ieee_model import assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +42,7 @@ def assert_same(got, want, exact_vals=True):
     assert np.array_equal(got.rowptr, want["rowptr"])
     assert np.array_equal(got.colidx, want["colidx"])
     if exact_vals:
-        assert np.array_equal(got.vals, want["vals"])
+        assert_same_bits(got.vals, want["vals"])   # bits, not ==: -0.0 is not +0.0; NaNs by position (tests/ieee_model.py)
     else:
         assert np.allclose(got.vals, want["vals"], rtol=RTOL[np.dtype(got.dtype)], atol=0)
 
@@ -170,7 +172,7 @@ def test_long_row_split_kernels_agree(ctx, port, monkeypatch, row_max):
         got, want = run_both(ctx, port, n, n, n, (rows, cols, vals), (rows, cols, vals), dt)
         assert got.info["heavy_rows"] > 100
         assert np.array_equal(got.rowptr, want["rowptr"]) and np.array_equal(got.colidx, want["colidx"])
-        assert np.array_equal(got.vals, want["vals"])
+        assert_same_bits(got.vals, want["vals"])
 
 
 @pytest.mark.parametrize("preset,scale", [("uniform", 12), ("mild", 12), ("g500", 12)])
@@ -574,7 +576,8 @@ def test_row_shards_tile_the_product(ctx, port):
             assert r0 == end and r.shape[0] == r1 - r0
             lo, hi = want["rowptr"][r0], want["rowptr"][r1]
             assert np.array_equal(r.rowptr, want["rowptr"][r0:r1 + 1] - lo)
-            assert np.array_equal(r.colidx, want["colidx"][lo:hi]) and np.array_equal(r.vals, want["vals"][lo:hi])
+            assert np.array_equal(r.colidx, want["colidx"][lo:hi])
+            assert_same_bits(r.vals, want["vals"][lo:hi])
             assert r.info["partials"] <= want["partials"] / G * 2.0 + 5000  # balanced by estimated work (long rows weigh more)
             end, P = r1, P + r.info["partials"]
         assert end == n and P == want["partials"]
@@ -617,7 +620,8 @@ def test_streamed_panels_equal_the_resident_product(ctx, port):
             lo, hi = want["rowptr"][d["row_begin"]], want["rowptr"][d["row_end"]]
             assert rp[0] == 0 and rp[-1] == d["nnz"] == hi - lo
             assert np.array_equal(rp, want["rowptr"][d["row_begin"]:d["row_end"] + 1] - lo)
-            assert np.array_equal(ci, want["colidx"][lo:hi]) and np.array_equal(cv, want["vals"][lo:hi])
+            assert np.array_equal(ci, want["colidx"][lo:hi])
+            assert_same_bits(cv, want["vals"][lo:hi])
     # a row shard, streamed
     info, got = collect(partial_capacity=P // 7 + 1, row_shard=(1, 3))
     r0, r1 = info["row_begin"], info["row_end"]
@@ -784,7 +788,8 @@ def test_compressing_product_keeps_or_copies_its_bound_sized_arrays(port, monkey
     want = port.spgemm(n, n, n, *host)
     with S.Context(0) as c2:
         res = c2.spgemm_csc_csr_device(np.float64, n, n, n, [t.data_ptr() for t in (*csc, *csr)])
-        assert np.array_equal(res.rowptr, want["rowptr"]) and np.array_equal(res.colidx, want["colidx"]) and np.array_equal(res.vals, want["vals"])
+        assert np.array_equal(res.rowptr, want["rowptr"]) and np.array_equal(res.colidx, want["colidx"])
+        assert_same_bits(res.vals, want["vals"])
         if min_waste == "0":
             assert res.info["output_slack_bytes"] == 0 and res.info["ms_compact"] > 0
         else:

@@ -255,6 +255,7 @@ import numpy as np
 sys.path.insert(0, os.environ["OSP_TEST_ROOT"])
 from outerspace_amd import spgemm as S
 from oracle import oracle   # checker only
+from tests.ieee_model import assert_same_bits
 from tests.test_gpu_split_from_b import N, _two_panel_operands
 port = oracle.port()
 ops, halves, stretch = _two_panel_operands(6)
@@ -265,7 +266,8 @@ with S.Context(0) as ctx:
     for rep in range(3):
         got = ctx.spgemm_csc_csr(M, K, N, *acsc, *bcsr, partial_capacity=max(halves) + 10)
         assert got.info["panels"] == 2 and got.info["plans_overlapped"] == 1 and got.info["expand_partials"] == 4000, got.info
-        assert np.array_equal(got.rowptr, want["rowptr"]) and np.array_equal(got.colidx, want["colidx"]) and np.array_equal(got.vals, want["vals"])
+        assert np.array_equal(got.rowptr, want["rowptr"]) and np.array_equal(got.colidx, want["colidx"])
+        assert_same_bits(got.vals, want["vals"])
         got.close()
 print("SPLIT_FROM_B_OK")
 """
