@@ -2336,6 +2336,39 @@ __global__ void heavy_heads_kernel(const uint64_t *key, const uint64_t *headscan
     if (x == nh) { head_pos[headscan[nh]] = nh; return; }
     if (x == 0 || key[x] != key[x - 1]) head_pos[headscan[x]] = x;
 }
+// The runs of equal keys among n (> 0) 64-bit keys with their positions, in buffers of `sc` (a Scratch of osp_context.h,
+// which the translation unit includes after this header: hence the template).  The caller's fill kernel writes keys[0] and
+// poss[0]; sort() orders them, stably; the caller gathers its values by poss[cur]; heads() scans the run heads and lists
+// them.  Both return the number of kernels they launched.
+struct SortedRuns {
+    uint64_t n;
+    uint64_t *keys[2];   // n + 1 entries each: the idle one holds the run heads later
+    uint32_t *poss[2], *hist, *hist_tmp;
+    uint64_t *headscan, *headscan_tmp;
+    int cur = 0;
+    hipStream_t stream;
+    bool rank_atomic;
+    template <class Pool>
+    SortedRuns(Pool &sc, uint64_t n_) : n(n_), stream(sc.ctx->stream), rank_atomic(sc.ctx->rank_atomic) {
+        for (auto &k : keys) k = sc.template get<uint64_t>(n + 1);
+        for (auto &p : poss) p = sc.template get<uint32_t>(n);
+        hist = sc.template get<uint32_t>(sort_hist_entries(n));
+        hist_tmp = sc.template get<uint32_t>(scan_scratch_entries(sort_hist_entries(n)));
+        headscan = sc.template get<uint64_t>(n + 1);
+        headscan_tmp = sc.template get<uint64_t>(scan_scratch_entries(n));
+    }
+    uint32_t sort(int nbits) {
+        const RadixSorted r = device_radix_sort_pairs<uint64_t>(keys, poss, n, nbits, hist, hist_tmp, stream, rank_atomic);
+        cur = r.cur;
+        return r.launches;
+    }
+    uint64_t *head_pos() const { return keys[cur ^ 1]; }   // one entry per run and a sentinel, <= n + 1
+    uint32_t heads() {
+        const uint32_t scan = device_exclusive_scan<HeavyHeadFlag, uint64_t>(HeavyHeadFlag{keys[cur]}, n, headscan, headscan_tmp, stream);
+        heavy_heads_kernel<<<(unsigned)((n + 1 + 255) / 256), 256, 0, stream>>>(keys[cur], headscan, n, head_pos());
+        return scan + 1;
+    }
+};
 // One thread per run of equal (segment, col) keys: the run is summed in sorted order (= ascending staging position
 // = ascending k) and written in place.  Short runs are summed by their own thread; a run of more than 64 entries --
 // a pile: one output entry fed by thousands of products -- is summed by the whole wave: 64 values per coalesced load,

@@ -118,17 +118,14 @@ static uint64_t slab_symbolic(Context *ctx, uint64_t M, uint64_t Ks, const int64
         return 0;
     }
     Scratch ss(ctx);
-    uint32_t *ka = ss.get<uint32_t>(nnz), *pa = ss.get<uint32_t>(nnz), *kb = ss.get<uint32_t>(nnz), *pb = ss.get<uint32_t>(nnz);
+    const RowSort rs(ss, nnz, std::max(1, bits_for(M)));
     uint32_t *rows_sorted = ss.get<uint32_t>(nnz), *perm = ss.get<uint32_t>(nnz), *w_sorted = ss.get<uint32_t>(nnz);
     uint32_t *rowfirst = ss.get<uint32_t>(M + 1);
-    uint32_t *hist = ss.get<uint32_t>(rs_hist_entries(nnz));
-    uint32_t *hist_tmp = ss.get<uint32_t>(scan_scratch_entries(rs_hist_entries(nnz)));
     uint64_t *offs_sorted = ss.get<uint64_t>(nnz + 1);
     uint64_t *scan_tmp = ss.get<uint64_t>(scan_scratch_entries(std::max<uint64_t>(nnz, M + 1)));
     uint32_t *w = ss.get<uint32_t>(nnz);
     sym_chunk_len_kernel<<<grid_for(nnz, 256), 256, 0, s>>>(a_colptr, b_rowptr, 0, Ks, 0, nnz, w, nullptr);
-    device_sort_rows<SymEpilogue>(a_rowidx, nnz, std::max(1, bits_for(M)), ka, pa, kb, pb, hist, hist_tmp,
-                                  SymEpilogue{w, nullptr, rows_sorted, perm, w_sorted, nullptr}, s, ctx->rank_atomic);
+    rs.sort(a_rowidx, SymEpilogue{w, nullptr, rows_sorted, perm, w_sorted, nullptr});
     device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{w_sorted}, nnz, offs_sorted, scan_tmp, s);
     sym_row_offsets_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(rows_sorted, offs_sorted, nnz, M, row_off, rowfirst);
     sym_scatter_offsets_kernel<<<grid_for(nnz, 256), 256, 0, s>>>(perm, offs_sorted, rows_sorted, row_off, 0, nnz, chunk_off);

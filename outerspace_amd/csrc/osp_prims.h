@@ -339,18 +339,20 @@ inline uint64_t sort_blocks(uint64_t n) { return (n + kSortTile - 1) / kSortTile
 inline uint64_t sort_hist_entries(uint64_t n) { return sort_blocks(n) * kRadix + 1; }
 
 // Sorts bits [0, nbits) of the keys.  keys/vals ping-pong between buffer 0 and 1; returns the
-// index (0/1) of the buffer holding the sorted data.  n must be < 2^32.
+// index (0/1) of the buffer holding the sorted data, and the number of kernels it launched.  n must be < 2^32.
+struct RadixSorted { int cur; uint32_t launches; };
 template <class K>
-inline int device_radix_sort_pairs(K *keys[2], uint32_t *vals[2], uint64_t n, int nbits,
-                                   uint32_t *hist, uint32_t *scan_scratch, hipStream_t stream, bool rank_atomic) {
+inline RadixSorted device_radix_sort_pairs(K *keys[2], uint32_t *vals[2], uint64_t n, int nbits,
+                                           uint32_t *hist, uint32_t *scan_scratch, hipStream_t stream, bool rank_atomic) {
     int cur = 0;
-    if (n == 0) return cur;
+    uint32_t launches = 0;
+    if (n == 0) return {cur, launches};
     const uint32_t nblocks = (uint32_t)sort_blocks(n);
     for (int shift = 0; shift < nbits; shift += 8) {
         sort_hist_kernel<K><<<nblocks, kSortThreads, 0, stream>>>(keys[cur], n, shift, hist, nblocks);
         // in-place exclusive scan of the digit-major histogram (reads precede writes per tile)
-        device_exclusive_scan<LoadU32, uint32_t>(LoadU32{hist}, (uint64_t)nblocks * kRadix, hist,
-                                                 scan_scratch, stream);
+        launches += 2 + device_exclusive_scan<LoadU32, uint32_t>(LoadU32{hist}, (uint64_t)nblocks * kRadix, hist,
+                                                                 scan_scratch, stream);
         if (rank_atomic)
             sort_scatter_kernel<K, true><<<nblocks, kSortThreads, 0, stream>>>(keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, shift,
                                                                                 hist, nblocks);
@@ -359,7 +361,7 @@ inline int device_radix_sort_pairs(K *keys[2], uint32_t *vals[2], uint64_t n, in
                                                                                  hist, nblocks);
         cur ^= 1;
     }
-    return cur;
+    return {cur, launches};
 }
 
 }  // namespace osp

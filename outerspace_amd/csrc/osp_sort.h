@@ -12,6 +12,8 @@
 //   * the LAST pass hands every sorted element to an epilogue functor (here: chunk length lookup),
 // so no (key, payload) arrays are materialised before the first or after the last pass.
 #pragma once
+#include <cassert>
+
 #include "osp_kernels.h"
 
 namespace osp {
@@ -139,16 +141,21 @@ __global__ __launch_bounds__(kRsThreads) void rs_scatter_kernel(
     }
 }
 
+// passes of a sort by the low `nbits` bits
+inline int rs_passes(int nbits) { return std::max(1, (nbits + 7) / 8); }
+
 // Sort (keys_raw[i], i) by the low `nbits` bits of the key.  Buffers a and b are (key, payload) pairs
 // of n entries each; the last pass calls epi(sorted position, key, payload) instead of storing.
-// hist needs rs_hist_entries(n) u32, scan_scratch scan_scratch_entries(rs_hist_entries(n)).
+// hist needs rs_hist_entries(n) u32, scan_scratch scan_scratch_entries(rs_hist_entries(n)).  Returns the number of kernels
+// it launched.
 template <bool RA, class Epi>
-inline void device_sort_rows_ra(const uint32_t *keys_raw, uint64_t n, int nbits, uint32_t *ka, uint32_t *pa, uint32_t *kb,
-                                uint32_t *pb, uint32_t *hist, uint32_t *scan_scratch, Epi epi, hipStream_t stream,
-                                const uint32_t *vals_raw) {
-    if (n == 0) return;
+inline uint32_t device_sort_rows_ra(const uint32_t *keys_raw, uint64_t n, int nbits, uint32_t *ka, uint32_t *pa, uint32_t *kb,
+                                    uint32_t *pb, uint32_t *hist, uint32_t *scan_scratch, Epi epi, hipStream_t stream,
+                                    const uint32_t *vals_raw) {
+    if (n == 0) return 0;
     const uint32_t nb = rs_blocks(n);
-    const int npass = std::max(1, (nbits + 7) / 8);
+    const int npass = rs_passes(nbits);
+    uint32_t launches = 0;
     const uint32_t *kin = keys_raw, *pin = vals_raw;
     uint32_t *kout = ka, *pout = pa;
     for (int p = 0; p < npass; p++) {
@@ -156,7 +163,7 @@ inline void device_sort_rows_ra(const uint32_t *keys_raw, uint64_t n, int nbits,
         const int shift = 8 * p;
         if (first) rs_hist_kernel<true><<<nb, kRsThreads, 0, stream>>>(kin, n, shift, hist, nb);
         else rs_hist_kernel<false><<<nb, kRsThreads, 0, stream>>>(kin, n, shift, hist, nb);
-        device_exclusive_scan<LoadU32, uint32_t>(LoadU32{hist}, (uint64_t)nb * kRadix, hist, scan_scratch, stream);
+        launches += 2 + device_exclusive_scan<LoadU32, uint32_t>(LoadU32{hist}, (uint64_t)nb * kRadix, hist, scan_scratch, stream);
         if (first && last) rs_scatter_kernel<true, true, RA, Epi><<<nb, kRsThreads, 0, stream>>>(kin, pin, kout, pout, n, shift, hist, nb, epi);
         else if (first) rs_scatter_kernel<true, false, RA, Epi><<<nb, kRsThreads, 0, stream>>>(kin, pin, kout, pout, n, shift, hist, nb, epi);
         else if (last) rs_scatter_kernel<false, true, RA, Epi><<<nb, kRsThreads, 0, stream>>>(kin, pin, kout, pout, n, shift, hist, nb, epi);
@@ -164,16 +171,48 @@ inline void device_sort_rows_ra(const uint32_t *keys_raw, uint64_t n, int nbits,
         kin = kout; pin = pout;
         if (kout == ka) { kout = kb; pout = pb; } else { kout = ka; pout = pa; }
     }
+    return launches;
 }
 
 // rank_atomic: which instantiation of the stable rank runs (Context::rank_atomic)
 template <class Epi>
-inline void device_sort_rows(const uint32_t *keys_raw, uint64_t n, int nbits, uint32_t *ka, uint32_t *pa, uint32_t *kb,
-                             uint32_t *pb, uint32_t *hist, uint32_t *scan_scratch, Epi epi, hipStream_t stream, bool rank_atomic,
-                             const uint32_t *vals_raw = nullptr /* payload of keys_raw[i]; default: i itself */) {
-    if (rank_atomic) device_sort_rows_ra<true, Epi>(keys_raw, n, nbits, ka, pa, kb, pb, hist, scan_scratch, epi, stream, vals_raw);
-    else device_sort_rows_ra<false, Epi>(keys_raw, n, nbits, ka, pa, kb, pb, hist, scan_scratch, epi, stream, vals_raw);
+inline uint32_t device_sort_rows(const uint32_t *keys_raw, uint64_t n, int nbits, uint32_t *ka, uint32_t *pa, uint32_t *kb,
+                                 uint32_t *pb, uint32_t *hist, uint32_t *scan_scratch, Epi epi, hipStream_t stream, bool rank_atomic,
+                                 const uint32_t *vals_raw = nullptr /* payload of keys_raw[i]; default: i itself */) {
+    if (rank_atomic) return device_sort_rows_ra<true, Epi>(keys_raw, n, nbits, ka, pa, kb, pb, hist, scan_scratch, epi, stream, vals_raw);
+    return device_sort_rows_ra<false, Epi>(keys_raw, n, nbits, ka, pa, kb, pb, hist, scan_scratch, epi, stream, vals_raw);
 }
+
+// The buffers of a sort of n keys of up to `nbits` bits, taken from `sc` (a Scratch of osp_context.h, which the translation
+// unit includes after this header: hence the template), and the sort on them.  The (key, payload) pairs between two passes:
+// none with one pass, one pair of arrays with two, two pairs beyond.  Several sorts in a row share one RowSort built for
+// the largest nbits among them.
+struct RowSort {
+    uint64_t n;
+    int max_bits;
+    uint32_t *ka = nullptr, *pa = nullptr, *kb = nullptr, *pb = nullptr, *hist, *hist_tmp;
+    hipStream_t stream;
+    bool rank_atomic;
+    template <class Pool>
+    RowSort(Pool &sc, uint64_t n_, int nbits) : n(n_), max_bits(nbits), stream(sc.ctx->stream), rank_atomic(sc.ctx->rank_atomic) {
+        if (rs_passes(nbits) > 1) { ka = sc.template get<uint32_t>(n); pa = sc.template get<uint32_t>(n); }
+        if (rs_passes(nbits) > 2) { kb = sc.template get<uint32_t>(n); pb = sc.template get<uint32_t>(n); }
+        hist = sc.template get<uint32_t>(rs_hist_entries(n));
+        hist_tmp = sc.template get<uint32_t>(scan_scratch_entries(rs_hist_entries(n)));
+    }
+    // device_sort_rows of (keys_raw[i], vals_raw ? vals_raw[i] : i) by the constructor's bits; returns the number of kernels
+    // launched
+    template <class Epi>
+    uint32_t sort(const uint32_t *keys_raw, Epi epi, const uint32_t *vals_raw = nullptr) const {
+        return sort_bits(keys_raw, max_bits, epi, vals_raw);
+    }
+    // the same by the low nbits: one of several sorts may need fewer passes than the buffers allow
+    template <class Epi>
+    uint32_t sort_bits(const uint32_t *keys_raw, int nbits, Epi epi, const uint32_t *vals_raw = nullptr) const {
+        assert(rs_passes(nbits) <= rs_passes(max_bits));
+        return device_sort_rows<Epi>(keys_raw, n, nbits, ka, pa, kb, pb, hist, hist_tmp, epi, stream, rank_atomic, vals_raw);
+    }
+};
 
 // plain epilogue: store the sorted pairs
 struct RsStoreEpilogue {
@@ -186,6 +225,20 @@ struct RsStoreEpilogue {
 __global__ void ingest_gather_u32_kernel(const uint32_t *in, const uint32_t *perm, uint64_t n, uint32_t *out) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < n) out[t] = in[perm[t]];
+}
+// The stable two-key LSD sort of a COO list of n (> 0) entries: by the inner index, the outer keys gathered in that order,
+// then by the outer key with the first permutation as payload.  outer_sorted[t] and perm[t]: the outer key and the list
+// position of the t-th entry in (outer, inner) order.  spare: n words of `sc` the sort is done with.  launches: all its kernels.
+struct CooOrder { uint32_t *outer_sorted, *perm, *spare; uint32_t launches; };
+template <class Pool>
+inline CooOrder coo_sort_two_keys(Pool &sc, uint64_t n, const uint32_t *inner, int inner_bits, const uint32_t *outer, int outer_bits) {
+    const RowSort rs(sc, n, std::max(inner_bits, outer_bits));
+    uint32_t *k1 = sc.template get<uint32_t>(n), *perm1 = sc.template get<uint32_t>(n), *k2 = sc.template get<uint32_t>(n);
+    CooOrder o{sc.template get<uint32_t>(n), sc.template get<uint32_t>(n), k1, 0};
+    o.launches = rs.sort_bits(inner, inner_bits, RsStoreEpilogue{k1, perm1});
+    ingest_gather_u32_kernel<<<(unsigned)((n + 255) / 256), 256, 0, rs.stream>>>(outer, perm1, n, k2);
+    o.launches += 1 + rs.sort_bits(k2, outer_bits, RsStoreEpilogue{o.outer_sorted, o.perm}, perm1);
+    return o;
 }
 // final gather in (segment, inner) order + range check + adjacent-duplicate check (the reference's dupcheck)
 template <class T>

@@ -207,6 +207,54 @@ def test_the_short_cap_knob_moves_rows_between_the_classes(operands, monkeypatch
     assert _want(dt, "plus", "times", 64)[1]["long_rows"] == 9 and _want(dt, "plus", "times", 63)[1]["long_rows"] == 10
 
 
+# ---- the launch count -----------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _small_pair():
+    """40 x 40 times 40 x 40, about 200 entries each, built by arithmetic: five entries a row, 25 products a row of a; row 7
+    of a is empty, and its row 9 holds one entry, at the one entry of b's row 3: one product."""
+    i, j = np.divmod(np.arange(1600), 40)
+
+    def csr(keep):
+        rowptr = np.concatenate([[0], np.cumsum(np.bincount(i[keep], minlength=40))]).astype(np.int64)
+        return rowptr, j[keep].astype(np.uint32), (1.0 + (np.flatnonzero(keep) % 7)).astype(np.float64)
+
+    ka = (7 * i + 3 * j) % 8 == 0
+    ka &= (i != 7) & ((i != 9) | (j < 8))
+    return csr(ka), csr(((3 * i + 7 * j) % 8 == 0) & ((i != 3) | (j < 8)))
+
+
+# st["launches"] of the three settings as commit acee2bd ("Test the product's summation paths on IEEE edge values, bit for
+# bit") reports them on an MI355X, before the sorts counted their own launches: short rows only; every row of more than one
+# product long (the sorted-runs path); that in several batches
+MXM_LAUNCHES = {(None, None): 8, ("1", None): 24, ("1", "50"): 326}
+
+
+@pytest.mark.parametrize("cap,batch", list(MXM_LAUNCHES))
+def test_mxm_reports_its_launches(mctx, monkeypatch, cap, batch):
+    for name, value in (("OSP_MXM_SHORT_CAP", cap), ("OSP_MXM_BATCH", batch)):
+        if value is None:
+            monkeypatch.delenv(name, raising=False)
+        else:
+            monkeypatch.setenv(name, value)
+    a, b = _small_pair()
+    assert (len(a[1]), len(b[1])) == (191, 196)
+    want, wst = model.mxm(a, b, 40, "plus", "times", int(cap or CAP), int(batch or model.BATCH))
+    ra, rb = _upload(mctx, 40, a), _upload(mctx, 40, b)
+    try:
+        res, st = ra.mxm(rb)
+        try:
+            print("mxm launches", (cap, batch), st["launches"], st["short_rows"], st["long_rows"], st["batches"])
+            _assert_same(res, want, (cap, batch))
+            _check_stats(st, res, wst, a, b)
+            assert (st["long_rows"] > 0) == (cap is not None) and (st["batches"] > 1) == (batch is not None)
+            assert st["launches"] == MXM_LAUNCHES[cap, batch], (cap, batch, st)
+        finally:
+            res.close()
+    finally:
+        ra.close()
+        rb.close()
+
+
 # ---- (PLUS, TIMES) is the library's own product ---------------------------------------------------------------------------------
 def _library_product(mctx, ra, rb):
     a, b = _result_as_input(ra, DEV), _result_as_input(rb, DEV)

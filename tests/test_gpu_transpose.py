@@ -13,6 +13,7 @@ import torch
 from outerspace_amd import _lib
 from outerspace_amd import generators as gen
 from outerspace_amd import spgemm as S
+from tests import build_model
 from tests import semiring_model
 from tests import test_gpu_apply_mask as am   # _upload, _bits, _special, _traps only
 from tests import transpose_model as model
@@ -177,6 +178,53 @@ def test_row_mask_path_one_row_of_half_a_million_entries(mctx, dt):
     src = _upload(mctx, N, csr)
     try:
         _transpose_and_check(src, csr, N, 1)
+    finally:
+        src.close()
+
+
+# ---- the launch count -------------------------------------------------------------------------------------------------------------
+def _launches(M, N, nnz, gather):
+    """Kernels of a call on a non-empty input, as transpose_impl counts them.  Row mask: the mask, the scan of its popcounts,
+    the placement.  Sort: the packing of the records (not with the bisecting gather), a histogram, a scan of the histogram
+    and a scatter per pass, the row pointer.  The constants come from the sources, as tests/build_model.py reads them."""
+    if M <= 64:
+        return 1 + build_model._scan_launches(N) + 1
+    per_pass = 2 + build_model._scan_launches(-(-nnz // build_model.SORT_TILE) * build_model.RADIX)
+    return (0 if gather == "bisect" else 1) + model.passes(N) * per_pass + 1
+
+
+# entries beyond which the scan of the sort's histogram takes its three-launch form
+BIG = build_model.SCAN_SMALL_TILES * build_model.SCAN_TILE // build_model.RADIX * build_model.SORT_TILE
+
+
+@functools.lru_cache(maxsize=None)
+def _counted(M, N, draws):
+    if M == 64:
+        return _rowmask(64, np.float64)
+    rng = np.random.default_rng(N + draws)
+    return _csr_of(M, N, np.concatenate([[0, M * N - 1], rng.integers(0, M * N, draws)]), np.float64, rng)
+
+
+@pytest.mark.parametrize("gather", [None, "bisect"])
+@pytest.mark.parametrize("M,N,draws,passes", [(65, 200, 300, 1), (65, 300, 300, 2), (65, 70000, 300, 3), (65, 70000, 2 * BIG, 3),
+                                              (64, 1000, 0, 0)])
+def test_transpose_reports_its_launches(mctx, monkeypatch, M, N, draws, passes, gather):
+    """M = 65 is one row past the row-mask path: about 300 entries sorted in one, two and three passes, and over a million
+    in three (the histogram's scan in three launches instead of one); M = 64 takes the row mask, whatever the gather."""
+    monkeypatch.delenv("OSP_TRANSPOSE_PATH", raising=False)
+    if gather is None:
+        monkeypatch.delenv("OSP_TRANSPOSE_GATHER", raising=False)
+    else:
+        monkeypatch.setenv("OSP_TRANSPOSE_GATHER", gather)
+    csr = _counted(M, N, draws)
+    nnz = len(csr[1])
+    assert M == 64 or 280 <= nnz <= 302 or (draws == 2 * BIG and nnz > BIG)
+    src = _upload(mctx, N, csr)
+    try:
+        st = _transpose_and_check(src, csr, N, 1 if M == 64 else 2, (M, N, gather))
+        print("transpose launches", (M, N, draws, gather), st["launches"], st["passes"])
+        assert st["passes"] == passes
+        assert st["launches"] == _launches(M, N, nnz, gather), (M, N, gather, st)
     finally:
         src.close()
 
