@@ -191,6 +191,18 @@ class MxvStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+MXD_MAX_COLS = 65536   # OSP_MXD_MAX_COLS
+
+
+class MxdStats(C.Structure):
+    """osp_mxd_stats_t"""
+    _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("cols", C.c_uint64), ("long_segments", C.c_uint64),
+                ("lanes_per_row", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float), ("reserved", C.c_uint32 * 7)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 class Transpose(C.Structure):
     """osp_transpose_t"""
     _fields_ = [("reserved", C.c_uint32 * 8)]
@@ -306,6 +318,9 @@ TRANSPOSE_EXPORTS = ["osp_csr_transpose"]
 # every symbol include/outerspace_spgemm_mxv.h declares
 MXV_EXPORTS = ["osp_csr_mxv"]
 
+# every symbol include/outerspace_spgemm_mxd.h declares
+MXD_EXPORTS = ["osp_csr_mxd"]
+
 # every symbol include/outerspace_spgemm_extract.h declares
 EXTRACT_EXPORTS = ["osp_csr_extract"]
 
@@ -399,6 +414,7 @@ def lib():
     L.osp_csr_mxm.argtypes = [vp, vp, C.POINTER(Semiring), C.POINTER(vp), C.POINTER(MxmStats)]
     L.osp_csr_transpose.argtypes = [vp, C.POINTER(Transpose), C.POINTER(vp), C.POINTER(TransposeStats)]
     L.osp_csr_mxv.argtypes = [vp, C.POINTER(Semiring), vp, vp, i32, C.POINTER(MxvStats)]
+    L.osp_csr_mxd.argtypes = [vp, C.POINTER(Semiring), vp, u64, vp, i32, C.POINTER(MxdStats)]
     L.osp_csr_extract.argtypes = [vp, C.POINTER(Extract), C.POINTER(vp), C.POINTER(ExtractStats)]
     L.osp_csr_build.argtypes = [vp, C.POINTER(Build), C.POINTER(vp), C.POINTER(BuildStats)]
     _lib = L

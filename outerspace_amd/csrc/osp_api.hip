@@ -30,6 +30,7 @@
 #include "../../include/outerspace_spgemm_mxm.h"
 #include "../../include/outerspace_spgemm_transpose.h"
 #include "../../include/outerspace_spgemm_mxv.h"
+#include "../../include/outerspace_spgemm_mxd.h"
 #include "../../include/outerspace_spgemm_extract.h"
 #include "../../include/outerspace_spgemm_build.h"
 #include "osp_internal.h"
@@ -47,6 +48,7 @@
 #include "osp_mxm.h"
 #include "osp_transpose.h"
 #include "osp_mxv.h"
+#include "osp_mxd.h"
 #include "osp_extract.h"
 #include "osp_build.h"
 
@@ -944,6 +946,18 @@ int osp_csr_mxv(osp_result_t in_, const osp_semiring_t *sr, const void *x, void 
         check_reserved(sr->reserved, "mxv");
         if (!x && sr->mul != OSP_EWISE_FIRST) throw Error(OSP_ERR_ARG, "mxv: x may be null only when mul is FIRST");
     }, [&](auto tag, osp_mxv_stats_t *st) { mxv_impl<decltype(tag)>(in->ctx, in, *sr, x, y, space, st); });
+}
+
+int osp_csr_mxd(osp_result_t in_, const osp_semiring_t *sr, const void *x, uint64_t k, void *y, osp_memspace_t space, osp_mxd_stats_t *stats) {
+    Result *in = (Result *)in_;
+    return csr_vector_op(in, sr && y, stats, [&] {
+        check_space(space);
+        if (sr->add != OSP_EWISE_PLUS && sr->add != OSP_EWISE_MIN && sr->add != OSP_EWISE_MAX) throw Error(OSP_ERR_ARG, "mxd: add is not one of PLUS, MIN, MAX");
+        if (sr->mul < OSP_EWISE_PLUS || sr->mul > OSP_EWISE_SECOND) throw Error(OSP_ERR_ARG, "mxd: mul is not one of TIMES, PLUS, MIN, MAX, FIRST, SECOND");
+        check_reserved(sr->reserved, "mxd");
+        if (!x && sr->mul != OSP_EWISE_FIRST) throw Error(OSP_ERR_ARG, "mxd: x may be null only when mul is FIRST");
+        if (k > kMxdMaxCols) throw Error(OSP_ERR_ARG, "mxd: k exceeds OSP_MXD_MAX_COLS");
+    }, [&](auto tag, osp_mxd_stats_t *st) { mxd_impl<decltype(tag)>(in->ctx, in, *sr, x, k, y, space, st); });
 }
 
 int osp_csr_apply_vectors(osp_result_t in_, const osp_vector_apply_t *ap, const void *x_rows, const void *y_cols, osp_memspace_t space,

@@ -1183,6 +1183,86 @@ static void mxv_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, c
                 launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
 }
 
+// ---- a CSR result times a dense matrix under a semiring (osp_mxd.h) ----
+template <class T>
+static void mxd_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, const void *x_in, uint64_t k, void *y_out, osp_memspace_t space,
+                     osp_mxd_stats_t *st) {
+    OpFrame fr(ctx);
+    hipStream_t s = fr.s;
+    Scratch &sc = fr.sc;
+    const uint64_t M = in->info.M, N = in->info.N, nnz = in->info.nnz_c;
+    const int add = sr.add == OSP_EWISE_PLUS ? RED_PLUS : sr.add == OSP_EWISE_MIN ? RED_MIN : RED_MAX;
+    uint32_t lgk = 0;   // log2 of the lanes a row gets: the power of two >= min(k, 64)
+    while (lgk < 6 && (1ull << lgk) < k) lgk++;
+    const uint32_t tiles = (uint32_t)((k + kWave - 1) / kWave);
+    uint64_t long_segments = 0;
+    uint32_t launches = 0;
+    // (the matrix is formed in a pool buffer and copied out last: x may be y, and a call that fails leaves y as it was)
+    T *out = sc.get<T>(M * k);
+    std::vector<T> ids;
+    if (M && k && nnz) {
+        const T *x = sr.mul == OSP_EWISE_FIRST ? nullptr : to_device(sc, (const T *)x_in, N * k, space, s);
+        const int64_t *rowptr = in->rowptr;
+        const uint32_t *col = in->colidx;
+        const T *vals = (const T *)in->vals;
+        // a grid of (items << lgk) lanes by column tiles: 64 >> lgk items per wave
+        const auto grid = [&](uint64_t items) { return dim3(grid_for((items + (kWave >> lgk) - 1) >> (6 - lgk), kReduceWaves), tiles); };
+        mxv_with_ops(add, sr.mul, [&](auto a, auto m) {
+            constexpr int ADD = decltype(a)::value, MUL = decltype(m)::value;
+            mxd_rows_kernel<T, ADD, MUL><<<grid(M), kReduceWaves * kWave, 0, s>>>(rowptr, col, vals, x, M, k, lgk, out);
+            launches++;
+            if (nnz <= kReduceBlock) return;   // (no row can be long)
+            // the long rows, listed and cut into blocks as mxv_impl lists and cuts them
+            unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MCL_COUNTERS);
+            zero_async(s, {{counters, MCL_COUNTERS * sizeof(uint64_t)}});
+            uint32_t *long_rows = sc.get<uint32_t>(nnz / ((uint64_t)kReduceBlock + 1) + 1);
+            mcl_classify_kernel<<<grid_for(M, 256), 256, 0, s>>>(rowptr, M, kReduceBlock, long_rows, counters);
+            launches += 2;
+            const uint64_t n_long = d2h((const uint64_t *)counters + MCL_NLONG, s);
+            long_segments = n_long;
+            if (!n_long) return;
+            const uint64_t max_blocks = nnz / kReduceBlock + n_long;
+            uint32_t *nblk = sc.get<uint32_t>(n_long + 1), *map = sc.get<uint32_t>(n_long);
+            int64_t *blkptr = sc.get<int64_t>(n_long + 1);
+            uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(n_long + 1));
+            T *partial = sc.get<T>(max_blocks * k);
+            reduce_long_setup_kernel<<<grid_for(n_long, 256), 256, 0, s>>>(rowptr, long_rows, n_long, nullptr, nblk, map);
+            launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{nblk}, n_long, (uint64_t *)blkptr, tmp, s);
+            mxd_blocks_kernel<T, ADD, MUL><<<grid(max_blocks), kReduceWaves * kWave, 0, s>>>(rowptr, col, vals, x, long_rows, blkptr, n_long, k, lgk,
+                                                                                             partial);
+            mxd_upper_kernel<T, ADD><<<grid(n_long), kReduceWaves * kWave, 0, s>>>(long_rows, blkptr, n_long, partial, k, lgk, out);
+            launches += 2;
+        });
+    } else if (M && k) {
+        const T inf = std::numeric_limits<T>::infinity();
+        ids.assign(M * k, add == RED_MIN ? inf : add == RED_MAX ? -inf : T(0));   // every row is empty: no kernel
+    }
+    const float ms = fr.stop();
+    if (M && k) {
+        if (!ids.empty()) {
+            if (space == OSP_DEVICE) copy_h2d(y_out, ids.data(), M * k * sizeof(T), s);
+            else memcpy(y_out, ids.data(), M * k * sizeof(T));
+        } else if (space == OSP_DEVICE) {
+            OSP_HIP(hipMemcpyAsync(y_out, out, M * k * sizeof(T), hipMemcpyDeviceToDevice, s));
+        } else {
+            copy_d2h(y_out, out, M * k * sizeof(T), s);
+        }
+        OSP_HIP(hipStreamSynchronize(s));
+    }
+    *st = osp_mxd_stats_t{};
+    st->nnz_in = nnz;
+    st->nnz_out = M * k;
+    st->cols = k;
+    st->long_segments = long_segments;
+    st->lanes_per_row = 1u << lgk;
+    st->launches = launches;
+    st->ms_total = ms;
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] mxd add=%d mul=%d M=%llu N=%llu k=%llu nnz=%llu lanes=%u long=%llu launches=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
+                sr.add, sr.mul, (unsigned long long)M, (unsigned long long)N, (unsigned long long)k, (unsigned long long)nnz, 1u << lgk,
+                (unsigned long long)long_segments, launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
+}
+
 template <class T, int OP = 0>
 static void launch_apply_rows(int op, hipStream_t s, const Result *in, const ValueBits<T> *src, const ValueBits<T> *x, Result *res) {
     if constexpr (OP < EW_OPS) {

@@ -1500,3 +1500,137 @@ def line_graph(rows, cols, n=None, *, dtype=np.float64, ctx=None):
         return P.select("offdiag")[0], u, v
     finally:
         P.close()
+
+
+# ---- a result times a dense matrix (osp_csr_mxd): label spreading, feature propagation ---------------------------------------------
+def _check_labels(labels, n):
+    """``labels`` -- a dict vertex -> class, or a sequence of n class ids with a negative id for "unlabelled" -- as (vertices
+    int64, column of each int64, classes): ``classes`` are the distinct classes in ascending order, one column of F each."""
+    if isinstance(labels, dict):
+        verts = np.fromiter(labels.keys(), np.int64, len(labels))
+        vals = list(labels.values())
+    else:
+        a = np.asarray(labels)
+        if a.shape != (n,):
+            raise ValueError(f"labels must be a dict or hold one class id per vertex ({n})")
+        verts = np.flatnonzero(a >= 0).astype(np.int64)
+        vals = a[verts].tolist()
+    if verts.size == 0:
+        raise ValueError("no vertex is labelled")
+    if verts.min() < 0 or verts.max() >= n:
+        raise ValueError(f"labelled vertices must lie in [0, {n})")
+    classes = sorted(set(vals))
+    column = {c: i for i, c in enumerate(classes)}
+    return verts, np.array([column[v] for v in vals], np.int64), classes
+
+
+def _normalised(A, device, td):
+    """D^-1/2 A D^-1/2 of the CSR result A as a new result, D its entries per row (``reduce("rows", "count")``; a count of 0
+    counts as 1) in ONE ``apply_vectors``.  Returns (S, maximum count)."""
+    n = A.shape[0]
+    deg = torch.empty(n, dtype=td, device=device)
+    _degrees(A, deg, device)
+    d = torch.clamp(deg, min=1.0).sqrt().reciprocal()
+    maxdeg = int(deg.max().item())   # (synchronises: d is ready for the library's stream)
+    return A.apply_vectors(rows=d, row_op="times", cols=d, col_op="times")[0], maxdeg
+
+
+def label_spreading(rows, cols, n=None, labels=None, *, alpha=0.99, max_iter=30, dtype=np.float64, ctx=None):
+    """Zhou et al.'s learning with local and global consistency on the undirected simple graph with edges (rows[e], cols[e])
+    on vertices [0, n) (any direction, duplicates and self loops dropped), as ``networkx``'s
+    ``node_classification.local_and_global_consistency`` iterates it: S = D^-1/2 A D^-1/2 (a degree of 0 counts as 1), Y0 the
+    n x c indicator of ``labels`` (a dict vertex -> class, or n class ids with a negative id for "unlabelled"; the classes in
+    ascending order are the columns), F = 0, and ``max_iter`` times  F <- alpha S.mxd(F) + (1 - alpha) Y0.  The matrix step is
+    ONE ``osp_csr_mxd`` per iteration, every other operation is torch's on n x c tensors; nothing synchronises inside the loop
+    but the call itself.
+
+    Returns (F numpy (n, c) of ``dtype``, predicted: a list of n classes -- the class of each row's largest entry, the first
+    on a tie -- and info): info = iterations, classes, nnz, max_degree, ms_mxd (a list: device time per iteration),
+    launches.  n == 0 and a graph without edges launch nothing (F is then (1 - alpha) Y0 after the first step)."""
+    if labels is None:
+        raise ValueError("labels is required")
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("alpha must lie in (0, 1)")
+    ctx, device, dtype, n, A = _pattern_result(rows, cols, n, False, dtype, ctx)
+    try:
+        verts, column, classes = _check_labels(labels, n)
+    except Exception:
+        if A is not None:
+            A.close()
+        raise
+    info = {"iterations": 0, "classes": classes, "nnz": 0, "max_degree": 0, "ms_mxd": [], "launches": 0}
+    td = _torch_dtype(dtype)
+    if A is None:
+        F = np.zeros((n, len(classes)), dtype)
+        if max_iter > 0:
+            F[verts, column] = dtype(1.0 - alpha)
+        info["iterations"] = max(int(max_iter), 0)
+        return F, [classes[i] for i in F.argmax(axis=1)], info
+    S = None
+    try:
+        info["nnz"] = A.nnz
+        S, info["max_degree"] = _normalised(A, device, td)
+        base = torch.zeros((n, len(classes)), dtype=td, device=device)
+        base[torch.as_tensor(verts, device=device), torch.as_tensor(column, device=device)] = 1.0 - alpha
+        F = torch.zeros_like(base)
+        Z = torch.empty_like(base)
+        for _ in range(max_iter):
+            torch.cuda.synchronize(device)   # the library works on its own stream
+            _, st = S.mxd(F, out=Z)
+            F = alpha * Z + base
+            info["iterations"] += 1
+            info["ms_mxd"].append(st["ms_total"])
+            info["launches"] += st["launches"]
+        out = F.cpu().numpy()
+        return out, [classes[i] for i in out.argmax(axis=1)], info
+    finally:
+        torch.cuda.synchronize(device)
+        A.close()
+        if S is not None:
+            S.close()
+
+
+def propagate_features(rows, cols, n=None, X=None, hops=2, *, self_loops=True, dtype=np.float64, ctx=None):
+    """The SGC / GCN aggregation  A^^hops X  of the n x k feature matrix ``X`` (an array-like or a torch tensor) over the
+    undirected simple graph with edges (rows[e], cols[e]) on vertices [0, n):  A^ = D~^-1/2 (A + I) D~^-1/2  with D~ the row
+    counts of A + I (``self_loops=True``, Kipf and Welling's renormalisation), or  D^-1/2 A D^-1/2  with a degree of 0
+    counting as 1 (``self_loops=False``).  A + I is a ``build`` of the identity and a ``union``; the normalisation is
+    ``reduce("rows", "count")`` and ONE ``apply_vectors``; every hop is ONE ``osp_csr_mxd`` that overwrites its iterate.
+
+    Returns (numpy (n, k) of ``dtype``, info): info = hops, nnz (of the matrix that is applied), max_degree (its largest row
+    count), ms_mxd (a list: device time per hop), launches.  n == 0 launches nothing; neither does an edgeless graph
+    without self loops (the result is 0 once hops >= 1)."""
+    if X is None:
+        raise ValueError("X is required")
+    if hops < 0:
+        raise ValueError("hops must be at least 0")
+    ctx, device, dtype, n, A = _pattern_result(rows, cols, n, False, dtype, ctx)
+    td = _torch_dtype(dtype)
+    H = S = At = eye = None
+    info = {"hops": int(hops), "nnz": 0, "max_degree": 0, "ms_mxd": [], "launches": 0}
+    try:
+        H = (X.to(device=device, dtype=td) if torch.is_tensor(X) else torch.as_tensor(np.asarray(X, dtype), device=device)).contiguous().clone()
+        if H.dim() != 2 or H.shape[0] != n:
+            raise ValueError(f"X must have shape ({n}, k)")
+        if n == 0 or H.shape[1] == 0 or hops == 0:
+            return H.cpu().numpy(), info
+        if self_loops:
+            diag = torch.arange(n, dtype=torch.int64, device=device)
+            eye = _build_device(ctx, device, n, n, diag, diag, None, "error", dtype)
+            At = A.union(eye)[0] if A is not None else eye
+        else:
+            At = A
+        if At is None:   # (no edge and no self loop: the matrix is 0)
+            return np.zeros(tuple(H.shape), dtype), info
+        info["nnz"] = At.nnz
+        S, info["max_degree"] = _normalised(At, device, td)
+        for _ in range(hops):
+            torch.cuda.synchronize(device)   # the library works on its own stream
+            _, st = S.mxd(H, out=H)
+            info["ms_mxd"].append(st["ms_total"])
+            info["launches"] += st["launches"]
+        return H.cpu().numpy(), info
+    finally:
+        torch.cuda.synchronize(device)
+        for r in {id(r): r for r in (A, eye, At, S) if r is not None}.values():
+            r.close()

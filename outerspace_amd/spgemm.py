@@ -352,6 +352,82 @@ class CsrResult:
         del keep_x, buf
         return ret, stats.as_dict()
 
+    def _matrix_arg(self, v, rows, k, space, what):
+        """A dense row-major ``rows`` x ``k`` argument of ``mxd``: (pointer, keep-alive), under ``_vector_arg``'s conventions.
+        A device address carries no shape: the caller vouches for it."""
+        dtype = self.dtype
+        if space == "host":
+            a = np.ascontiguousarray(v, dtype)
+            if a.shape != (rows, k):
+                raise OspError(_lib.ERR_ARG, f"{what} must have shape ({rows}, {k}) (got {a.shape})")
+            a = a if a.size else np.zeros(1, dtype)   # (never a null pointer)
+            return C.c_void_p(a.ctypes.data), a
+        if hasattr(v, "data_ptr"):
+            if (tuple(v.shape) != (rows, k) or v.element_size() != np.dtype(dtype).itemsize or not v.is_floating_point()
+                    or not v.is_contiguous()):
+                raise OspError(_lib.ERR_ARG, f"{what} must be a contiguous ({rows}, {k}) tensor of {np.dtype(dtype)}")
+            if v.numel() == 0:
+                a = np.zeros(1, dtype)
+                return C.c_void_p(a.ctypes.data), a
+            return C.c_void_p(v.data_ptr()), v
+        return C.c_void_p(int(v)), None
+
+    def mxd(self, X, add="plus", mul="times", out=None, space="device", k=None):
+        """This CSR (M x N) times the dense matrix ``X`` (N x k, row-major, contiguous) under the semiring ``(add, mul)``
+        (``osp_csr_mxd``): column c of the M x k result equals ``mxv(X[:, c], add, mul)`` BIT FOR BIT, in one pass over this
+        result per 64 columns instead of k.  ``add`` is ``"plus" "min" "max"``, ``mul`` is ``"times" "plus" "min" "max"
+        "first" "second"``; ``"first"`` reads no ``X`` (which may be None: then ``k`` names the number of columns),
+        ``"second"`` no value of this result.  An empty row gives +0.0, +inf, -inf.  ``X``: a 2-D torch tensor or a device
+        address (``space="device"``; an address carries no shape, so ``k`` is needed) or an array-like (``space="host"``).
+        ``out=None``: returns (torch tensor (M, k) on the context's device, stats dict), or (numpy array, stats dict) with
+        ``space="host"``; ``out`` a device address or torch tensor of shape (M, k) (a numpy array of this dtype with
+        ``space="host"``): fills and returns it.  ``out is X`` is allowed on a square result.  Stats: nnz_in, nnz_out, cols,
+        long_segments, lanes_per_row, launches, ms_total."""
+        if add not in _lib.MXV_ADD_OPS:
+            raise ValueError(f"add must be one of {' '.join(_lib.MXV_ADD_OPS)} (got {add!r})")
+        if mul not in _lib.MXM_MUL_OPS:
+            raise ValueError(f"mul must be one of {' '.join(_lib.MXM_MUL_OPS)} (got {mul!r})")
+        if space not in ("device", "host"):
+            raise ValueError('space must be "device" or "host"')
+        M, N = self.shape
+        if X is None and mul != "first":
+            raise OspError(_lib.ERR_ARG, 'X may be None only when mul is "first"')
+        if k is None:
+            shape = None if X is None else tuple(X.shape) if hasattr(X, "shape") else np.shape(X) if space == "host" else None
+            if shape is None or len(shape) != 2:
+                raise OspError(_lib.ERR_ARG, "X must be 2-D (N x k); with X None or a device address, pass k")
+            k = shape[1]
+        k = int(k)
+        if not 0 <= k <= _lib.MXD_MAX_COLS:
+            raise OspError(_lib.ERR_ARG, f"k must lie in [0, {_lib.MXD_MAX_COLS}] (got {k})")
+        xp, keep_x = (None, None) if X is None or mul == "first" else self._matrix_arg(X, N, k, space, "X")
+        if out is None and space == "host":
+            ret = np.empty((M, k), self.dtype)
+            buf = ret if ret.size else np.empty(1, self.dtype)   # (never a null pointer)
+            yp = C.c_void_p(buf.ctypes.data)
+        elif out is None:
+            import torch
+            buf = torch.empty(max(M * k, 1), dtype=torch.float32 if self.dtype == np.float32 else torch.float64,
+                              device=f"cuda:{self._ctx.device}")
+            ret = buf[:M * k].view(M, k)
+            yp = C.c_void_p(buf.data_ptr())
+        elif space == "host":
+            if not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.shape == (M, k) and out.flags.c_contiguous):
+                raise OspError(_lib.ERR_ARG, f"out must be a contiguous ({M}, {k}) numpy array of {np.dtype(self.dtype)}")
+            ret = out
+            buf = out if out.size else np.empty(1, self.dtype)
+            yp = C.c_void_p(buf.ctypes.data)
+        else:
+            yp, buf = self._matrix_arg(out, M, k, "device", "out")
+            ret = out
+        sr = _lib.Semiring()
+        sr.add, sr.mul = _lib.MXV_ADD_OPS[add], _lib.MXM_MUL_OPS[mul]
+        stats = _lib.MxdStats()
+        _lib.check(_lib.lib().osp_csr_mxd(self._h, C.byref(sr), xp, k, yp, _lib.OSP_HOST if space == "host" else _lib.OSP_DEVICE,
+                                          C.byref(stats)))
+        del keep_x, buf
+        return ret, stats.as_dict()
+
     def apply_vectors(self, rows=None, row_op=None, cols=None, col_op=None, space="device"):
         """This CSR's pattern with every value ``col_op(row_op(c, rows[i]), cols[j])`` as a new CSR result on the device
         (``osp_csr_apply_vectors``).  Each op is ``"plus" "times" "minus" "div" "min" "max" "second"`` -- one IEEE operation
