@@ -26,13 +26,20 @@ class OspError(RuntimeError):
         self.status = status
 
 
-class Config(C.Structure):
+class _Stats(C.Structure):
+    """Base of every stats, info and descriptor struct: ``as_dict`` is the fields by name, without the ABI's ``reserved``."""
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+class Config(_Stats):
     _fields_ = [("validate", C.c_int), ("partial_capacity", C.c_uint64), ("k_begin", C.c_uint64),
                 ("k_end", C.c_uint64), ("row_shard_index", C.c_int), ("row_shard_count", C.c_int), ("algorithm", C.c_int),
                 ("reserved", C.c_int * 5)]
 
 
-class ResultInfo(C.Structure):
+class ResultInfo(_Stats):
     _fields_ = [("M", C.c_uint64), ("K", C.c_uint64), ("N", C.c_uint64),
                 ("row_begin", C.c_uint64), ("row_end", C.c_uint64),
                 ("nnz_a", C.c_uint64), ("nnz_b", C.c_uint64), ("nnz_c", C.c_uint64),
@@ -53,86 +60,63 @@ class ResultInfo(C.Structure):
                 ("gathered_short_partials", C.c_uint64), ("ms_expand_kernel", C.c_float), ("expand_launches", C.c_uint32),
                 ("expand_partials", C.c_uint64)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
-
-class Panel(C.Structure):
+class Panel(_Stats):
     """osp_panel_t: one finished row panel of a streamed product (device pointers)."""
     _fields_ = [("row_begin", C.c_uint64), ("row_end", C.c_uint64), ("nnz", C.c_uint64),
                 ("rowptr", C.c_void_p), ("colidx", C.c_void_p), ("vals", C.c_void_p),
                 ("index", C.c_uint32), ("count", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
-class Conv2dGeometry(C.Structure):
+class Conv2dGeometry(_Stats):
     """osp_conv2d_geometry_t"""
     _fields_ = [("kh", C.c_uint32), ("kw", C.c_uint32), ("stride_h", C.c_uint32), ("stride_w", C.c_uint32),
                 ("pad_h", C.c_uint32), ("pad_w", C.c_uint32), ("dil_h", C.c_uint32), ("dil_w", C.c_uint32),
                 ("reserved", C.c_uint32 * 8)]
 
 
-class MclStep(C.Structure):
+class MclStep(_Stats):
     """osp_mcl_step_t"""
     _fields_ = [("power", C.c_double), ("threshold", C.c_double), ("max_per_row", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
 
-class MclStats(C.Structure):
+class MclStats(_Stats):
     """osp_mcl_stats_t"""
     _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("rows_capped", C.c_uint64), ("rows_rescued", C.c_uint64),
                 ("rows_long", C.c_uint64), ("chaos", C.c_double), ("ms_total", C.c_float), ("ms_select_kernel", C.c_float),
                 ("launches", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
-
-
-class ApplyMaskStats(C.Structure):
+class ApplyMaskStats(_Stats):
     """osp_apply_mask_stats_t"""
     _fields_ = [("nnz_in", C.c_uint64), ("nnz_mask", C.c_uint64), ("nnz_out", C.c_uint64), ("ms_total", C.c_float),
                 ("launches", C.c_uint32), ("reserved", C.c_uint32 * 6)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
-
-
 SELECT_OPS = {"lt": 0, "le": 1, "gt": 2, "ge": 3, "eq": 4, "ne": 5, "tril": 6, "triu": 7, "diag": 8, "offdiag": 9}  # osp_select_op_t
 
 
-class Select(C.Structure):
+class Select(_Stats):
     """osp_select_t"""
     _fields_ = [("op", C.c_int32), ("fill", C.c_int32), ("threshold", C.c_double), ("diag", C.c_int64), ("fill_value", C.c_double),
                 ("reserved", C.c_uint32 * 8)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
-
-
-class SelectStats(C.Structure):
+class SelectStats(_Stats):
     """osp_select_stats_t"""
     _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("ms_total", C.c_float), ("launches", C.c_uint32),
                 ("reserved", C.c_uint32 * 6)]
-
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
-
 
 EWISE_MODES = {"union": 0, "intersect": 1}  # osp_ewise_mode_t
 EWISE_OPS = {"plus": 0, "times": 1, "min": 2, "max": 3, "first": 4, "second": 5, "minus": 6, "div": 7}  # osp_ewise_op_t
 
 
-class Ewise(C.Structure):
+class Ewise(_Stats):
     """osp_ewise_t"""
     _fields_ = [("mode", C.c_int32), ("op", C.c_int32), ("reserved", C.c_uint32 * 8)]
 
 
-class EwiseStats(C.Structure):
+class EwiseStats(_Stats):
     """osp_ewise_stats_t"""
     _fields_ = [("nnz_a", C.c_uint64), ("nnz_b", C.c_uint64), ("nnz_both", C.c_uint64), ("nnz_out", C.c_uint64),
                 ("ms_total", C.c_float), ("launches", C.c_uint32), ("reserved", C.c_uint32 * 6)]
-
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
-
 
 AXES = {"rows": 0, "cols": 1}  # osp_axis_t
 REDUCE_OPS = {"plus": 0, "min": 1, "max": 2, "count": 3}  # osp_reduce_op_t
@@ -141,121 +125,89 @@ VECTOR_NONE = -1  # OSP_VECTOR_NONE
 VECTOR_APPLY_OPS = {name: v for name, v in EWISE_OPS.items() if name != "first"}
 
 
-class VectorApply(C.Structure):
+class VectorApply(_Stats):
     """osp_vector_apply_t"""
     _fields_ = [("row_op", C.c_int32), ("col_op", C.c_int32), ("reserved", C.c_uint32 * 8)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
-
-
-class VectorStats(C.Structure):
+class VectorStats(_Stats):
     """osp_vector_stats_t"""
     _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("long_segments", C.c_uint64), ("ms_total", C.c_float),
                 ("launches", C.c_uint32), ("reserved", C.c_uint32 * 6)]
-
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
-
 
 # the operators osp_semiring_t takes (osp_ewise_op_t values)
 MXM_ADD_OPS = {name: EWISE_OPS[name] for name in ("plus", "min", "max", "first")}
 MXM_MUL_OPS = {name: EWISE_OPS[name] for name in ("times", "plus", "min", "max", "first", "second")}
 
 
-class Semiring(C.Structure):
+class Semiring(_Stats):
     """osp_semiring_t"""
     _fields_ = [("add", C.c_int32), ("mul", C.c_int32), ("reserved", C.c_uint32 * 8)]
 
 
-class MxmStats(C.Structure):
+class MxmStats(_Stats):
     """osp_mxm_stats_t"""
     _fields_ = [("nnz_a", C.c_uint64), ("nnz_b", C.c_uint64), ("products", C.c_uint64), ("nnz_out", C.c_uint64),
                 ("short_rows", C.c_uint64), ("long_rows", C.c_uint64), ("batches", C.c_uint32), ("launches", C.c_uint32),
                 ("ms_total", C.c_float), ("reserved", C.c_uint32 * 7)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
-
-
 # the add operators osp_csr_mxv takes: the value operators of osp_csr_reduce (mul: MXM_MUL_OPS)
 MXV_ADD_OPS = {name: EWISE_OPS[name] for name in ("plus", "min", "max")}
 
 
-class MxvStats(C.Structure):
+class MxvStats(_Stats):
     """osp_mxv_stats_t"""
     _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("long_segments", C.c_uint64), ("group", C.c_uint32),
                 ("launches", C.c_uint32), ("ms_total", C.c_float), ("reserved", C.c_uint32 * 7)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
-
-
 MXD_MAX_COLS = 65536   # OSP_MXD_MAX_COLS
 
 
-class MxdStats(C.Structure):
+class MxdStats(_Stats):
     """osp_mxd_stats_t"""
     _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("cols", C.c_uint64), ("long_segments", C.c_uint64),
                 ("lanes_per_row", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float), ("reserved", C.c_uint32 * 7)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
-
-
-class Transpose(C.Structure):
+class Transpose(_Stats):
     """osp_transpose_t"""
     _fields_ = [("reserved", C.c_uint32 * 8)]
 
 
-class TransposeStats(C.Structure):
+class TransposeStats(_Stats):
     """osp_transpose_stats_t"""
     _fields_ = [("nnz", C.c_uint64), ("path", C.c_uint32), ("passes", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float),
                 ("reserved", C.c_uint32 * 6)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
-
-
-class Extract(C.Structure):
+class Extract(_Stats):
     """osp_extract_t"""
     _fields_ = [("rows", C.c_void_p), ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("n_cols", C.c_uint64), ("space", C.c_int32),
                 ("reserved", C.c_uint32 * 7)]
 
 
-class ExtractStats(C.Structure):
+class ExtractStats(_Stats):
     """osp_extract_stats_t"""
     _fields_ = [("nnz_in", C.c_uint64), ("nnz_gathered", C.c_uint64), ("nnz_out", C.c_uint64), ("ms_total", C.c_float),
                 ("launches", C.c_uint32), ("readbacks", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
-
-
 DUP_OPS = {"error": 0, "plus": 1, "min": 2, "max": 3, "first": 4, "last": 5, "count": 6}  # osp_dup_op_t
 
 
-class Build(C.Structure):
+class Build(_Stats):
     """osp_build_t"""
     _fields_ = [("M", C.c_uint64), ("N", C.c_uint64), ("nnz", C.c_uint64), ("rows", C.c_void_p), ("cols", C.c_void_p), ("vals", C.c_void_p),
                 ("dtype", C.c_int32), ("space", C.c_int32), ("dup", C.c_int32), ("reserved", C.c_uint32 * 7)]
 
 
-class BuildStats(C.Structure):
+class BuildStats(_Stats):
     """osp_build_stats_t"""
     _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("long_runs", C.c_uint64), ("ms_total", C.c_float),
                 ("launches", C.c_uint32), ("readbacks", C.c_uint32), ("reserved", C.c_uint32 * 5)]
-
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
-
 
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
 
 
-class MultiRankInfo(C.Structure):
+class MultiRankInfo(_Stats):
     """osp_multi_rank_info_t"""
     _fields_ = [("device", C.c_int), ("k_begin", C.c_uint64), ("k_end", C.c_uint64), ("row_begin", C.c_uint64), ("row_end", C.c_uint64),
                 ("partials_local", C.c_uint64), ("records_received", C.c_uint64), ("bytes_sent", C.c_uint64), ("nnz_c", C.c_uint64),
@@ -264,7 +216,7 @@ class MultiRankInfo(C.Structure):
                 ("max_copies_in_flight", C.c_int), ("ms_exchange", C.c_float)]
 
 
-class MultiInfo(C.Structure):
+class MultiInfo(_Stats):
     """osp_multi_info_t"""
     _fields_ = [("nranks", C.c_int), ("subpanels", C.c_int), ("M", C.c_uint64), ("K", C.c_uint64), ("N", C.c_uint64),
                 ("nnz_c", C.c_uint64), ("partials", C.c_uint64), ("bytes_exchanged", C.c_uint64), ("ms_total", C.c_float),

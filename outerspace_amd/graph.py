@@ -23,11 +23,74 @@ import numpy as np
 import torch
 
 from . import spgemm as _S
+from .spgemm import _torch_dtype
 
 
+# ---- what the functions below share ------------------------------------------------------------------------
 def _as_index(x, device):
     t = torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x)
     return t.to(device=device, dtype=torch.int64)
+
+
+def _edges(rows, cols, n, device, weights=None, wdtype=torch.float64):
+    """The one check of an edge list: ``rows`` and ``cols`` as int64 tensors on ``device`` (default: the edges' own, the
+    CPU for array-likes), one-dimensional and of one length; ``n`` inferred as the largest id + 1 when None, every id in
+    [0, n); ``weights``, when given, one value per edge as a tensor of ``wdtype``.  Returns (device, n, r, c, w), w None
+    without weights."""
+    device = torch.device(device) if device is not None else (rows.device if torch.is_tensor(rows) else torch.device("cpu"))
+    r, c = _as_index(rows, device), _as_index(cols, device)
+    if r.shape != c.shape or r.dim() != 1:
+        raise ValueError("rows and cols must be lists of the same length")
+    if n is None:
+        n = int(torch.maximum(r.max(), c.max()).item()) + 1 if r.numel() else 0
+    n = int(n)
+    if r.numel() and (int(torch.minimum(r.min(), c.min()).item()) < 0 or int(torch.maximum(r.max(), c.max()).item()) >= n):
+        raise ValueError(f"vertex ids must lie in [0, {n})")
+    w = None
+    if weights is not None:
+        ndt = np.float32 if wdtype == torch.float32 else np.float64
+        w = torch.as_tensor(np.asarray(weights, ndt) if not torch.is_tensor(weights) else weights).to(device=device, dtype=wdtype)
+        if w.shape != r.shape:
+            raise ValueError("weights must have one entry per edge")
+    return device, n, r, c, w
+
+
+def _rowptr(keys, n, device):
+    """The row pointers of n rows from sorted keys ``row * n + col``."""
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    if n:
+        rowptr[1:] = torch.cumsum(torch.bincount(keys // n, minlength=n), 0)
+    return rowptr
+
+
+def _value_dtype(dtype):
+    dtype = np.dtype(dtype).type
+    if dtype not in (np.float32, np.float64):
+        raise TypeError("dtype must be float32 or float64")
+    return dtype
+
+
+def _setup(dtype, ctx):
+    """The context first (without a GPU this is where the callers fail), its torch device, the value dtype checked.
+    Returns (ctx, device, dtype)."""
+    ctx = ctx or _S.default_context()
+    return ctx, torch.device("cuda", ctx.device), _value_dtype(dtype)
+
+
+def _csr_result(ctx, dtype, M, N, rowptr, cols, vals, device, sync=True):
+    """Non-empty CSR arrays (torch, on the device: int64, int32, ``dtype``) as a library result: the merge of ONE part is the
+    part itself.  ``sync=False``: the caller has synchronised since the arrays were made."""
+    if sync:
+        torch.cuda.synchronize(device)   # the library works on its own stream
+    return ctx.merge_csr_parts_device(dtype, M, N, [(rowptr.data_ptr(), cols.data_ptr(), vals.data_ptr())])
+
+
+def _close_all(device, results):
+    """Close the results (None allowed) once nothing torch holds of their arrays is in flight."""
+    torch.cuda.synchronize(device)
+    for r in results:
+        if r is not None:
+            r.close()
 
 
 def oriented_adjacency(rows, cols, n=None, device=None):
@@ -35,15 +98,7 @@ def oriented_adjacency(rows, cols, n=None, device=None):
     relabelled by their rank in (degree, id) order, every undirected edge {u, v} becomes one entry L[rank u, rank v] with
     rank u < rank v.  Returns (n, rowptr, colidx, colptr, rowidx) as int64 tensors on `device` (default: the edges'):
     L in CSR and the same L in CSC, indices ascending inside every row / column."""
-    device = torch.device(device) if device is not None else (rows.device if torch.is_tensor(rows) else torch.device("cpu"))
-    r, c = _as_index(rows, device), _as_index(cols, device)
-    if r.shape != c.shape:
-        raise ValueError("rows and cols must have the same length")
-    if n is None:
-        n = int(torch.maximum(r.max(), c.max()).item()) + 1 if r.numel() else 0
-    n = int(n)
-    if r.numel() and (int(torch.minimum(r.min(), c.min()).item()) < 0 or int(torch.maximum(r.max(), c.max()).item()) >= n):
-        raise ValueError(f"vertex ids must lie in [0, {n})")
+    device, n, r, c, _ = _edges(rows, cols, n, device)
     keep = r != c
     r, c = r[keep], c[keep]
     # symmetrise and deduplicate: every undirected edge once per direction
@@ -57,12 +112,7 @@ def oriented_adjacency(rows, cols, n=None, device=None):
     src, dst = ru[fwd], rv[fwd]
     csr = torch.sort(src * n + dst).values
     csc = torch.sort(dst * n + src).values
-    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
-    colptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
-    if n:
-        rowptr[1:] = torch.cumsum(torch.bincount(csr // n, minlength=n), 0)
-        colptr[1:] = torch.cumsum(torch.bincount(csc // n, minlength=n), 0)
-    return n, rowptr, csr % n, colptr, csc % n
+    return n, _rowptr(csr, n, device), csr % n, _rowptr(csc, n, device), csc % n
 
 
 def triangle_count(rows, cols, n=None, ctx=None):
@@ -91,22 +141,14 @@ def triangle_count(rows, cols, n=None, ctx=None):
     return int(total)
 
 
-def _undirected_keys(rows, cols, n, device):
+def _undirected_keys(rows, cols, n, device, weights=None):
     """What ``walk_pattern`` and ``symmetric_adjacency`` share: the edge list checked, self loops dropped, every remaining
-    edge in both directions.  Returns (device, n, keep, both): ``keep`` marks the input edges that are no self loops, ``both``
-    holds the keys u * n + v of the kept edges followed by those of their reversals (duplicates still in)."""
-    device = torch.device(device) if device is not None else (rows.device if torch.is_tensor(rows) else torch.device("cpu"))
-    r, c = _as_index(rows, device), _as_index(cols, device)
-    if r.shape != c.shape:
-        raise ValueError("rows and cols must have the same length")
-    if n is None:
-        n = int(torch.maximum(r.max(), c.max()).item()) + 1 if r.numel() else 0
-    n = int(n)
-    if r.numel() and (int(torch.minimum(r.min(), c.min()).item()) < 0 or int(torch.maximum(r.max(), c.max()).item()) >= n):
-        raise ValueError(f"vertex ids must lie in [0, {n})")
+    edge in both directions.  Returns (device, n, both, wt): ``both`` holds the keys u * n + v of the kept edges followed by
+    those of their reversals (duplicates still in), ``wt`` the kept edges' weights (None without weights)."""
+    device, n, r, c, wt = _edges(rows, cols, n, device, weights)
     keep = r != c
     r, c = r[keep], c[keep]
-    return device, n, keep, torch.cat([r * n + c, c * n + r])
+    return device, n, torch.cat([r * n + c, c * n + r]), wt[keep] if wt is not None else None
 
 
 def walk_pattern(rows, cols, n=None, weights=None, device=None):
@@ -115,15 +157,11 @@ def walk_pattern(rows, cols, n=None, weights=None, device=None):
     direction they were given in), and every vertex gets a self loop of weight 1 (weighted: of the largest weight in its
     row, 1 for an isolated vertex).  Returns (n, rowptr int64, colidx int64, vals float64) as tensors on `device`
     (default: the edges'), CSR with ascending columns.  Runs on the CPU as well."""
-    device, n, keep, both = _undirected_keys(rows, cols, n, device)
+    device, n, both, wt = _undirected_keys(rows, cols, n, device, weights)
     if weights is None:
         key = torch.unique(both)
         w = torch.ones(key.numel(), dtype=torch.float64, device=device)
     else:
-        wt = torch.as_tensor(np.asarray(weights, np.float64) if not torch.is_tensor(weights) else weights).to(device=device, dtype=torch.float64)
-        if wt.shape != keep.shape:
-            raise ValueError("weights must have one entry per edge")
-        wt = wt[keep]
         key, inv = torch.unique(both, return_inverse=True)
         w = torch.zeros(key.numel(), dtype=torch.float64, device=device)
         w.scatter_reduce_(0, inv, torch.cat([wt, wt]), reduce="amax", include_self=False)
@@ -134,10 +172,7 @@ def walk_pattern(rows, cols, n=None, weights=None, device=None):
     diag = torch.arange(n, dtype=torch.int64, device=device)
     allkey, order = torch.sort(torch.cat([key, diag * n + diag]))
     vals = torch.cat([w, loop])[order]
-    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
-    if n:
-        rowptr[1:] = torch.cumsum(torch.bincount(allkey // n, minlength=n), 0)
-    return n, rowptr, allkey % n, vals
+    return n, _rowptr(allkey, n, device), allkey % n, vals
 
 
 def _cluster_labels(n, rowptr, colidx):
@@ -170,16 +205,13 @@ def markov_cluster(rows, cols, n=None, *, inflation=2.0, threshold=1e-4, max_per
     ctx = ctx or _S.default_context()
     device = torch.device("cuda", ctx.device)
     dtype = np.dtype(dtype).type
-    tdt = torch.float32 if dtype == np.float32 else torch.float64
     n, rowptr, colidx, vals = walk_pattern(rows, cols, n, weights, device)
     info = {"iterations": 0, "chaos": 0.0, "converged": True, "n_clusters": 0, "nnz_expanded": [], "nnz_kept": [], "ms_product": [],
             "ms_prune": [], "ms_select": [], "rows_capped": [], "rows_long": []}
     if n == 0:
         return np.zeros(0, np.int64), info
-    ci, va = colidx.to(torch.int32), vals.to(tdt)
-    torch.cuda.synchronize(device)   # the library works on its own stream
-    # the pattern as a library CSR result: the merge of ONE part is the part itself
-    pat = ctx.merge_csr_parts_device(dtype, n, n, [(rowptr.data_ptr(), ci.data_ptr(), va.data_ptr())])
+    ci, va = colidx.to(torch.int32), vals.to(_torch_dtype(dtype))
+    pat = _csr_result(ctx, dtype, n, n, rowptr, ci, va, device)
     try:
         T, st = pat.inflate_prune(1.0, 0.0, 0)
     finally:
@@ -223,12 +255,9 @@ def symmetric_adjacency(rows, cols, n=None, device=None):
     allowed): symmetric, every edge once per direction, no self loops, unit values -- ``walk_pattern`` without the loops.
     Returns (n, rowptr int64, colidx int64, vals float64) as tensors on `device` (default: the edges'), CSR with ascending
     columns.  Runs on the CPU as well."""
-    device, n, _, both = _undirected_keys(rows, cols, n, device)
+    device, n, both, _ = _undirected_keys(rows, cols, n, device)
     key = torch.unique(both)
-    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
-    if n:
-        rowptr[1:] = torch.cumsum(torch.bincount(key // n, minlength=n), 0)
-    return n, rowptr, key % n, torch.ones(key.numel(), dtype=torch.float64, device=device)
+    return n, _rowptr(key, n, device), key % n, torch.ones(key.numel(), dtype=torch.float64, device=device)
 
 
 class _Adjacency:
@@ -296,12 +325,11 @@ def _bfs_forward(ctx, device, adj, src, max_levels=None, keep_levels=False, mask
     rp0 = torch.arange(S + 1, dtype=torch.int64, device=device)
     c0, v0 = s_dev.to(torch.int32), torch.ones(S, dtype=torch.float64, device=device)
     torch.cuda.synchronize(device)   # the library works on its own stream
-    # the sources as library CSR results: the merge of ONE part is the part itself.  F = the frontier, V = the visited set
-    part = [(rp0.data_ptr(), c0.data_ptr(), v0.data_ptr())]
+    # the sources as library CSR results, twice after the one synchronisation.  F = the frontier, V = the visited set
     F = V = None
     try:
-        F = ctx.merge_csr_parts_device(np.float64, S, n, part)
-        V = ctx.merge_csr_parts_device(np.float64, S, n, part)
+        F = _csr_result(ctx, np.float64, S, n, rp0, c0, v0, device, sync=False)
+        V = _csr_result(ctx, np.float64, S, n, rp0, c0, v0, device, sync=False)
         if keep_levels:
             levels.append((F, lin0))
         a = _result_as_input(F, device)
@@ -429,9 +457,7 @@ def betweenness_centrality(rows, cols, n=None, sources=None, *, batch=64, ctx=No
             dl[levels[0][1]] = 0.0   # delta_s(s) is not part of the sum
             bc += delta.sum(0)
         finally:
-            torch.cuda.synchronize(device)
-            for res, _ in levels:
-                res.close()
+            _close_all(device, [res for res, _ in levels])
     return bc.cpu().numpy()
 
 
@@ -484,12 +510,11 @@ def personalized_pagerank(rows, cols, n=None, sources=(0,), *, alpha=0.85, tol=1
     c0 = torch.as_tensor(src, device=device).to(torch.int32)
     v0 = torch.full((S,), 1.0 - alpha, dtype=torch.float64, device=device)
     torch.cuda.synchronize(device)   # the library works on its own stream
-    # the sources as library CSR results: the merge of ONE part is the part itself.  F = the series' term, PI = its sum
-    part = [(rp0.data_ptr(), c0.data_ptr(), v0.data_ptr())]
+    # the sources as library CSR results, twice after the one synchronisation.  F = the series' term, PI = its sum
     F = PI = a = None
     try:
-        F = ctx.merge_csr_parts_device(np.float64, S, n, part)
-        PI = ctx.merge_csr_parts_device(np.float64, S, n, part)
+        F = _csr_result(ctx, np.float64, S, n, rp0, c0, v0, device, sync=False)
+        PI = _csr_result(ctx, np.float64, S, n, rp0, c0, v0, device, sync=False)
         for _ in range(K):
             a = _result_as_input(F, device)
             P = ctx.spgemm_coo_device(np.float64, S, n, n, a.nnz, (a.rows.data_ptr(), a.cols.data_ptr(), a.vals.data_ptr()), adj.nnz, b_ptrs)
@@ -518,12 +543,8 @@ def personalized_pagerank(rows, cols, n=None, sources=(0,), *, alpha=0.85, tol=1
         a = _result_as_input(PI, device)
         ppr.view(-1)[a.rows.to(torch.int64)[:a.nnz] * n + a.cols.to(torch.int64)] = a.vals
     finally:
-        torch.cuda.synchronize(device)
         a = None
-        if F is not None:
-            F.close()
-        if PI is not None:
-            PI.close()
+        _close_all(device, (F, PI))
     return ppr.cpu().numpy(), info
 
 
@@ -535,11 +556,7 @@ def _truss_info():
 def _truss_setup(rows, cols, n, dtype, ctx):
     """What the three truss functions share: the context first (without a GPU this is where they fail), the adjacency on
     its device, and the guard of float32's exact range.  Returns (ctx, device, dtype, adj)."""
-    ctx = ctx or _S.default_context()
-    device = torch.device("cuda", ctx.device)
-    dtype = np.dtype(dtype).type
-    if dtype not in (np.float32, np.float64):
-        raise TypeError("dtype must be float32 or float64")
+    ctx, device, dtype = _setup(dtype, ctx)
     adj = _Adjacency(rows, cols, n, device)
     # a support is below the smaller degree of the edge's ends
     if dtype == np.float32 and adj.nnz and int((adj.rowptr[1:] - adj.rowptr[:-1]).max().item()) >= 1 << 24:
@@ -548,11 +565,8 @@ def _truss_setup(rows, cols, n, dtype, ctx):
 
 
 def _adjacency_result(ctx, adj, dtype, device):
-    """A non-empty ``_Adjacency`` as a library CSR result with unit values of ``dtype``: the merge of ONE part is the part
-    itself."""
-    vals = adj.vals.to(torch.float32 if dtype == np.float32 else torch.float64)
-    torch.cuda.synchronize(device)   # the library works on its own stream
-    return ctx.merge_csr_parts_device(dtype, adj.n, adj.n, [(adj.rowptr.data_ptr(), adj.cols.data_ptr(), vals.data_ptr())])
+    """A non-empty ``_Adjacency`` as a library CSR result with unit values of ``dtype``."""
+    return _csr_result(ctx, dtype, adj.n, adj.n, adj.rowptr, adj.cols, adj.vals.to(_torch_dtype(dtype)), device)
 
 
 def _support_product(ctx, A):
@@ -699,10 +713,6 @@ def truss_decomposition(rows, cols, n=None, *, dtype=np.float64, ctx=None):
 
 
 # ---- k-core, Jaccard similarity, clustering coefficient --------------------------------------------------
-def _torch_dtype(dtype):
-    return torch.float32 if dtype == np.float32 else torch.float64
-
-
 def _degrees(A, deg, device):
     """deg <- the entries per row of the CSR result A (``reduce("rows", "count")``), written on the device into the torch
     vector ``deg`` of A's dtype.  Returns the call's device time."""
@@ -767,8 +777,7 @@ def core_numbers(rows, cols, n=None, *, dtype=np.float64, ctx=None):
             info["k_max"] = k
             k += 1
     finally:
-        torch.cuda.synchronize(device)
-        A.close()
+        _close_all(device, [A])
     return core.cpu().numpy(), info
 
 
@@ -792,8 +801,7 @@ def k_core(rows, cols, n=None, k=1, *, dtype=np.float64, ctx=None):
         A = _peel_level(A, k, deg, device, info)
         u, v, _ = _upper_entries(A)
     finally:
-        torch.cuda.synchronize(device)
-        A.close()
+        _close_all(device, [A])
     return u, v, info
 
 
@@ -828,9 +836,7 @@ def jaccard_similarity(rows, cols, n=None, *, dtype=np.float64, ctx=None):
         held.append(J)
         ju, jv, jval = _upper_entries(J)
     finally:
-        torch.cuda.synchronize(device)
-        for res in held:
-            res.close()
+        _close_all(device, held)
     jaccard = np.zeros(len(u), np.float64)
     jaccard[np.searchsorted(u * adj.n + v, ju * adj.n + jv)] = jval.astype(np.float64)   # (the product has no entry where it is 0)
     return u, v, jaccard
@@ -858,9 +864,7 @@ def local_clustering(rows, cols, n=None, *, dtype=np.float64, ctx=None):
         held.append(S)
         S.reduce("rows", "plus", out=t)
     finally:
-        torch.cuda.synchronize(device)
-        for res in held:
-            res.close()
+        _close_all(device, held)
     # the one division, in float64 on the host: numpy's is the IEEE division whatever the device's
     d64, t64 = deg.cpu().numpy().astype(np.float64), t.cpu().numpy().astype(np.float64)
     cc = np.zeros(adj.n, np.float64)
@@ -879,21 +883,9 @@ def weighted_adjacency(rows, cols, n=None, weights=None, *, directed=False, keep
     columns.  Runs on the CPU as well."""
     if keep not in ("min", "max"):
         raise ValueError('keep must be "min" or "max"')
-    device = torch.device(device) if device is not None else (rows.device if torch.is_tensor(rows) else torch.device("cpu"))
-    r, c = _as_index(rows, device), _as_index(cols, device)
-    if r.shape != c.shape:
-        raise ValueError("rows and cols must have the same length")
-    if n is None:
-        n = int(torch.maximum(r.max(), c.max()).item()) + 1 if r.numel() else 0
-    n = int(n)
-    if r.numel() and (int(torch.minimum(r.min(), c.min()).item()) < 0 or int(torch.maximum(r.max(), c.max()).item()) >= n):
-        raise ValueError(f"vertex ids must lie in [0, {n})")
-    if weights is None:
+    device, n, r, c, wt = _edges(rows, cols, n, device, weights)
+    if wt is None:
         wt = torch.ones(r.numel(), dtype=torch.float64, device=device)
-    else:
-        wt = torch.as_tensor(np.asarray(weights, np.float64) if not torch.is_tensor(weights) else weights).to(device=device, dtype=torch.float64)
-        if wt.shape != r.shape:
-            raise ValueError("weights must have one entry per edge")
     loop = r != c
     r, c, wt = r[loop], c[loop], wt[loop]
     keys = r * n + c
@@ -903,10 +895,17 @@ def weighted_adjacency(rows, cols, n=None, weights=None, *, directed=False, keep
     w = torch.zeros(key.numel(), dtype=torch.float64, device=device)
     if key.numel():
         w.scatter_reduce_(0, inv, wt, reduce="amin" if keep == "min" else "amax", include_self=False)
-    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
-    if n:
-        rowptr[1:] = torch.cumsum(torch.bincount(key // n, minlength=n), 0)
-    return n, rowptr, key % n, w
+    return n, _rowptr(key, n, device), key % n, w
+
+
+def directed_pattern(rows, cols, n=None, device=None):
+    """The deduplicated 0/1 adjacency matrix of the DIRECTED graph of an edge list: every edge (rows[e], cols[e]) as given,
+    one entry however often it is listed, self loops kept, an edge given in both directions as two entries.  Returns
+    (n, rowptr int64, colidx int64, vals float64) as tensors on `device` (default: the edges'), CSR with ascending columns.
+    Runs on the CPU as well."""
+    device, n, r, c, _ = _edges(rows, cols, n, device)
+    key = torch.unique(r * n + c)
+    return n, _rowptr(key, n, device), key % n, torch.ones(key.numel(), dtype=torch.float64, device=device)
 
 
 def _check_weights(weights):
@@ -920,20 +919,11 @@ def _check_weights(weights):
 def _paths_setup(rows, cols, n, weights, directed, keep, dtype, ctx):
     """What the path functions share: the checks of the arguments, the context (without a GPU this is where they fail), and
     the weighted adjacency on its device.  Returns (ctx, device, dtype, n, rowptr, cols int32, vals of dtype)."""
-    dtype = np.dtype(dtype).type
-    if dtype not in (np.float32, np.float64):
-        raise TypeError("dtype must be float32 or float64")
+    _value_dtype(dtype)   # (these two before the context: a bad argument is a Python error without a GPU as well)
     _check_weights(weights)
-    ctx = ctx or _S.default_context()
-    device = torch.device("cuda", ctx.device)
+    ctx, device, dtype = _setup(dtype, ctx)
     n, rowptr, colidx, vals = weighted_adjacency(rows, cols, n, weights, directed=directed, keep=keep, device=device)
     return ctx, device, dtype, n, rowptr, colidx.to(torch.int32), vals.to(_torch_dtype(dtype))
-
-
-def _csr_result(ctx, dtype, M, N, rowptr, cols, vals, device):
-    """Non-empty CSR arrays (torch, on the device) as a library result: the merge of ONE part is the part itself."""
-    torch.cuda.synchronize(device)   # the library works on its own stream
-    return ctx.merge_csr_parts_device(dtype, M, N, [(rowptr.data_ptr(), cols.data_ptr(), vals.data_ptr())])
 
 
 def _paths_info():
@@ -1011,10 +1001,7 @@ def _semiring_paths(rows, cols, n, sources, weights, directed, max_iter, dtype, 
         torch.cuda.synchronize(device)   # torch holds views of D's arrays: nothing of it is in flight when they go back to the pool
         del a
     finally:
-        torch.cuda.synchronize(device)
-        for r in (W, D, F):
-            if r is not None:
-                r.close()
+        _close_all(device, (W, D, F))
     return out.cpu().numpy(), info
 
 
@@ -1146,37 +1133,21 @@ def strongly_connected(rows, cols, n=None, sources=(0,), *, max_iter=None, ctx=N
         torch.cuda.synchronize(device)   # torch holds views of the result's arrays: nothing of it is in flight when they go back to the pool
         del a
     finally:
-        torch.cuda.synchronize(device)
-        for r in held:
-            r.close()
+        _close_all(device, held)
     return out.cpu().numpy(), info
 
 
 def _directed_pattern_result(rows, cols, n, dtype, ctx):
-    """The deduplicated directed 0/1 adjacency of an edge list, self loops kept, as a CSR result with unit values of
-    ``dtype`` (the context first: without a GPU this is where the callers fail).  Returns (ctx, A)."""
-    ctx = ctx or _S.default_context()
-    device = torch.device("cuda", ctx.device)
-    dtype = np.dtype(dtype).type
-    if dtype not in (np.float32, np.float64):
-        raise TypeError("dtype must be float32 or float64")
-    r, c = _as_index(rows, device), _as_index(cols, device)
-    if r.shape != c.shape:
-        raise ValueError("rows and cols must have the same length")
-    if n is None:
-        n = int(torch.maximum(r.max(), c.max()).item()) + 1 if r.numel() else 0
-    n = int(n)
-    if r.numel() and (int(torch.minimum(r.min(), c.min()).item()) < 0 or int(torch.maximum(r.max(), c.max()).item()) >= n):
-        raise ValueError(f"vertex ids must lie in [0, {n})")
-    key = torch.unique(r * n + c)
-    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
-    if n and key.numel():
-        rowptr[1:] = torch.cumsum(torch.bincount(key // n, minlength=n), 0)
+    """``directed_pattern`` as a CSR result with unit values of ``dtype`` (the context first: without a GPU this is where the
+    callers fail).  Returns (ctx, A)."""
+    ctx, device, dtype = _setup(dtype, ctx)
+    n, rowptr, colidx, vals = directed_pattern(rows, cols, n, device)
+    nnz = int(colidx.numel())
     # (an edgeless graph: arrays of one unused element, a pointer is never null)
-    ci = (key % n).to(torch.int32) if key.numel() else torch.zeros(1, dtype=torch.int32, device=device)
-    va = torch.ones(max(int(key.numel()), 1), dtype=_torch_dtype(dtype), device=device)
+    ci = colidx.to(torch.int32) if nnz else torch.zeros(1, dtype=torch.int32, device=device)
+    va = vals.to(_torch_dtype(dtype)) if nnz else torch.ones(1, dtype=_torch_dtype(dtype), device=device)
     # a count is at most a vertex's degree
-    if dtype == np.float32 and key.numel() and max(int(torch.bincount(key // n).max().item()), int(torch.bincount(key % n).max().item())) >= 1 << 24:
+    if dtype == np.float32 and nnz and max(int((rowptr[1:] - rowptr[:-1]).max().item()), int(torch.bincount(colidx).max().item())) >= 1 << 24:
         raise ValueError("float32 holds the counts exactly only while the maximum degree is below 2^24: use float64")
     return ctx, _csr_result(ctx, dtype, n, n, rowptr, ci, va, device)
 
@@ -1278,10 +1249,7 @@ def pagerank(rows, cols, n=None, *, alpha=0.85, tol=1e-6, max_iter=100, directed
                 break
         return r.cpu().numpy(), info
     finally:
-        torch.cuda.synchronize(device)
-        A.close()
-        if At is not None and At is not A:
-            At.close()
+        _close_all(device, (A, At))   # (an undirected At is A: closing twice is closing once)
 
 
 def connected_components(rows, cols, n=None, *, dtype=np.float64, ctx=None):
@@ -1321,8 +1289,7 @@ def connected_components(rows, cols, n=None, *, dtype=np.float64, ctx=None):
                 break
         labels = lab.long().cpu().numpy()
     finally:
-        torch.cuda.synchronize(device)
-        A.close()
+        _close_all(device, [A])
     info["components"] = int((labels == np.arange(n)).sum())
     return labels, info
 
@@ -1407,30 +1374,6 @@ def largest_component(rows, cols, n=None, *, dtype=np.float64, ctx=None):
 
 
 # ---- a result from an edge list (osp_csr_build): adjacency, Laplacian, incidence matrix, line graph --------------------------------
-def _edge_list(rows, cols, n, weights, dtype, ctx):
-    """What the builders share: the context first (without a GPU this is where they fail), the checked edge list on its
-    device.  Returns (ctx, device, dtype, n, r, c, w): r, c int64 tensors, w a tensor of ``dtype`` or None."""
-    ctx = ctx or _S.default_context()
-    device = torch.device("cuda", ctx.device)
-    dtype = np.dtype(dtype).type
-    if dtype not in (np.float32, np.float64):
-        raise TypeError("dtype must be float32 or float64")
-    r, c = _as_index(rows, device), _as_index(cols, device)
-    if r.shape != c.shape or r.dim() != 1:
-        raise ValueError("rows and cols must be lists of the same length")
-    if n is None:
-        n = int(torch.maximum(r.max(), c.max()).item()) + 1 if r.numel() else 0
-    n = int(n)
-    if r.numel() and (int(torch.minimum(r.min(), c.min()).item()) < 0 or int(torch.maximum(r.max(), c.max()).item()) >= n):
-        raise ValueError(f"vertex ids must lie in [0, {n})")
-    w = None
-    if weights is not None:
-        w = torch.as_tensor(np.asarray(weights, dtype) if not torch.is_tensor(weights) else weights).to(device=device, dtype=_torch_dtype(dtype))
-        if w.shape != r.shape:
-            raise ValueError("weights must have one entry per edge")
-    return ctx, device, dtype, n, r, c, w
-
-
 def _build_device(ctx, device, n_rows, n_cols, r, c, w, dup, dtype):
     """``ctx.build`` of int64 index tensors (and a value tensor or None) that live on the device."""
     r32, c32 = r.to(torch.int32).contiguous(), c.to(torch.int32).contiguous()   # (the low 32 bits: a uint32 list's bits)
@@ -1445,7 +1388,8 @@ def adjacency_matrix(rows, cols, n=None, weights=None, *, directed=False, loops=
     parallel edges combined by ``dup`` in list order (``Context.build``'s operators; ``"count"`` gives multiplicities).
     ``weights=None`` means 1 for every edge.  Self loops are masked out unless ``loops`` (an undirected loop is then listed
     twice, as every edge is).  An edgeless graph gives an empty n x n result.  The caller closes the result."""
-    ctx, device, dtype, n, r, c, w = _edge_list(rows, cols, n, weights, dtype, ctx)
+    ctx, device, dtype = _setup(dtype, ctx)
+    _, n, r, c, w = _edges(rows, cols, n, device, weights, _torch_dtype(dtype))
     if not loops:
         keep = r != c
         r, c = r[keep], c[keep]
@@ -1461,7 +1405,8 @@ def laplacian(rows, cols, n=None, weights=None, *, dtype=np.float64, ctx=None):
     self loops are dropped, parallel edges add.  ONE ``osp_csr_build`` with ``dup="plus"`` of the four blocks (u, v, -w),
     (v, u, -w), (u, u, w), (v, v, w) concatenated in that order, which fixes every sum's order and with it its bits.  A
     vertex without an edge has an empty row.  The caller closes the result."""
-    ctx, device, dtype, n, r, c, w = _edge_list(rows, cols, n, weights, dtype, ctx)
+    ctx, device, dtype = _setup(dtype, ctx)
+    _, n, r, c, w = _edges(rows, cols, n, device, weights, _torch_dtype(dtype))
     keep = r != c
     u, v = r[keep], c[keep]
     w = w[keep] if w is not None else torch.ones(u.numel(), dtype=_torch_dtype(dtype), device=device)
@@ -1584,10 +1529,7 @@ def label_spreading(rows, cols, n=None, labels=None, *, alpha=0.99, max_iter=30,
         out = F.cpu().numpy()
         return out, [classes[i] for i in out.argmax(axis=1)], info
     finally:
-        torch.cuda.synchronize(device)
-        A.close()
-        if S is not None:
-            S.close()
+        _close_all(device, (A, S))
 
 
 def propagate_features(rows, cols, n=None, X=None, hops=2, *, self_loops=True, dtype=np.float64, ctx=None):
@@ -1631,6 +1573,4 @@ def propagate_features(rows, cols, n=None, X=None, hops=2, *, self_loops=True, d
             info["launches"] += st["launches"]
         return H.cpu().numpy(), info
     finally:
-        torch.cuda.synchronize(device)
-        for r in {id(r): r for r in (A, eye, At, S) if r is not None}.values():
-            r.close()
+        _close_all(device, (A, eye, At, S))   # (At may be A or eye: closing twice is closing once)

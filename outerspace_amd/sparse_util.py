@@ -73,7 +73,7 @@ def _coo_on_device(x, dtype, device):
     if not sp.issparse(x):
         x = sp.csr_matrix(np.asarray(x))
     x = x.tocoo()
-    tdt = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
+    tdt = _S._torch_dtype(dtype)
     return (x.shape[0], x.shape[1], torch.from_numpy(x.row.astype(np.int32)).to(device), torch.from_numpy(x.col.astype(np.int32)).to(device),
             torch.from_numpy(x.data.astype(dtype)).to(device, tdt))
 
@@ -115,7 +115,7 @@ def _result_as_input(res, device):
     from .distributed import _as_tensor
     _, ci, va = res.device_ptrs()
     nnz = res.nnz
-    tdt = torch.float32 if res.dtype == np.float32 else torch.float64
+    tdt = _S._torch_dtype(res.dtype)
     rows = torch.empty(max(nnz, 1), dtype=torch.int32, device=device)
     torch.cuda.synchronize(device)
     if nnz:
@@ -228,7 +228,7 @@ def unfold(x, kernel_size, padding=0, stride=1, dilation=1, ctx=None, dtype=np.f
     K = C * g.kh * g.kw
     torch.cuda.synchronize(device)
     nnz = ctx.im2col_device(dtype, N, C, H, W, act.nnz, _dev_ptrs(act), g)
-    tdt = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
+    tdt = _S._torch_dtype(dtype)
     colptr = torch.empty(K + 1, dtype=torch.int64, device=device)
     rowidx = torch.empty(max(nnz, 1), dtype=torch.int32, device=device)
     vals = torch.empty(max(nnz, 1), dtype=tdt, device=device)

@@ -13,6 +13,7 @@ Mirrors the reference's call surface for this path:
 All numeric work happens in ``libouterspace_spgemm.so`` on the GPU; nothing here computes.
 """
 import ctypes as C
+import math
 import os
 import weakref
 
@@ -30,6 +31,106 @@ def _ptr(a):
 
 def _pair(v):
     return (int(v), int(v)) if np.isscalar(v) else (int(v[0]), int(v[1]))
+
+
+# ---- argument helpers the methods below share ------------------------------------------------------------
+def _enum(table, value, what):
+    """``table[value]``, or the ValueError of a name the table does not hold."""
+    if value not in table:
+        raise ValueError(f"{what} must be one of {' '.join(table)} (got {value!r})")
+    return table[value]
+
+
+def _space(space):
+    """``OSP_HOST`` / ``OSP_DEVICE`` of a ``space`` argument."""
+    if space not in ("device", "host"):
+        raise ValueError('space must be "device" or "host"')
+    return _lib.OSP_HOST if space == "host" else _lib.OSP_DEVICE
+
+
+def _dptrs(ptrs, null=False):
+    """Addresses (ints) as pointer arguments; ``null=True`` passes a zero or absent address as NULL."""
+    return [None if null and not p else C.c_void_p(int(p)) for p in ptrs]
+
+
+def _torch_dtype(dtype):
+    import torch
+    return torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
+
+
+def _call(ctx, name, *args, stats=None, keep=()):
+    """The frame of every entry point that makes a result: ``name(*args, &handle[, &stats])``, ``_lib.check``, the handle
+    wrapped as a ``CsrResult`` of ``ctx``.  Returns the result, or (result, stats dict) when a stats struct is passed.
+    ``keep`` holds the objects the addresses in ``args`` point into: it is an argument so that they outlive the call."""
+    h = C.c_void_p()
+    tail = (C.byref(h),) if stats is None else (C.byref(h), C.byref(stats))
+    _lib.check(getattr(_lib.lib(), name)(*args, *tail))
+    res = CsrResult(ctx, h)
+    return res if stats is None else (res, stats.as_dict())
+
+
+def _dense_arg(v, shape, dtype, space, what, floating=False):
+    """A dense argument of the ``osp_csr_*`` functions that take one -- a vector ``(n,)`` or a row-major matrix ``(rows, k)``
+    -- as (pointer, keep-alive); the pointer is never null.  ``space="host"``: an array-like of that shape, converted to
+    ``dtype``; ``space="device"``: a device address, which carries no shape (the caller vouches for it), or an object with
+    ``data_ptr()`` (a contiguous torch tensor of ``dtype``, floating point when ``floating``: the caller has synchronised
+    its stream)."""
+    if v is None:
+        return None, None
+    vector, size = len(shape) == 1, math.prod(shape)
+    if space == "host" or (vector and size == 0):   # (an empty vector on the device: nothing is read, v is not looked at)
+        a = np.ascontiguousarray(v, dtype) if space == "host" else np.zeros(0, dtype)
+        if a.shape != shape:
+            raise OspError(_lib.ERR_ARG, f"{what} must have {size} entries (got shape {a.shape})" if vector else
+                           f"{what} must have shape ({shape[0]}, {shape[1]}) (got {a.shape})")
+        a = a if a.size else np.zeros(1, dtype)   # (never a null pointer)
+        return C.c_void_p(a.ctypes.data), a
+    if hasattr(v, "data_ptr"):
+        fits = v.numel() == size if vector else tuple(v.shape) == shape
+        if not fits or v.element_size() != np.dtype(dtype).itemsize or (floating and not v.is_floating_point()) or not v.is_contiguous():
+            raise OspError(_lib.ERR_ARG, f"{what} must be a contiguous tensor of {size} values of {np.dtype(dtype)}" if vector else
+                           f"{what} must be a contiguous ({shape[0]}, {shape[1]}) tensor of {np.dtype(dtype)}")
+        if size == 0:
+            a = np.zeros(1, dtype)
+            return C.c_void_p(a.ctypes.data), a
+        return C.c_void_p(v.data_ptr()), v
+    return C.c_void_p(int(v)), None
+
+
+def _u32_list(v, space, what):
+    """An index list of ``extract`` and ``build``: (address, count, keep-alive); the address of an empty list is 0, and what
+    that says is the caller's convention.  ``space="host"``: an array-like of integers in [0, 2^32); ``space="device"``: a
+    torch tensor of 4-byte integers (the caller has synchronised its stream) or an ``(address, count)`` pair."""
+    if space == "host":
+        a = np.atleast_1d(np.asarray(v))
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise OspError(_lib.ERR_ARG, f"{what} must be a one-dimensional list of integers")
+        a = a.astype(np.int64) if a.size else np.zeros(0, np.int64)
+        if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+            raise OspError(_lib.ERR_ARG, f"{what} holds an index outside [0, 2^32)")
+        a = np.ascontiguousarray(a, np.uint32)
+        return (a.ctypes.data if a.size else 0), int(a.size), a
+    if hasattr(v, "data_ptr"):
+        if v.dim() != 1 or v.element_size() != 4 or v.is_floating_point() or not v.is_contiguous():
+            raise OspError(_lib.ERR_ARG, f"{what} must be a contiguous one-dimensional tensor of 4-byte integers")
+        return (v.data_ptr() if v.numel() else 0), int(v.numel()), v
+    return int(v[0]), int(v[1]), None
+
+
+def _index_arg(v, space, what):
+    """An index list of ``extract``: (pointer, count, keep-alive, ascending).  None takes every row / column (a null
+    pointer), so an empty list never passes one.  ``ascending`` says whether the list is strictly ascending -- numpy on the
+    host, one torch comparison on the device -- and is None for a bare address, which nothing here can read."""
+    if v is None:
+        return None, 0, None, True
+    addr, n, keep = _u32_list(v, space, what)
+    if n == 0:   # (nothing is read: any non-null pointer says "an empty list")
+        keep = np.zeros(1, np.uint32)
+        return C.c_void_p(keep.ctypes.data), 0, keep, True
+    if keep is None:
+        return C.c_void_p(addr), n, None, None
+    w = keep if space == "host" else keep.long() & 0xffffffff   # (an int32 tensor holds a uint32 list's bits)
+    return C.c_void_p(addr), n, keep, bool((w[1:] > w[:-1]).all())
 
 
 def conv2d_geometry(kernel_size, stride=1, padding=0, dilation=1):
@@ -95,9 +196,7 @@ class CsrResult:
         b = None if bias is None else np.ascontiguousarray(bias, self.dtype)
         if b is not None and b.shape != (self.shape[1],):
             raise ValueError(f"bias must have {self.shape[1]} entries")
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_csr_bias_relu(self._h, _ptr(b) if b is not None else None, _lib.OSP_HOST, int(bool(relu)), C.byref(h)))
-        return CsrResult(self._ctx, h)
+        return _call(self._ctx, "osp_csr_bias_relu", self._h, _ptr(b) if b is not None else None, _lib.OSP_HOST, int(bool(relu)), keep=b)
 
     def maxpool2d(self, N, H, W, kernel_size, stride=None):
         """MaxPool2d of this CSR read as a "pixel x channel" activation of N images of H x W pixels (row n*H*W + y*W + x):
@@ -106,9 +205,7 @@ class CsrResult:
         defaults to the kernel size, as in torch."""
         kh, kw = _pair(kernel_size)
         sh, sw = _pair(kernel_size if stride is None else stride)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_csr_maxpool2d(self._h, int(N), int(H), int(W), kh, kw, sh, sw, C.byref(h)))
-        return CsrResult(self._ctx, h)
+        return _call(self._ctx, "osp_csr_maxpool2d", self._h, int(N), int(H), int(W), kh, kw, sh, sw)
 
     def inflate_prune(self, power=2.0, threshold=0.0, max_per_row=0, validate=False):
         """One Markov-clustering step on this CSR, row by row, as a new CSR result on the device
@@ -118,10 +215,7 @@ class CsrResult:
         chaos, ms_total, ms_select_kernel, launches.  validate=True refuses negative, NaN and infinite values."""
         step = _lib.MclStep()
         step.power, step.threshold, step.max_per_row = float(power), float(threshold), int(max_per_row)
-        stats = _lib.MclStats()
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_csr_inflate_prune(self._h, C.byref(step), int(bool(validate)), C.byref(h), C.byref(stats)))
-        return CsrResult(self._ctx, h), stats.as_dict()
+        return _call(self._ctx, "osp_csr_inflate_prune", self._h, C.byref(step), int(bool(validate)), stats=_lib.MclStats())
 
     def apply_mask(self, mask, *, complement=False, validate=False, space="device"):
         """The entries of this CSR that are in ``mask`` (``complement=True``: that are NOT in it) as a new CSR result on the
@@ -144,12 +238,8 @@ class CsrResult:
             rp, ci, sp_, keep = C.c_void_p(int(mask[0])), C.c_void_p(int(mask[1])), _lib.OSP_DEVICE, None
         else:
             raise ValueError('space must be "device" or "host"')
-        stats = _lib.ApplyMaskStats()
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_csr_apply_mask(self._h, M, N, rp, ci, sp_, int(bool(complement)), int(bool(validate)), C.byref(h),
-                                                 C.byref(stats)))
-        del keep
-        return CsrResult(self._ctx, h), stats.as_dict()
+        return _call(self._ctx, "osp_csr_apply_mask", self._h, M, N, rp, ci, sp_, int(bool(complement)), int(bool(validate)),
+                     stats=_lib.ApplyMaskStats(), keep=keep)
 
     def select(self, op, threshold=0.0, *, diag=0, fill=None):
         """The entries of this CSR that pass a predicate as a new CSR result on the device (``osp_csr_select``).  ``op`` is
@@ -157,16 +247,22 @@ class CsrResult:
         ``"ne"`` only) -- or ``"tril" "triu" "diag" "offdiag"`` -- column ``<=``, ``>=``, ``==``, ``!=`` row + ``diag``.
         ``fill=None``: kept entries keep their value bits; otherwise every kept entry's value is ``fill``.  Returns
         (result, stats dict): nnz_in, nnz_out, ms_total, launches."""
-        if op not in _lib.SELECT_OPS:
-            raise ValueError(f"op must be one of {' '.join(_lib.SELECT_OPS)} (got {op!r})")
         sel = _lib.Select()
-        sel.op, sel.threshold, sel.diag = _lib.SELECT_OPS[op], float(threshold), int(diag)
+        sel.op, sel.threshold, sel.diag = _enum(_lib.SELECT_OPS, op, "op"), float(threshold), int(diag)
         if fill is not None:
             sel.fill, sel.fill_value = 1, float(fill)
-        stats = _lib.SelectStats()
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_csr_select(self._h, C.byref(sel), C.byref(h), C.byref(stats)))
-        return CsrResult(self._ctx, h), stats.as_dict()
+        return _call(self._ctx, "osp_csr_select", self._h, C.byref(sel), stats=_lib.SelectStats())
+
+    def _same_family(self, other, *, shape=False, context=True):
+        """The checks of a second operand: a ``CsrResult``, of this result's context, shape (``shape=True``) and dtype."""
+        if not isinstance(other, CsrResult):
+            raise TypeError("other must be a CsrResult")
+        if context and other._ctx is not self._ctx:
+            raise OspError(_lib.ERR_ARG, "the operands belong to different contexts")
+        if shape and other.shape != self.shape:
+            raise OspError(_lib.ERR_ARG, f"the operands' shapes differ: {self.shape} and {other.shape}")
+        if other.dtype != self.dtype:
+            raise OspError(_lib.ERR_ARG, f"the operands' dtypes differ: {np.dtype(self.dtype)} and {np.dtype(other.dtype)}")
 
     def ewise(self, other, mode, op):
         """This CSR combined with ``other`` entry by entry as a new CSR result on the device (``osp_csr_ewise``); nothing is
@@ -176,22 +272,10 @@ class CsrResult:
         ``"minus" "div"``: one IEEE operation in the results' dtype.  ``other`` is a ``CsrResult`` of the same context, shape
         and dtype (``self`` itself is allowed).  Returns (result, stats dict): nnz_a, nnz_b, nnz_both, nnz_out, ms_total,
         launches."""
-        if mode not in _lib.EWISE_MODES:
-            raise ValueError(f"mode must be one of {' '.join(_lib.EWISE_MODES)} (got {mode!r})")
-        if op not in _lib.EWISE_OPS:
-            raise ValueError(f"op must be one of {' '.join(_lib.EWISE_OPS)} (got {op!r})")
-        if not isinstance(other, CsrResult):
-            raise TypeError("other must be a CsrResult")
-        if other.shape != self.shape:
-            raise OspError(_lib.ERR_ARG, f"the operands' shapes differ: {self.shape} and {other.shape}")
-        if other.dtype != self.dtype:
-            raise OspError(_lib.ERR_ARG, f"the operands' dtypes differ: {np.dtype(self.dtype)} and {np.dtype(other.dtype)}")
         ew = _lib.Ewise()
-        ew.mode, ew.op = _lib.EWISE_MODES[mode], _lib.EWISE_OPS[op]
-        stats = _lib.EwiseStats()
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_csr_ewise(self._h, other._h, C.byref(ew), C.byref(h), C.byref(stats)))
-        return CsrResult(self._ctx, h), stats.as_dict()
+        ew.mode, ew.op = _enum(_lib.EWISE_MODES, mode, "mode"), _enum(_lib.EWISE_OPS, op, "op")
+        self._same_family(other, shape=True, context=False)   # (the context is not checked here: the library refuses a foreign operand)
+        return _call(self._ctx, "osp_csr_ewise", self._h, other._h, C.byref(ew), stats=_lib.EwiseStats())
 
     def union(self, other, op="plus"):
         """``ewise(other, "union", op)``: the accumulation ``self (+) other``."""
@@ -211,22 +295,10 @@ class CsrResult:
         bit for bit; ``("min", "plus")`` relaxes a frontier of distances.  ``other`` is a ``CsrResult`` of the same context and
         dtype (``self`` itself is allowed).  Returns (result, stats dict): nnz_a, nnz_b, products, nnz_out, short_rows,
         long_rows, batches, launches, ms_total."""
-        if add not in _lib.MXM_ADD_OPS:
-            raise ValueError(f"add must be one of {' '.join(_lib.MXM_ADD_OPS)} (got {add!r})")
-        if mul not in _lib.MXM_MUL_OPS:
-            raise ValueError(f"mul must be one of {' '.join(_lib.MXM_MUL_OPS)} (got {mul!r})")
-        if not isinstance(other, CsrResult):
-            raise TypeError("other must be a CsrResult")
-        if other._ctx is not self._ctx:
-            raise OspError(_lib.ERR_ARG, "the operands belong to different contexts")
-        if other.dtype != self.dtype:
-            raise OspError(_lib.ERR_ARG, f"the operands' dtypes differ: {np.dtype(self.dtype)} and {np.dtype(other.dtype)}")
         sr = _lib.Semiring()
-        sr.add, sr.mul = _lib.MXM_ADD_OPS[add], _lib.MXM_MUL_OPS[mul]
-        stats = _lib.MxmStats()
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_csr_mxm(self._h, other._h, C.byref(sr), C.byref(h), C.byref(stats)))
-        return CsrResult(self._ctx, h), stats.as_dict()
+        sr.add, sr.mul = _enum(_lib.MXM_ADD_OPS, add, "add"), _enum(_lib.MXM_MUL_OPS, mul, "mul")
+        self._same_family(other)
+        return _call(self._ctx, "osp_csr_mxm", self._h, other._h, C.byref(sr), stats=_lib.MxmStats())
 
     def transpose(self):
         """This CSR (M x N) transposed as a new N x M CSR result on the device (``osp_csr_transpose``): entry (j, i) exists
@@ -234,10 +306,7 @@ class CsrResult:
         three arrays back.  A result of at most 64 rows takes the row-mask path (nothing is sorted), everything else a
         stable radix sort by column.  Returns (result, stats dict): nnz, path (0 nothing launched, 1 row mask, 2 sort),
         passes, launches, ms_total."""
-        stats = _lib.TransposeStats()
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_csr_transpose(self._h, None, C.byref(h), C.byref(stats)))
-        return CsrResult(self._ctx, h), stats.as_dict()
+        return _call(self._ctx, "osp_csr_transpose", self._h, None, stats=_lib.TransposeStats())
 
     def matmul(self, other, *, self_transposed=False, validate=False, partial_capacity=0):
         """This CSR (M x K) times ``other`` (K x N) with + and x through the outer-product pipeline
@@ -246,12 +315,7 @@ class CsrResult:
         ``self_transposed=True`` computes ``self^T @ other`` instead (self K x M), with no transpose at all: self's own CSR
         arrays are the CSC of ``self^T``.  Equals ``mxm(other, "plus", "times")`` in row pointers, columns and value bits.
         ``other`` is a ``CsrResult`` of the same context and dtype (``self`` itself is allowed)."""
-        if not isinstance(other, CsrResult):
-            raise TypeError("other must be a CsrResult")
-        if other._ctx is not self._ctx:
-            raise OspError(_lib.ERR_ARG, "the operands belong to different contexts")
-        if other.dtype != self.dtype:
-            raise OspError(_lib.ERR_ARG, f"the operands' dtypes differ: {np.dtype(self.dtype)} and {np.dtype(other.dtype)}")
+        self._same_family(other)
         M, K = (self.shape[1], self.shape[0]) if self_transposed else self.shape
         if K != other.shape[0]:
             raise OspError(_lib.ERR_DIM, f"the inner dimensions differ: {K} and {other.shape[0]}")
@@ -263,25 +327,27 @@ class CsrResult:
             if at is not self:
                 at.close()
 
-    def _vector_arg(self, v, n, dtype, space, what):
-        """A dense vector argument of the ``osp_csr_*`` functions that take one: (pointer, keep-alive).  ``space="host"``: an
-        array-like of n values, converted to ``dtype``; ``space="device"``: a device address, or an object with
-        ``data_ptr()`` (a torch tensor of n values of ``dtype``: the caller has synchronised its stream)."""
-        if space not in ("device", "host"):
-            raise ValueError('space must be "device" or "host"')
-        if v is None:
-            return None, None
-        if space == "host" or n == 0:   # (n == 0: nothing is read, and the pointer is never null)
-            a = np.ascontiguousarray(v, dtype) if space == "host" else np.zeros(0, dtype)
-            if a.shape != (n,):
-                raise OspError(_lib.ERR_ARG, f"{what} must have {n} entries (got shape {a.shape})")
-            a = a if n else np.zeros(1, dtype)
-            return C.c_void_p(a.ctypes.data), a
-        if hasattr(v, "data_ptr"):
-            if v.numel() != n or v.element_size() != np.dtype(dtype).itemsize or not v.is_contiguous():
-                raise OspError(_lib.ERR_ARG, f"{what} must be a contiguous tensor of {n} values of {np.dtype(dtype)}")
-            return C.c_void_p(v.data_ptr()), v
-        return C.c_void_p(int(v)), None
+    def _out_arg(self, out, shape, space):
+        """The output of ``mxv`` (``shape`` (M,)) and ``mxd`` ((M, k)): (pointer, buffer the pointer points into, what the
+        method returns).  ``out=None`` allocates -- numpy on the host, torch on the context's device --, else ``out`` is checked
+        and filled.  The pointer is never null."""
+        size = math.prod(shape)
+        if out is None and space == "host":
+            ret = np.empty(shape, self.dtype)
+            buf = ret if size else np.empty(1, self.dtype)
+            return C.c_void_p(buf.ctypes.data), buf, ret
+        if out is None:
+            import torch
+            buf = torch.empty(max(size, 1), dtype=_torch_dtype(self.dtype), device=f"cuda:{self._ctx.device}")
+            return C.c_void_p(buf.data_ptr()), buf, buf[:size].view(shape)
+        if space == "host":
+            if not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.shape == shape and out.flags.c_contiguous):
+                raise OspError(_lib.ERR_ARG, f"out must be a contiguous numpy array of {size} values of {np.dtype(self.dtype)}" if len(shape) == 1
+                               else f"out must be a contiguous ({shape[0]}, {shape[1]}) numpy array of {np.dtype(self.dtype)}")
+            buf = out if size else np.empty(1, self.dtype)
+            return C.c_void_p(buf.ctypes.data), buf, out
+        ptr, buf = _dense_arg(out, shape, self.dtype, "device", "out", floating=len(shape) == 2)
+        return ptr, buf, out
 
     def reduce(self, axis, op, out=None):
         """One value per row (``axis="rows"``, M values) or per column (``"cols"``, N values) of this CSR
@@ -290,19 +356,16 @@ class CsrResult:
         +inf, -inf, 0.  ``out=None``: returns (numpy array on the host, stats dict); ``out`` a device address (or a torch
         tensor of that many values of this dtype): fills it and returns (out, stats dict).  Stats: nnz_in, nnz_out,
         long_segments, ms_total, launches."""
-        if axis not in _lib.AXES:
-            raise ValueError(f"axis must be one of {' '.join(_lib.AXES)} (got {axis!r})")
-        if op not in _lib.REDUCE_OPS:
-            raise ValueError(f"op must be one of {' '.join(_lib.REDUCE_OPS)} (got {op!r})")
-        n = self.shape[_lib.AXES[axis]]
+        ax, rop = _enum(_lib.AXES, axis, "axis"), _enum(_lib.REDUCE_OPS, op, "op")
+        n = self.shape[ax]
         stats = _lib.VectorStats()
         if out is None:
             buf = np.empty(max(n, 1), self.dtype)   # (never a null pointer)
             ptr, space, ret = C.c_void_p(buf.ctypes.data), _lib.OSP_HOST, buf[:n]
         else:
-            ptr, _ = self._vector_arg(out, n, self.dtype, "device", "out")
+            ptr, buf = _dense_arg(out, (n,), self.dtype, "device", "out")
             space, ret = _lib.OSP_DEVICE, out
-        _lib.check(_lib.lib().osp_csr_reduce(self._h, _lib.AXES[axis], _lib.REDUCE_OPS[op], ptr, space, C.byref(stats)))
+        _lib.check(_lib.lib().osp_csr_reduce(self._h, ax, rop, ptr, space, C.byref(stats)))
         return ret, stats.as_dict()
 
     def mxv(self, x, add="plus", mul="times", out=None, space="device"):
@@ -315,62 +378,17 @@ class CsrResult:
         tensor on the context's device, stats dict), or (numpy array, stats dict) with ``space="host"``; ``out`` a device
         address or torch tensor of M values (a numpy array of this dtype with ``space="host"``): fills and returns it.
         ``out is x`` is allowed on a square result.  Stats: nnz_in, nnz_out, long_segments, group, launches, ms_total."""
-        if add not in _lib.MXV_ADD_OPS:
-            raise ValueError(f"add must be one of {' '.join(_lib.MXV_ADD_OPS)} (got {add!r})")
-        if mul not in _lib.MXM_MUL_OPS:
-            raise ValueError(f"mul must be one of {' '.join(_lib.MXM_MUL_OPS)} (got {mul!r})")
-        if space not in ("device", "host"):
-            raise ValueError('space must be "device" or "host"')
+        sr = _lib.Semiring()
+        sr.add, sr.mul = _enum(_lib.MXV_ADD_OPS, add, "add"), _enum(_lib.MXM_MUL_OPS, mul, "mul")
+        sp = _space(space)
         M, N = self.shape
         if x is None and mul != "first":
             raise OspError(_lib.ERR_ARG, 'x may be None only when mul is "first"')
-        xp, keep_x = self._vector_arg(x if mul != "first" else None, N, self.dtype, space, "x")
-        if out is None and space == "host":
-            ret = np.empty(M, self.dtype)
-            buf = ret if M else np.empty(1, self.dtype)   # (never a null pointer)
-            yp = C.c_void_p(buf.ctypes.data)
-        elif out is None:
-            import torch
-            buf = torch.empty(max(M, 1), dtype=torch.float32 if self.dtype == np.float32 else torch.float64,
-                              device=f"cuda:{self._ctx.device}")
-            ret = buf[:M]
-            yp = C.c_void_p(buf.data_ptr())
-        elif space == "host":
-            if not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.shape == (M,) and out.flags.c_contiguous):
-                raise OspError(_lib.ERR_ARG, f"out must be a contiguous numpy array of {M} values of {np.dtype(self.dtype)}")
-            ret = out
-            buf = out if M else np.empty(1, self.dtype)
-            yp = C.c_void_p(buf.ctypes.data)
-        else:
-            yp, buf = self._vector_arg(out, M, self.dtype, "device", "out")
-            ret = out
-        sr = _lib.Semiring()
-        sr.add, sr.mul = _lib.MXV_ADD_OPS[add], _lib.MXM_MUL_OPS[mul]
+        xp, keep_x = _dense_arg(x if mul != "first" else None, (N,), self.dtype, space, "x")
+        yp, buf, ret = self._out_arg(out, (M,), space)
         stats = _lib.MxvStats()
-        _lib.check(_lib.lib().osp_csr_mxv(self._h, C.byref(sr), xp, yp, _lib.OSP_HOST if space == "host" else _lib.OSP_DEVICE,
-                                          C.byref(stats)))
-        del keep_x, buf
+        _lib.check(_lib.lib().osp_csr_mxv(self._h, C.byref(sr), xp, yp, sp, C.byref(stats)))   # (keep_x and buf live until here)
         return ret, stats.as_dict()
-
-    def _matrix_arg(self, v, rows, k, space, what):
-        """A dense row-major ``rows`` x ``k`` argument of ``mxd``: (pointer, keep-alive), under ``_vector_arg``'s conventions.
-        A device address carries no shape: the caller vouches for it."""
-        dtype = self.dtype
-        if space == "host":
-            a = np.ascontiguousarray(v, dtype)
-            if a.shape != (rows, k):
-                raise OspError(_lib.ERR_ARG, f"{what} must have shape ({rows}, {k}) (got {a.shape})")
-            a = a if a.size else np.zeros(1, dtype)   # (never a null pointer)
-            return C.c_void_p(a.ctypes.data), a
-        if hasattr(v, "data_ptr"):
-            if (tuple(v.shape) != (rows, k) or v.element_size() != np.dtype(dtype).itemsize or not v.is_floating_point()
-                    or not v.is_contiguous()):
-                raise OspError(_lib.ERR_ARG, f"{what} must be a contiguous ({rows}, {k}) tensor of {np.dtype(dtype)}")
-            if v.numel() == 0:
-                a = np.zeros(1, dtype)
-                return C.c_void_p(a.ctypes.data), a
-            return C.c_void_p(v.data_ptr()), v
-        return C.c_void_p(int(v)), None
 
     def mxd(self, X, add="plus", mul="times", out=None, space="device", k=None):
         """This CSR (M x N) times the dense matrix ``X`` (N x k, row-major, contiguous) under the semiring ``(add, mul)``
@@ -383,12 +401,9 @@ class CsrResult:
         ``space="host"``; ``out`` a device address or torch tensor of shape (M, k) (a numpy array of this dtype with
         ``space="host"``): fills and returns it.  ``out is X`` is allowed on a square result.  Stats: nnz_in, nnz_out, cols,
         long_segments, lanes_per_row, launches, ms_total."""
-        if add not in _lib.MXV_ADD_OPS:
-            raise ValueError(f"add must be one of {' '.join(_lib.MXV_ADD_OPS)} (got {add!r})")
-        if mul not in _lib.MXM_MUL_OPS:
-            raise ValueError(f"mul must be one of {' '.join(_lib.MXM_MUL_OPS)} (got {mul!r})")
-        if space not in ("device", "host"):
-            raise ValueError('space must be "device" or "host"')
+        sr = _lib.Semiring()
+        sr.add, sr.mul = _enum(_lib.MXV_ADD_OPS, add, "add"), _enum(_lib.MXM_MUL_OPS, mul, "mul")
+        sp = _space(space)
         M, N = self.shape
         if X is None and mul != "first":
             raise OspError(_lib.ERR_ARG, 'X may be None only when mul is "first"')
@@ -400,32 +415,10 @@ class CsrResult:
         k = int(k)
         if not 0 <= k <= _lib.MXD_MAX_COLS:
             raise OspError(_lib.ERR_ARG, f"k must lie in [0, {_lib.MXD_MAX_COLS}] (got {k})")
-        xp, keep_x = (None, None) if X is None or mul == "first" else self._matrix_arg(X, N, k, space, "X")
-        if out is None and space == "host":
-            ret = np.empty((M, k), self.dtype)
-            buf = ret if ret.size else np.empty(1, self.dtype)   # (never a null pointer)
-            yp = C.c_void_p(buf.ctypes.data)
-        elif out is None:
-            import torch
-            buf = torch.empty(max(M * k, 1), dtype=torch.float32 if self.dtype == np.float32 else torch.float64,
-                              device=f"cuda:{self._ctx.device}")
-            ret = buf[:M * k].view(M, k)
-            yp = C.c_void_p(buf.data_ptr())
-        elif space == "host":
-            if not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.shape == (M, k) and out.flags.c_contiguous):
-                raise OspError(_lib.ERR_ARG, f"out must be a contiguous ({M}, {k}) numpy array of {np.dtype(self.dtype)}")
-            ret = out
-            buf = out if out.size else np.empty(1, self.dtype)
-            yp = C.c_void_p(buf.ctypes.data)
-        else:
-            yp, buf = self._matrix_arg(out, M, k, "device", "out")
-            ret = out
-        sr = _lib.Semiring()
-        sr.add, sr.mul = _lib.MXV_ADD_OPS[add], _lib.MXM_MUL_OPS[mul]
+        xp, keep_x = _dense_arg(X if mul != "first" else None, (N, k), self.dtype, space, "X", floating=True)
+        yp, buf, ret = self._out_arg(out, (M, k), space)
         stats = _lib.MxdStats()
-        _lib.check(_lib.lib().osp_csr_mxd(self._h, C.byref(sr), xp, k, yp, _lib.OSP_HOST if space == "host" else _lib.OSP_DEVICE,
-                                          C.byref(stats)))
-        del keep_x, buf
+        _lib.check(_lib.lib().osp_csr_mxd(self._h, C.byref(sr), xp, k, yp, sp, C.byref(stats)))   # (keep_x and buf live until here)
         return ret, stats.as_dict()
 
     def apply_vectors(self, rows=None, row_op=None, cols=None, col_op=None, space="device"):
@@ -440,15 +433,11 @@ class CsrResult:
             if op is not None and op not in _lib.VECTOR_APPLY_OPS:
                 raise ValueError(f"{side} must be None or one of {' '.join(_lib.VECTOR_APPLY_OPS)} (got {op!r})")
             setattr(ap, side, _lib.VECTOR_NONE if op is None else _lib.VECTOR_APPLY_OPS[op])
+        sp = _space(space)
         M, N = self.shape
-        x, keep_x = self._vector_arg(rows if row_op is not None else None, M, self.dtype, space, "rows")
-        y, keep_y = self._vector_arg(cols if col_op is not None else None, N, self.dtype, space, "cols")
-        stats = _lib.VectorStats()
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_csr_apply_vectors(self._h, C.byref(ap), x, y, _lib.OSP_HOST if space == "host" else _lib.OSP_DEVICE,
-                                                    C.byref(h), C.byref(stats)))
-        del keep_x, keep_y
-        return CsrResult(self._ctx, h), stats.as_dict()
+        x, keep_x = _dense_arg(rows if row_op is not None else None, (M,), self.dtype, space, "rows")
+        y, keep_y = _dense_arg(cols if col_op is not None else None, (N,), self.dtype, space, "cols")
+        return _call(self._ctx, "osp_csr_apply_vectors", self._h, C.byref(ap), x, y, sp, stats=_lib.VectorStats(), keep=(keep_x, keep_y))
 
     def select_vertices(self, keep_rows=None, keep_cols=None, space="device"):
         """The entries (i, j) of this CSR with ``keep_rows[i] != 0`` and ``keep_cols[j] != 0`` as a new CSR result on the
@@ -456,50 +445,11 @@ class CsrResult:
         The shape stays: a removed vertex is an empty row or column.  ``keep_rows``: M bytes, ``keep_cols``: N bytes (uint8 /
         bool), device addresses / torch tensors (``space="device"``) or array-likes (``space="host"``).  Returns (result,
         stats dict): nnz_in, nnz_out, long_segments, ms_total, launches."""
+        sp = _space(space)
         M, N = self.shape
-        kr, keep_r = self._vector_arg(keep_rows, M, np.uint8, space, "keep_rows")
-        kc, keep_c = self._vector_arg(keep_cols, N, np.uint8, space, "keep_cols")
-        stats = _lib.VectorStats()
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_csr_select_vertices(self._h, kr, kc, _lib.OSP_HOST if space == "host" else _lib.OSP_DEVICE, C.byref(h),
-                                                      C.byref(stats)))
-        del keep_r, keep_c
-        return CsrResult(self._ctx, h), stats.as_dict()
-
-    @staticmethod
-    def _index_arg(v, space, what):
-        """An index list of ``extract``: (pointer, count, keep-alive, ascending).  ``space="host"``: an array-like of integers
-        in [0, 2^32); ``space="device"``: a torch tensor of 4-byte integers (the caller has synchronised its stream) or an
-        ``(address, count)`` pair.  ``ascending`` says whether the list is strictly ascending -- numpy on the host, one torch
-        comparison on the device -- and is None for a bare address, which nothing here can read."""
-        if space not in ("device", "host"):
-            raise ValueError('space must be "device" or "host"')
-        if v is None:
-            return None, 0, None, True
-        if space == "host":
-            a = np.atleast_1d(np.asarray(v))
-            if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
-                raise OspError(_lib.ERR_ARG, f"{what} must be a one-dimensional list of integers")
-            a = a.astype(np.int64) if a.size else np.zeros(0, np.int64)
-            if a.size and (a.min() < 0 or a.max() > 0xffffffff):
-                raise OspError(_lib.ERR_ARG, f"{what} holds an index outside [0, 2^32)")
-            ascending = bool(np.all(a[1:] > a[:-1]))
-            a = np.ascontiguousarray(a, np.uint32)
-            keep = a if a.size else np.zeros(1, np.uint32)   # (an empty list: never a null pointer, NULL means "all")
-            return C.c_void_p(keep.ctypes.data), int(a.size), keep, ascending
-        if hasattr(v, "data_ptr"):
-            if v.dim() != 1 or v.element_size() != 4 or v.is_floating_point() or not v.is_contiguous():
-                raise OspError(_lib.ERR_ARG, f"{what} must be a contiguous one-dimensional tensor of 4-byte integers")
-            addr, n = v.data_ptr(), int(v.numel())
-        else:
-            addr, n = int(v[0]), int(v[1])
-        if n == 0:   # (nothing is read: any non-null pointer says "an empty list")
-            keep = np.zeros(1, np.uint32)
-            return C.c_void_p(keep.ctypes.data), 0, keep, True
-        if not hasattr(v, "data_ptr"):
-            return C.c_void_p(addr), n, None, None
-        w = v.long() & 0xffffffff   # (an int32 tensor holds a uint32 list's bits)
-        return C.c_void_p(addr), n, v, bool((w[1:] > w[:-1]).all().item())
+        kr, keep_r = _dense_arg(keep_rows, (M,), np.uint8, space, "keep_rows")
+        kc, keep_c = _dense_arg(keep_cols, (N,), np.uint8, space, "keep_cols")
+        return _call(self._ctx, "osp_csr_select_vertices", self._h, kr, kc, sp, stats=_lib.VectorStats(), keep=(keep_r, keep_c))
 
     def extract(self, rows=None, cols=None, space="device"):
         """The submatrix ``out[i, k] = self[rows[i], cols[k]]``, renumbered, as a new ``len(rows) x len(cols)`` CSR result
@@ -513,8 +463,9 @@ class CsrResult:
         bare address is taken as ascending) or array-likes (``space="host"``).  An index beyond its dimension is
         ``OspError(ERR_ARG)`` on either path.  Values keep their bits.  Returns (result, stats dict): nnz_in, nnz_gathered,
         nnz_out, ms_total, launches, readbacks, composed (the composed path: the sums over its calls)."""
-        rp, nr, keep_r, _ = self._index_arg(rows, space, "rows")
-        cp, nc, keep_c, ascending = self._index_arg(cols, space, "cols")
+        sp = _space(space)
+        rp, nr, keep_r, _ = _index_arg(rows, space, "rows")
+        cp, nc, keep_c, ascending = _index_arg(cols, space, "cols")
         if ascending is False:
             made = []
             try:
@@ -538,13 +489,9 @@ class CsrResult:
                      "readbacks": st_y["readbacks"] + (0 if rows is None else st["readbacks"]), "composed": True}
             return out, stats
         ex = _lib.Extract()
-        ex.rows, ex.n_rows, ex.cols, ex.n_cols = rp, nr, cp, nc
-        ex.space = _lib.OSP_HOST if space == "host" else _lib.OSP_DEVICE
-        stats = _lib.ExtractStats()
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_csr_extract(self._h, C.byref(ex), C.byref(h), C.byref(stats)))
-        del keep_r, keep_c
-        return CsrResult(self._ctx, h), dict(stats.as_dict(), composed=False)
+        ex.rows, ex.n_rows, ex.cols, ex.n_cols, ex.space = rp, nr, cp, nc, sp
+        out, stats = _call(self._ctx, "osp_csr_extract", self._h, C.byref(ex), stats=_lib.ExtractStats(), keep=(keep_r, keep_c))
+        return out, dict(stats, composed=False)
 
     def permute(self, perm, space="device"):
         """``extract(perm, perm)`` on a square result: vertex ``perm[i]`` becomes vertex i."""
@@ -583,6 +530,34 @@ ALGORITHMS = {"outer": 0, "rowwise": 1}  # osp_algorithm_t
 def aos_dtype(value_dtype):
     """numpy view of the reference's packed ``CSRElement{index_t idx; value_t val}`` (``common.h:10-16``)."""
     return np.dtype([("idx", "<u4"), ("val", np.dtype(value_dtype).newbyteorder("<"))], align=False)
+
+
+def _config(validate, partial_capacity, k_range=None, row_shard=None, algorithm=None):
+    """``osp_config_t``: the library's defaults with the given fields set."""
+    cfg = _lib.Config()
+    _lib.lib().osp_config_default(C.byref(cfg))
+    cfg.validate = int(bool(validate))
+    cfg.partial_capacity = int(partial_capacity or 0)
+    if k_range is not None:
+        cfg.k_begin, cfg.k_end = int(k_range[0]), int(k_range[1])
+    if row_shard is not None:
+        cfg.row_shard_index, cfg.row_shard_count = int(row_shard[0]), int(row_shard[1])
+    if algorithm is not None:
+        cfg.algorithm = ALGORITHMS[algorithm]
+    return cfg
+
+
+def _csc_csr_arrays(K, a_colptr, a_rowidx, a_vals, b_rowptr, b_colidx, b_vals):
+    """The six host operands of a product A(CSC) * B(CSR) as contiguous arrays of the ABI's types: (value dtype, arrays)."""
+    dt = np.dtype(a_vals.dtype)
+    if dt not in _DT or np.dtype(b_vals.dtype) != dt:
+        raise TypeError("values must both be float32 or both float64")
+    arrs = [np.ascontiguousarray(a_colptr, np.int64), np.ascontiguousarray(a_rowidx, np.uint32), np.ascontiguousarray(a_vals, dt),
+            np.ascontiguousarray(b_rowptr, np.int64), np.ascontiguousarray(b_colidx, np.uint32), np.ascontiguousarray(b_vals, dt)]
+    if len(arrs[0]) != K + 1 or len(arrs[3]) != K + 1:
+        # reference: assert(csc.pos.size() == csr.pos.size()), SimSpGEMM.cpp:267
+        raise OspError(_lib.ERR_DIM, f"pointer arrays must have K+1={K + 1} entries (got {len(arrs[0])} and {len(arrs[3])})")
+    return dt, arrs
 
 
 class Context:
@@ -624,36 +599,15 @@ class Context:
             pass
 
     def _config(self, validate, partial_capacity, k_range, row_shard=None):
-        cfg = _lib.Config()
-        _lib.lib().osp_config_default(C.byref(cfg))
-        cfg.validate = int(bool(validate))
-        cfg.partial_capacity = int(partial_capacity or 0)
-        if k_range is not None:
-            cfg.k_begin, cfg.k_end = int(k_range[0]), int(k_range[1])
-        if row_shard is not None:
-            cfg.row_shard_index, cfg.row_shard_count = int(row_shard[0]), int(row_shard[1])
-        cfg.algorithm = ALGORITHMS[self.algorithm]
-        return cfg
+        return _config(validate, partial_capacity, k_range, row_shard, self.algorithm)
 
     def spgemm_csc_csr(self, M, K, N, a_colptr, a_rowidx, a_vals, b_rowptr, b_colidx, b_vals, *,
                        validate=True, partial_capacity=0, k_range=None, row_shard=None):
         """C = A(CSC) * B(CSR) with numpy (host) operands.  row_shard=(i, G): only the i-th of G output-row ranges
         (balanced by partial products; ``result.info['row_begin'/'row_end']`` say which rows came back)."""
-        dt = np.dtype(a_vals.dtype)
-        if dt not in _DT or np.dtype(b_vals.dtype) != dt:
-            raise TypeError("values must both be float32 or both float64")
-        arrs = [np.ascontiguousarray(a_colptr, np.int64), np.ascontiguousarray(a_rowidx, np.uint32),
-                np.ascontiguousarray(a_vals, dt), np.ascontiguousarray(b_rowptr, np.int64),
-                np.ascontiguousarray(b_colidx, np.uint32), np.ascontiguousarray(b_vals, dt)]
-        if len(arrs[0]) != K + 1 or len(arrs[3]) != K + 1:
-            # reference: assert(csc.pos.size() == csr.pos.size()), SimSpGEMM.cpp:267
-            raise OspError(_lib.ERR_DIM, f"pointer arrays must have K+1={K + 1} entries "
-                                         f"(got {len(arrs[0])} and {len(arrs[3])})")
+        dt, arrs = _csc_csr_arrays(K, a_colptr, a_rowidx, a_vals, b_rowptr, b_colidx, b_vals)
         cfg = self._config(validate, partial_capacity, k_range, row_shard)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_spgemm_csc_csr(self._h, _DT[dt], M, K, N, *[_ptr(a) for a in arrs],
-                                                 _lib.OSP_HOST, C.byref(cfg), C.byref(h)))
-        return CsrResult(self, h)
+        return _call(self, "osp_spgemm_csc_csr", self._h, _DT[dt], M, K, N, *[_ptr(a) for a in arrs], _lib.OSP_HOST, C.byref(cfg), keep=arrs)
 
     def spgemm_csc_csr_aos(self, M, K, N, a_pos, a_data, b_pos, b_data, *, validate=True, partial_capacity=0):
         """The reference's in-memory operands as they stand (``osp_spgemm_csc_csr_aos``): ``pos`` = ``CSRMatrix::pos``
@@ -668,10 +622,8 @@ class Context:
             raise OspError(_lib.ERR_DIM, f"pos arrays must have K+1={K + 1} entries (got {len(ap)} and {len(bp)})")
         ad, bd = np.ascontiguousarray(a_data), np.ascontiguousarray(b_data)
         cfg = self._config(validate, partial_capacity, None)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_spgemm_csc_csr_aos(self._h, _DT[vdt], M, K, N, _ptr(ap), _ptr(ad), _ptr(bp), _ptr(bd),
-                                                     _lib.OSP_HOST, C.byref(cfg), C.byref(h)))
-        return CsrResult(self, h)
+        return _call(self, "osp_spgemm_csc_csr_aos", self._h, _DT[vdt], M, K, N, _ptr(ap), _ptr(ad), _ptr(bp), _ptr(bd), _lib.OSP_HOST,
+                     C.byref(cfg), keep=(ap, ad, bp, bd))
 
     def alloc(self, nbytes):
         """Device memory from the context's buffer pool (``osp_context_alloc``); give it back with ``free``."""
@@ -692,11 +644,8 @@ class Context:
         arrs = [np.ascontiguousarray(a[0], np.uint32), np.ascontiguousarray(a[1], np.uint32), np.ascontiguousarray(a[2], dt),
                 np.ascontiguousarray(b[0], np.uint32), np.ascontiguousarray(b[1], np.uint32), np.ascontiguousarray(b[2], dt)]
         cfg = self._config(True, partial_capacity, None)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_spgemm_coo(self._h, _DT[dt], M, K, N, len(arrs[0]), _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]),
-                                             len(arrs[3]), _ptr(arrs[3]), _ptr(arrs[4]), _ptr(arrs[5]), _lib.OSP_HOST,
-                                             C.byref(cfg), C.byref(h)))
-        return CsrResult(self, h)
+        return _call(self, "osp_spgemm_coo", self._h, _DT[dt], M, K, N, len(arrs[0]), _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]),
+                     len(arrs[3]), _ptr(arrs[3]), _ptr(arrs[4]), _ptr(arrs[5]), _lib.OSP_HOST, C.byref(cfg), keep=arrs)
 
     def stream_copy_gbps(self, nbytes=2 << 30, reps=10):
         """What a plain 16-bytes-per-lane copy reaches on this device, read + written bytes per second in GB/s
@@ -710,10 +659,8 @@ class Context:
         order.  ``result.info['ms_ingest']`` is the device time of the two COO -> CSC / CSR conversions.  ``k_range``
         restricts the PRODUCT behind the conversions to a slab of k (the conversions always take the whole operands)."""
         cfg = self._config(True, partial_capacity, k_range)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_spgemm_coo(self._h, _DT[np.dtype(dtype)], M, K, N, int(nnz_a), *[C.c_void_p(int(p)) for p in a_ptrs],
-                                             int(nnz_b), *[C.c_void_p(int(p)) for p in b_ptrs], _lib.OSP_DEVICE, C.byref(cfg), C.byref(h)))
-        return CsrResult(self, h)
+        return _call(self, "osp_spgemm_coo", self._h, _DT[np.dtype(dtype)], M, K, N, int(nnz_a), *_dptrs(a_ptrs), int(nnz_b), *_dptrs(b_ptrs),
+                     _lib.OSP_DEVICE, C.byref(cfg))
 
     def im2col_device(self, dtype, N, C_, H, W, nnz_x, x_ptrs, geom, *, out_ptrs=None, validate=True):
         """im2col of a "pixel x channel" activation into CSC (``osp_im2col_csc``).  x_ptrs = (rows, cols, vals) DEVICE
@@ -721,74 +668,50 @@ class Context:
         ``out_ptrs`` only nnz(A) is computed; with out_ptrs = (colptr, rowidx, vals) device addresses of C*kh*kw + 1,
         nnz(A) and nnz(A) entries A is written there.  Returns nnz(A)."""
         n = C.c_uint64()
-        outs = [None, None, None] if out_ptrs is None else [C.c_void_p(int(p)) if p else None for p in out_ptrs]
+        outs = [None, None, None] if out_ptrs is None else _dptrs(out_ptrs, null=True)
         _lib.check(_lib.lib().osp_im2col_csc(self._h, _DT[np.dtype(dtype)], int(N), int(C_), int(H), int(W), int(nnz_x),
-                                             *[C.c_void_p(int(p)) if p else None for p in x_ptrs], _lib.OSP_DEVICE, C.byref(geom),
-                                             int(bool(validate)), C.byref(n), *outs))
+                                             *_dptrs(x_ptrs, null=True), _lib.OSP_DEVICE, C.byref(geom), int(bool(validate)), C.byref(n), *outs))
         return n.value
 
     def spgemm_conv2d_device(self, dtype, N, C_, H, W, nnz_x, x_ptrs, OC, nnz_w, w_ptrs, geom, *, validate=True, partial_capacity=0):
         """A conv layer as the CLI's product im2col(x) * W^T (``osp_spgemm_conv2d``): x as in ``im2col_device``, W the
         OC x (C*kh*kw) weight as (rows, cols, vals) DEVICE addresses.  Returns the (N*OH*OW) x OC CSR result (NHWC)."""
         cfg = self._config(validate, partial_capacity, None)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_spgemm_conv2d(self._h, _DT[np.dtype(dtype)], int(N), int(C_), int(H), int(W), int(nnz_x),
-                                                *[C.c_void_p(int(p)) if p else None for p in x_ptrs], int(OC), int(nnz_w),
-                                                *[C.c_void_p(int(p)) if p else None for p in w_ptrs], _lib.OSP_DEVICE, C.byref(geom),
-                                                C.byref(cfg), C.byref(h)))
-        return CsrResult(self, h)
+        return _call(self, "osp_spgemm_conv2d", self._h, _DT[np.dtype(dtype)], int(N), int(C_), int(H), int(W), int(nnz_x),
+                     *_dptrs(x_ptrs, null=True), int(OC), int(nnz_w), *_dptrs(w_ptrs, null=True), _lib.OSP_DEVICE, C.byref(geom), C.byref(cfg))
 
     def spgemm_csc_csr_device(self, dtype, M, K, N, ptrs, *, validate=False, partial_capacity=0, k_range=None, row_shard=None):
         """Same with six DEVICE addresses (ints): a_colptr, a_rowidx, a_vals, b_rowptr, b_colidx, b_vals.
         The arrays must be COMPLETE when this is called: the context works on a stream of its own (or the one it was
         created on) and does not wait for kernels other streams -- e.g. torch's -- still have in flight on them."""
         cfg = self._config(validate, partial_capacity, k_range, row_shard)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_spgemm_csc_csr(self._h, _DT[np.dtype(dtype)], M, K, N,
-                                                 *[C.c_void_p(int(p)) for p in ptrs], _lib.OSP_DEVICE,
-                                                 C.byref(cfg), C.byref(h)))
-        return CsrResult(self, h)
+        return _call(self, "osp_spgemm_csc_csr", self._h, _DT[np.dtype(dtype)], M, K, N, *_dptrs(ptrs), _lib.OSP_DEVICE, C.byref(cfg))
 
     def spgemm_masked(self, M, K, N, a_colptr, a_rowidx, a_vals, b_rowptr, b_colidx, b_vals, m_rowptr, m_colidx, *, validate=True):
         """C<mask> = A(CSC) * B(CSR) with numpy (host) operands (``osp_spgemm_masked``): the entries of the product at the
         mask's pattern (M x N, CSR, no values) where at least one product exists, the same bits as the unmasked product
         there.  ``result.info['partials']`` is the number of products formed."""
-        dt = np.dtype(a_vals.dtype)
-        if dt not in _DT or np.dtype(b_vals.dtype) != dt:
-            raise TypeError("values must both be float32 or both float64")
-        arrs = [np.ascontiguousarray(a_colptr, np.int64), np.ascontiguousarray(a_rowidx, np.uint32),
-                np.ascontiguousarray(a_vals, dt), np.ascontiguousarray(b_rowptr, np.int64),
-                np.ascontiguousarray(b_colidx, np.uint32), np.ascontiguousarray(b_vals, dt),
-                np.ascontiguousarray(m_rowptr, np.int64), np.ascontiguousarray(m_colidx, np.uint32)]
-        if len(arrs[0]) != K + 1 or len(arrs[3]) != K + 1:
-            raise OspError(_lib.ERR_DIM, f"pointer arrays must have K+1={K + 1} entries "
-                                         f"(got {len(arrs[0])} and {len(arrs[3])})")
-        if len(arrs[6]) != M + 1:
-            raise OspError(_lib.ERR_ARG, f"the mask's row pointers must have M+1={M + 1} entries (got {len(arrs[6])})")
+        dt, arrs = _csc_csr_arrays(K, a_colptr, a_rowidx, a_vals, b_rowptr, b_colidx, b_vals)
+        mr, mc = np.ascontiguousarray(m_rowptr, np.int64), np.ascontiguousarray(m_colidx, np.uint32)
+        if len(mr) != M + 1:
+            raise OspError(_lib.ERR_ARG, f"the mask's row pointers must have M+1={M + 1} entries (got {len(mr)})")
         cfg = self._config(validate, 0, None)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_spgemm_masked(self._h, _DT[dt], M, K, N, *[_ptr(a) for a in arrs[:6]],
-                                                C.c_void_p(arrs[6].ctypes.data), _ptr(arrs[7]), _lib.OSP_HOST, C.byref(cfg), C.byref(h)))
-        return CsrResult(self, h)
+        return _call(self, "osp_spgemm_masked", self._h, _DT[dt], M, K, N, *[_ptr(a) for a in arrs], C.c_void_p(mr.ctypes.data), _ptr(mc),
+                     _lib.OSP_HOST, C.byref(cfg), keep=(arrs, mr, mc))
 
     def spgemm_masked_device(self, dtype, M, K, N, ptrs, mask_ptrs, *, validate=False):
         """Same with DEVICE addresses (ints): ``ptrs`` as in ``spgemm_csc_csr_device``, ``mask_ptrs`` = (m_rowptr, m_colidx).
         The arrays must be complete when this is called (see ``spgemm_csc_csr_device``)."""
         cfg = self._config(validate, 0, None)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_spgemm_masked(self._h, _DT[np.dtype(dtype)], M, K, N, *[C.c_void_p(int(p)) for p in ptrs],
-                                                *[C.c_void_p(int(p)) for p in mask_ptrs], _lib.OSP_DEVICE, C.byref(cfg), C.byref(h)))
-        return CsrResult(self, h)
+        return _call(self, "osp_spgemm_masked", self._h, _DT[np.dtype(dtype)], M, K, N, *_dptrs(ptrs), *_dptrs(mask_ptrs), _lib.OSP_DEVICE,
+                     C.byref(cfg))
 
     def spgemm_partials_device(self, dtype, M, K, N, ptrs, *, k_range=None):
         """The multiply phase alone (``osp_spgemm_partials``): the product's partial products, unmerged, as packed records
         grouped by output row.  ``ptrs`` = six DEVICE addresses as in ``spgemm_csc_csr_device``.  ``result.nnz`` = P;
         ``result.partials_ptrs()`` borrows the arrays."""
         cfg = self._config(False, 0, k_range)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_spgemm_partials(self._h, _DT[np.dtype(dtype)], M, K, N, *[C.c_void_p(int(p)) for p in ptrs],
-                                                  _lib.OSP_DEVICE, C.byref(cfg), C.byref(h)))
-        return CsrResult(self, h)
+        return _call(self, "osp_spgemm_partials", self._h, _DT[np.dtype(dtype)], M, K, N, *_dptrs(ptrs), _lib.OSP_DEVICE, C.byref(cfg))
 
     def merge_record_parts_device(self, dtype, M, N, part_ptrs, *, partial_capacity=0, validate=False):
         """Sum parts given as (rowptr, records) DEVICE addresses (``osp_merge_record_parts``) into one CSR.
@@ -798,10 +721,7 @@ class Context:
         for i, (r, c) in enumerate(part_ptrs):
             rp[i], rc[i] = int(r), int(c)
         cfg = self._config(validate, partial_capacity, None)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_merge_record_parts(self._h, _DT[np.dtype(dtype)], M, N, n, rp, rc, _lib.OSP_DEVICE, C.byref(cfg),
-                                                     C.byref(h)))
-        return CsrResult(self, h)
+        return _call(self, "osp_merge_record_parts", self._h, _DT[np.dtype(dtype)], M, N, n, rp, rc, _lib.OSP_DEVICE, C.byref(cfg))
 
     def spgemm_csc_csr_panels(self, dtype, M, K, N, ptrs, on_panel, *, device=True, validate=False, partial_capacity=0,
                               k_range=None, row_shard=None):
@@ -825,7 +745,7 @@ class Context:
 
         fn = _lib.PANEL_FN(tramp)
         info = _lib.ResultInfo()
-        st = _lib.lib().osp_spgemm_csc_csr_panels(self._h, _DT[np.dtype(dtype)], M, K, N, *[C.c_void_p(int(p)) for p in ptrs],
+        st = _lib.lib().osp_spgemm_csc_csr_panels(self._h, _DT[np.dtype(dtype)], M, K, N, *_dptrs(ptrs),
                                                   _lib.OSP_DEVICE if device else _lib.OSP_HOST, C.byref(cfg), fn, None, C.byref(info))
         if err:
             raise err[0]
@@ -842,10 +762,7 @@ class Context:
             keep += [r, c, v]
             rp[i], ci[i], va[i] = r.ctypes.data, (c.ctypes.data if c.size else 0), (v.ctypes.data if v.size else 0)
         cfg = self._config(False, partial_capacity, None)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_merge_csr_parts(self._h, _DT[dt], M, N, n, rp, ci, va, _lib.OSP_HOST,
-                                                  C.byref(cfg), C.byref(h)))
-        return CsrResult(self, h)
+        return _call(self, "osp_merge_csr_parts", self._h, _DT[dt], M, N, n, rp, ci, va, _lib.OSP_HOST, C.byref(cfg), keep=keep)
 
     def merge_csr_parts_device(self, dtype, M, N, part_ptrs, *, partial_capacity=0):
         """Device-resident parts: list of (rowptr, colidx, vals) device addresses."""
@@ -854,30 +771,7 @@ class Context:
         for i, (r, c, v) in enumerate(part_ptrs):
             rp[i], ci[i], va[i] = int(r), int(c), int(v)
         cfg = self._config(False, partial_capacity, None)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_merge_csr_parts(self._h, _DT[np.dtype(dtype)], M, N, n, rp, ci, va,
-                                                  _lib.OSP_DEVICE, C.byref(cfg), C.byref(h)))
-        return CsrResult(self, h)
-
-    @staticmethod
-    def _coo_index_arg(v, space, what):
-        """An index list of ``build``: (address, count, keep-alive), taken as ``CsrResult.extract`` takes its lists.
-        ``space="host"``: an array-like of integers in [0, 2^32); ``space="device"``: a torch tensor of 4-byte integers (the
-        caller has synchronised its stream) or an ``(address, count)`` pair."""
-        if space == "host":
-            a = np.atleast_1d(np.asarray(v))
-            if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
-                raise OspError(_lib.ERR_ARG, f"{what} must be a one-dimensional list of integers")
-            a = a.astype(np.int64) if a.size else np.zeros(0, np.int64)
-            if a.size and (a.min() < 0 or a.max() > 0xffffffff):
-                raise OspError(_lib.ERR_ARG, f"{what} holds an index outside [0, 2^32)")
-            a = np.ascontiguousarray(a, np.uint32)
-            return (a.ctypes.data if a.size else 0), int(a.size), a
-        if hasattr(v, "data_ptr"):
-            if v.dim() != 1 or v.element_size() != 4 or v.is_floating_point() or not v.is_contiguous():
-                raise OspError(_lib.ERR_ARG, f"{what} must be a contiguous one-dimensional tensor of 4-byte integers")
-            return (v.data_ptr() if v.numel() else 0), int(v.numel()), v
-        return int(v[0]), int(v[1]), None
+        return _call(self, "osp_merge_csr_parts", self._h, _DT[np.dtype(dtype)], M, N, n, rp, ci, va, _lib.OSP_DEVICE, C.byref(cfg))
 
     def build(self, M, N, rows, cols, vals=None, *, dup="plus", dtype=np.float64, space="host"):
         """An M x N CSR result from the COO list (rows[t], cols[t], vals[t]) (``osp_csr_build``): any order, a coordinate may
@@ -888,15 +782,13 @@ class Context:
         ``(device address, count)`` pairs, with ``vals`` a tensor of ``dtype`` or a device address (``space="device"``: the
         caller has synchronised).  An index beyond its dimension is ``OspError(ERR_RANGE)`` on either path.  Returns
         (result, stats dict): nnz_in, nnz_out, long_runs, ms_total, launches, readbacks."""
-        if space not in ("device", "host"):
-            raise ValueError('space must be "device" or "host"')
-        if dup not in _lib.DUP_OPS:
-            raise ValueError(f"dup must be one of {' '.join(_lib.DUP_OPS)} (got {dup!r})")
+        b = _lib.Build()
+        b.space, b.dup = _space(space), _enum(_lib.DUP_OPS, dup, "dup")
         dt = np.dtype(dtype)
         if dt not in _DT:
             raise TypeError("dtype must be float32 or float64")
-        rp, nr, keep_r = self._coo_index_arg(rows, space, "rows")
-        cp, nc, keep_c = self._coo_index_arg(cols, space, "cols")
+        rp, nr, keep_r = _u32_list(rows, space, "rows")   # (an empty list: address 0, passed as NULL)
+        cp, nc, keep_c = _u32_list(cols, space, "cols")
         if nr != nc:
             raise OspError(_lib.ERR_ARG, f"rows and cols must have the same length (got {nr} and {nc})")
         vp, keep_v = None, None
@@ -912,23 +804,15 @@ class Context:
                 keep_v, vp = vals, (vals.data_ptr() if nr else None)
             else:
                 vp = int(vals)
-        b = _lib.Build()
-        b.M, b.N, b.nnz = int(M), int(N), nr
+        b.M, b.N, b.nnz, b.dtype = int(M), int(N), nr, _DT[dt]
         b.rows, b.cols, b.vals = rp or None, cp or None, vp
-        b.dtype, b.space, b.dup = _DT[dt], (_lib.OSP_HOST if space == "host" else _lib.OSP_DEVICE), _lib.DUP_OPS[dup]
-        stats = _lib.BuildStats()
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_csr_build(self._h, C.byref(b), C.byref(h), C.byref(stats)))
-        del keep_r, keep_c, keep_v
-        return CsrResult(self, h), stats.as_dict()
+        return _call(self, "osp_csr_build", self._h, C.byref(b), stats=_lib.BuildStats(), keep=(keep_r, keep_c, keep_v))
 
     def spgemm_mtx(self, path_a, path_b, transpose_b=True, dtype=np.float32, *, validate=True, partial_capacity=0):
         """The reference CLI's data flow: two .mtx files in, A * B^T (default) out."""
         cfg = self._config(validate, partial_capacity, None)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().osp_spgemm_mtx(self._h, _DT[np.dtype(dtype)], os.fsencode(path_a), os.fsencode(path_b),
-                                             int(bool(transpose_b)), C.byref(cfg), C.byref(h)))
-        return CsrResult(self, h)
+        return _call(self, "osp_spgemm_mtx", self._h, _DT[np.dtype(dtype)], os.fsencode(path_a), os.fsencode(path_b), int(bool(transpose_b)),
+                     C.byref(cfg))
 
 
 class MultiGpu:
@@ -948,13 +832,7 @@ class MultiGpu:
 
     def load(self, M, K, N, a_colptr, a_rowidx, a_vals, b_rowptr, b_colidx, b_vals):
         """Cut k into slabs and put every rank's slab on its GPU (host numpy operands).  Replaces what was loaded before."""
-        dt = np.dtype(a_vals.dtype)
-        if dt not in _DT or np.dtype(b_vals.dtype) != dt:
-            raise TypeError("values must both be float32 or both float64")
-        arrs = [np.ascontiguousarray(a_colptr, np.int64), np.ascontiguousarray(a_rowidx, np.uint32), np.ascontiguousarray(a_vals, dt),
-                np.ascontiguousarray(b_rowptr, np.int64), np.ascontiguousarray(b_colidx, np.uint32), np.ascontiguousarray(b_vals, dt)]
-        if len(arrs[0]) != K + 1 or len(arrs[3]) != K + 1:
-            raise OspError(_lib.ERR_DIM, f"pointer arrays must have K+1={K + 1} entries (got {len(arrs[0])} and {len(arrs[3])})")
+        dt, arrs = _csc_csr_arrays(K, a_colptr, a_rowidx, a_vals, b_rowptr, b_colidx, b_vals)
         self.unload()
         h = C.c_void_p()
         _lib.check(_lib.lib().osp_multi_operands_create(self._h, _DT[dt], M, K, N, *[_ptr(a) for a in arrs], C.byref(h)))
@@ -968,10 +846,7 @@ class MultiGpu:
     def multiply(self, *, validate=False, partial_capacity=0, fetch=True, checksum=False):
         """One product of the loaded operands.  Returns (info dict, (rowptr, colidx, vals) host arrays or None).
         checksum=True adds info["val_sum"] = the sum of all values of C, formed shard by shard on the GPUs (torch)."""
-        cfg = _lib.Config()
-        _lib.lib().osp_config_default(C.byref(cfg))
-        cfg.validate = int(bool(validate))
-        cfg.partial_capacity = int(partial_capacity or 0)
+        cfg = _config(validate, partial_capacity)
         h = C.c_void_p()
         _lib.check(_lib.lib().osp_spgemm_multi(self._h, self._ops, C.byref(cfg), C.byref(h)))
         try:
@@ -1092,23 +967,35 @@ def _as_coo(x):
     return x.shape[0], x.shape[1], x.row.astype(np.uint32), x.col.astype(np.uint32), x.data
 
 
-def spgemm(A, B, transpose_b=True, ctx=None, dtype=None):
-    """``A @ B.T`` (default, as the reference CLI) or ``A @ B`` as scipy CSR, computed on the GPU."""
-    ctx = ctx or default_context()
+def _product_operands(A, B, transpose_b, dtype, mask=None):
+    """What ``spgemm`` and ``spgemm_masked`` share: the operands checked and compressed on the host.  Returns (M, K, N, the six
+    arrays of A in CSC and B in CSR -- followed by the mask's row pointers and columns when a mask is given)."""
     M, K, ar, ac, av = _as_coo(A)
     br_n, bc_n, br, bc, bv = _as_coo(B)
     if transpose_b:
         br_n, bc_n, br, bc = bc_n, br_n, bc, br
     if br_n != K:
         raise OspError(_lib.ERR_DIM, f"inner dimensions differ: A is {M}x{K}, B is {br_n}x{bc_n}")
+    if mask is not None:
+        mm, mn, mr, mc, _ = _as_coo(mask)
+        if (mm, mn) != (M, bc_n):
+            raise OspError(_lib.ERR_ARG, f"the mask is {mm}x{mn}, the product {M}x{bc_n}")
     dt = np.dtype(dtype or np.result_type(av.dtype, bv.dtype))
     if dt not in _DT:
         dt = np.dtype(np.float64)
-    a = coo_to_csc(K, ar, ac, av.astype(dt))
-    b = coo_to_csr(K, br, bc, bv.astype(dt))
-    with_res = ctx.spgemm_csc_csr(M, K, bc_n, *a, *b)
-    out = with_res.to_scipy()
-    with_res.close()
+    arrs = coo_to_csc(K, ar, ac, av.astype(dt)) + coo_to_csr(K, br, bc, bv.astype(dt))
+    if mask is not None:
+        arrs += coo_to_csr(M, mr, mc, np.zeros(len(mr), np.float32))[:2]
+    return M, K, bc_n, arrs
+
+
+def spgemm(A, B, transpose_b=True, ctx=None, dtype=None):
+    """``A @ B.T`` (default, as the reference CLI) or ``A @ B`` as scipy CSR, computed on the GPU."""
+    ctx = ctx or default_context()
+    M, K, N, arrs = _product_operands(A, B, transpose_b, dtype)
+    res = ctx.spgemm_csc_csr(M, K, N, *arrs)
+    out = res.to_scipy()
+    res.close()
     return out
 
 
@@ -1117,22 +1004,8 @@ def spgemm_masked(A, B, mask, transpose_b=True, ctx=None, dtype=None):
     read), as scipy CSR.  An entry of the mask where no product exists is absent from the result; an entry whose products
     cancel is kept as an explicit 0."""
     ctx = ctx or default_context()
-    M, K, ar, ac, av = _as_coo(A)
-    br_n, bc_n, br, bc, bv = _as_coo(B)
-    if transpose_b:
-        br_n, bc_n, br, bc = bc_n, br_n, bc, br
-    if br_n != K:
-        raise OspError(_lib.ERR_DIM, f"inner dimensions differ: A is {M}x{K}, B is {br_n}x{bc_n}")
-    mm, mn, mr, mc, _ = _as_coo(mask)
-    if (mm, mn) != (M, bc_n):
-        raise OspError(_lib.ERR_ARG, f"the mask is {mm}x{mn}, the product {M}x{bc_n}")
-    dt = np.dtype(dtype or np.result_type(av.dtype, bv.dtype))
-    if dt not in _DT:
-        dt = np.dtype(np.float64)
-    a = coo_to_csc(K, ar, ac, av.astype(dt))
-    b = coo_to_csr(K, br, bc, bv.astype(dt))
-    m_rowptr, m_colidx, _ = coo_to_csr(M, mr, mc, np.zeros(len(mr), np.float32))
-    res = ctx.spgemm_masked(M, K, bc_n, *a, *b, m_rowptr, m_colidx)
+    M, K, N, arrs = _product_operands(A, B, transpose_b, dtype, mask)
+    res = ctx.spgemm_masked(M, K, N, *arrs)
     out = res.to_scipy()
     res.close()
     return out
