@@ -167,6 +167,15 @@ class MxdStats(_Stats):
     _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("cols", C.c_uint64), ("long_segments", C.c_uint64),
                 ("lanes_per_row", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float), ("reserved", C.c_uint32 * 7)]
 
+# the accum operators osp_csr_sddmm takes: osp_csr_apply_vectors' table (None passes VECTOR_NONE, which means "second")
+SDDMM_ACCUM_OPS = VECTOR_APPLY_OPS
+
+
+class SddmmStats(_Stats):
+    """osp_sddmm_stats_t"""
+    _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("cols", C.c_uint64), ("lanes_per_entry", C.c_uint32),
+                ("launches", C.c_uint32), ("ms_total", C.c_float), ("reserved", C.c_uint32 * 7)]
+
 class Transpose(_Stats):
     """osp_transpose_t"""
     _fields_ = [("reserved", C.c_uint32 * 8)]
@@ -273,6 +282,9 @@ MXV_EXPORTS = ["osp_csr_mxv"]
 # every symbol include/outerspace_spgemm_mxd.h declares
 MXD_EXPORTS = ["osp_csr_mxd"]
 
+# every symbol include/outerspace_spgemm_sddmm.h declares
+SDDMM_EXPORTS = ["osp_csr_sddmm"]
+
 # every symbol include/outerspace_spgemm_extract.h declares
 EXTRACT_EXPORTS = ["osp_csr_extract"]
 
@@ -367,6 +379,7 @@ def lib():
     L.osp_csr_transpose.argtypes = [vp, C.POINTER(Transpose), C.POINTER(vp), C.POINTER(TransposeStats)]
     L.osp_csr_mxv.argtypes = [vp, C.POINTER(Semiring), vp, vp, i32, C.POINTER(MxvStats)]
     L.osp_csr_mxd.argtypes = [vp, C.POINTER(Semiring), vp, u64, vp, i32, C.POINTER(MxdStats)]
+    L.osp_csr_sddmm.argtypes = [vp, C.POINTER(Semiring), i32, vp, vp, u64, i32, C.POINTER(vp), C.POINTER(SddmmStats)]
     L.osp_csr_extract.argtypes = [vp, C.POINTER(Extract), C.POINTER(vp), C.POINTER(ExtractStats)]
     L.osp_csr_build.argtypes = [vp, C.POINTER(Build), C.POINTER(vp), C.POINTER(BuildStats)]
     _lib = L

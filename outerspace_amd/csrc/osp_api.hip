@@ -31,6 +31,7 @@
 #include "../../include/outerspace_spgemm_transpose.h"
 #include "../../include/outerspace_spgemm_mxv.h"
 #include "../../include/outerspace_spgemm_mxd.h"
+#include "../../include/outerspace_spgemm_sddmm.h"
 #include "../../include/outerspace_spgemm_extract.h"
 #include "../../include/outerspace_spgemm_build.h"
 #include "osp_internal.h"
@@ -49,6 +50,7 @@
 #include "osp_transpose.h"
 #include "osp_mxv.h"
 #include "osp_mxd.h"
+#include "osp_sddmm.h"
 #include "osp_extract.h"
 #include "osp_build.h"
 
@@ -958,6 +960,22 @@ int osp_csr_mxd(osp_result_t in_, const osp_semiring_t *sr, const void *x, uint6
         if (!x && sr->mul != OSP_EWISE_FIRST) throw Error(OSP_ERR_ARG, "mxd: x may be null only when mul is FIRST");
         if (k > kMxdMaxCols) throw Error(OSP_ERR_ARG, "mxd: k exceeds OSP_MXD_MAX_COLS");
     }, [&](auto tag, osp_mxd_stats_t *st) { mxd_impl<decltype(tag)>(in->ctx, in, *sr, x, k, y, space, st); });
+}
+
+int osp_csr_sddmm(osp_result_t in_, const osp_semiring_t *sr, int accum, const void *x, const void *y, uint64_t k, osp_memspace_t space,
+                  osp_result_t *out, osp_sddmm_stats_t *stats) {
+    Result *in = (Result *)in_;
+    return csr_op({in}, sr != nullptr, out, stats, [&] {
+        check_space(space);
+        if (sr->add != OSP_EWISE_PLUS && sr->add != OSP_EWISE_MIN && sr->add != OSP_EWISE_MAX) throw Error(OSP_ERR_ARG, "sddmm: add is not one of PLUS, MIN, MAX");
+        if (sr->mul < OSP_EWISE_PLUS || sr->mul > OSP_EWISE_SECOND) throw Error(OSP_ERR_ARG, "sddmm: mul is not one of TIMES, PLUS, MIN, MAX, FIRST, SECOND");
+        check_reserved(sr->reserved, "sddmm");
+        if (accum != OSP_VECTOR_NONE && (accum < OSP_EWISE_PLUS || accum > OSP_EWISE_DIV || accum == OSP_EWISE_FIRST))
+            throw Error(OSP_ERR_ARG, "sddmm: accum is PLUS, TIMES, MINUS, DIV, MIN, MAX, SECOND or OSP_VECTOR_NONE");
+        if (!x && sr->mul != OSP_EWISE_SECOND) throw Error(OSP_ERR_ARG, "sddmm: x may be null only when mul is SECOND");
+        if (!y && sr->mul != OSP_EWISE_FIRST) throw Error(OSP_ERR_ARG, "sddmm: y may be null only when mul is FIRST");
+        if (k > kMxdMaxCols) throw Error(OSP_ERR_ARG, "sddmm: k exceeds OSP_MXD_MAX_COLS");
+    }, [&](auto tag, Result *res, osp_sddmm_stats_t *st) { sddmm_impl<decltype(tag)>(in->ctx, in, res, *sr, accum, x, y, k, space, st); });
 }
 
 int osp_csr_apply_vectors(osp_result_t in_, const osp_vector_apply_t *ap, const void *x_rows, const void *y_cols, osp_memspace_t space,

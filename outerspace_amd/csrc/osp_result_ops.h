@@ -1263,6 +1263,51 @@ static void mxd_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, c
                 (unsigned long long)long_segments, launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
 }
 
+// ---- the sampled dense-dense product on a result's pattern (osp_sddmm.h) ----
+template <class T>
+static void sddmm_impl(Context *ctx, const Result *in, Result *res, const osp_semiring_t &sr, int accum, const void *x_in, const void *y_in, uint64_t k,
+                       osp_memspace_t space, osp_sddmm_stats_t *st) {
+    typedef ValueBits<T> V;
+    OpFrame fr(ctx);
+    hipStream_t s = fr.s;
+    Scratch &sc = fr.sc;
+    const uint64_t M = in->info.M, N = in->info.N, nnz = in->info.nnz_c;
+    const int add = sr.add == OSP_EWISE_PLUS ? RED_PLUS : sr.add == OSP_EWISE_MIN ? RED_MIN : RED_MAX;
+    uint32_t lgk = 0;   // log2 of the lanes an entry gets: the power of two >= min(k, 64)
+    while (lgk < 6 && (1ull << lgk) < k) lgk++;
+    res->info = in->info;
+    uint32_t launches = 0;
+    if (M == 0 || nnz == 0) {
+        empty_result<T>(res, M, s);
+    } else {
+        const T *x = sr.mul == OSP_EWISE_SECOND ? nullptr : to_device(sc, (const T *)x_in, M * k, space, s);
+        // (x == y: one staging serves both)
+        const T *y = sr.mul == OSP_EWISE_FIRST ? nullptr : y_in == x_in && x && M == N ? x : to_device(sc, (const T *)y_in, N * k, space, s);
+        alloc_rowptr(res, M);
+        OSP_HIP(hipMemcpyAsync(res->rowptr, in->rowptr, (M + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        alloc_entries<T>(res, nnz);
+        OSP_HIP(hipMemcpyAsync(res->colidx, in->colidx, nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        mxv_with_ops(add, sr.mul, [&](auto a, auto m) {
+            constexpr int ADD = decltype(a)::value, MUL = decltype(m)::value;
+            // a wave per 64 entries
+            sddmm_kernel<T, ADD, MUL><<<grid_for((nnz + kWave - 1) / kWave, kReduceWaves), kReduceWaves * kWave, 0, s>>>(
+                in->rowptr, in->colidx, (const V *)in->vals, x, y, M, nnz, k, lgk, accum, (V *)res->vals);
+            launches++;
+        });
+    }
+    fr.finish(res, nnz);
+    *st = osp_sddmm_stats_t{};
+    st->nnz_in = st->nnz_out = nnz;
+    st->cols = k;
+    st->lanes_per_entry = 1u << lgk;
+    st->launches = launches;
+    st->ms_total = res->info.ms_total;
+    if (getenv("OSP_VERBOSE"))
+        fprintf(stderr, "[osp] sddmm add=%d mul=%d accum=%d M=%llu N=%llu k=%llu nnz=%llu lanes=%u launches=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
+                sr.add, sr.mul, accum, (unsigned long long)M, (unsigned long long)N, (unsigned long long)k, (unsigned long long)nnz, 1u << lgk, launches,
+                st->ms_total, (unsigned long long)ctx->malloc_calls);
+}
+
 template <class T, int OP = 0>
 static void launch_apply_rows(int op, hipStream_t s, const Result *in, const ValueBits<T> *src, const ValueBits<T> *x, Result *res) {
     if constexpr (OP < EW_OPS) {

@@ -11,7 +11,10 @@ which need the transpose of a result ``osp_csr_transpose`` (``strongly_connected
 ``bibliographic_coupling``), and global PageRank and connected components on the product of a result with a dense vector
 ``osp_csr_mxv`` (``pagerank``, ``connected_components``), and subgraphs as matrices of their own on the submatrix of a result
 ``osp_csr_extract`` (``induced_subgraph``, ``ego_network``, ``largest_component``), and matrices made from an edge list in
-one ``osp_csr_build`` (``adjacency_matrix``, ``laplacian``, ``incidence_matrix``, ``line_graph``, at the end).
+one ``osp_csr_build`` (``adjacency_matrix``, ``laplacian``, ``incidence_matrix``, ``line_graph``), and label spreading and
+feature propagation on the product of a result with a dense matrix ``osp_csr_mxd`` (``label_spreading``,
+``propagate_features``), and edge scores, landmark distance bounds and a factorisation of the observed entries on the sampled
+dense-dense product ``osp_csr_sddmm`` (``edge_scores``, ``landmark_bounds``, ``factorize``, at the end).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -1574,3 +1577,158 @@ def propagate_features(rows, cols, n=None, X=None, hops=2, *, self_loops=True, d
         return H.cpu().numpy(), info
     finally:
         _close_all(device, (A, eye, At, S))   # (At may be A or eye: closing twice is closing once)
+
+
+# ---- dense x dense on a result's pattern (osp_csr_sddmm): edge scores, landmark bounds, factorisation -------------------------------
+def _dense_on_device(X, rows, device, td, what):
+    """``X`` (an array-like or a torch tensor) as a contiguous (rows, k) tensor of ``td`` on the device."""
+    T = (X.to(device=device, dtype=td) if torch.is_tensor(X) else torch.as_tensor(np.asarray(X), device=device).to(td)).contiguous()
+    if T.dim() != 2 or T.shape[0] != rows:
+        raise ValueError(f"{what} must have shape ({rows}, k)")
+    return T
+
+
+def _result_coo(E):
+    """(u, v, values) of the CSR result E on the host, ascending by (u, v)."""
+    rowptr, colidx, vals = E.to_host()
+    return np.repeat(np.arange(E.shape[0], dtype=np.int64), np.diff(rowptr)), colidx.astype(np.int64), vals
+
+
+def _inverse_norms(T, td):
+    """1 / ||row|| of every row of T, the norm taken in float64 and a norm of 0 counting as 1, as a tensor of ``td``."""
+    nrm = T.double().pow(2).sum(dim=1).sqrt()
+    return (1.0 / torch.where(nrm == 0, torch.ones_like(nrm), nrm)).to(td)
+
+
+def edge_scores(rows, cols, n=None, X=None, Y=None, kind="dot", directed=False, *, dtype=np.float64, ctx=None):
+    """A score per edge of the graph with edges (rows[e], cols[e]) on vertices [0, n) from the vertex embeddings ``X`` (n x k)
+    and ``Y`` (n x k; None: X): ``kind="dot"`` is  X[u] . Y[v],  ``"cosine"`` that divided by ||X[u]|| ||Y[v]|| (a norm of 0
+    counts as 1, so the score is 0).  The pattern is deduplicated as ``pagerank`` does it (``directed=True``: self loops kept;
+    ``directed=False``: a simple graph, every edge once with u < v: ``select("triu", diag=1)`` of the symmetric pattern); the
+    dot products are ONE ``osp_csr_sddmm`` on it, in ``reduce``'s bit-defined order; the cosine is ONE ``apply_vectors`` of the
+    inverse norms after it.  The norms (taken in float64) are torch's.
+
+    Returns (u, v, score, info): the edges ascending by (u, v) as int64 arrays, the scores as a numpy array of ``dtype``;
+    info = nnz, k, launches, ms_sddmm, ms_apply.  n == 0 and a graph without edges launch nothing."""
+    if kind not in ("dot", "cosine"):
+        raise ValueError('kind must be "dot" or "cosine"')
+    if X is None:
+        raise ValueError("X is required")
+    ctx, device, dtype, n, A = _pattern_result(rows, cols, n, directed, dtype, ctx)
+    td = _torch_dtype(dtype)
+    info = {"nnz": 0, "k": 0, "launches": 0, "ms_sddmm": 0.0, "ms_apply": 0.0}
+    P = E = Z = None
+    try:
+        Xd = _dense_on_device(X, n, device, td, "X")
+        Yd = Xd if Y is None else _dense_on_device(Y, n, device, td, "Y")
+        if Yd.shape[1] != Xd.shape[1]:
+            raise ValueError("X and Y must have the same number of columns")
+        info["k"] = int(Xd.shape[1])
+        if A is None:
+            return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, dtype), info
+        P = A if directed else A.select("triu", diag=1)[0]
+        info["nnz"] = P.nnz
+        rx = ry = None
+        if kind == "cosine":
+            rx = _inverse_norms(Xd, td)
+            ry = rx if Yd is Xd else _inverse_norms(Yd, td)
+        torch.cuda.synchronize(device)   # the library works on its own stream
+        E, st = P.sddmm(Xd, Yd)
+        info["launches"], info["ms_sddmm"] = st["launches"], st["ms_total"]
+        if kind == "cosine":
+            Z, st = E.apply_vectors(rows=rx, row_op="times", cols=ry, col_op="times")
+            info["launches"] += st["launches"]
+            info["ms_apply"] = st["ms_total"]
+        u, v, score = _result_coo(Z if Z is not None else E)
+        return u, v, score.copy(), info
+    finally:
+        _close_all(device, (A, P, E, Z))   # (a directed P is A: closing twice is closing once)
+
+
+def landmark_bounds(rows, cols, n=None, landmarks=(0,), pairs=(), weights=None, *, dtype=np.float64, ctx=None):
+    """The landmark (triangle-inequality) upper bound  min_c d(c, u) + d(c, v)  of the distance of every vertex pair (u, v) of
+    ``pairs`` (a list of pairs, or an array of shape (q, 2); a pair may repeat) on the undirected graph ``shortest_paths``
+    reads from (rows, cols, weights), c running over ``landmarks``:  d = shortest_paths(.., landmarks)  is k x n,
+    D = d.T  is n x k, the distinct pairs are a pattern (``Context.build`` with ``dup="first"``), and
+    ``P.sddmm(D, D, "min", "plus")`` is the bound per pair, one IEEE addition per landmark and the minimum of those.
+
+    Returns (bound, info): ``bound`` numpy[q] of ``dtype`` in the callers' pair order, +inf where no landmark reaches both
+    ends (and for every pair when there is no landmark); info = landmarks, pairs, distinct_pairs, launches, ms_sddmm and
+    ``paths``, the info of ``shortest_paths``."""
+    pr = np.asarray(pairs, np.int64).reshape(-1, 2)
+    d, pinfo = shortest_paths(rows, cols, n, landmarks, weights=weights, dtype=dtype, ctx=ctx)
+    dtype, (k, n) = d.dtype.type, d.shape
+    if pr.size and (pr.min() < 0 or pr.max() >= n):
+        raise ValueError(f"pairs must lie in [0, {n})")
+    info = {"landmarks": int(k), "pairs": int(len(pr)), "distinct_pairs": 0, "launches": 0, "ms_sddmm": 0.0, "paths": pinfo}
+    if len(pr) == 0:
+        return np.zeros(0, dtype), info
+    ctx, device, dtype = _setup(dtype, ctx)
+    P = E = None
+    try:
+        D = torch.as_tensor(np.ascontiguousarray(d.T), device=device)
+        P, _ = ctx.build(n, n, pr[:, 0], pr[:, 1], None, dup="first", dtype=dtype, space="host")
+        info["distinct_pairs"] = P.nnz
+        torch.cuda.synchronize(device)   # the library works on its own stream
+        E, st = P.sddmm(D, D, "min", "plus")
+        info["launches"], info["ms_sddmm"] = st["launches"], st["ms_total"]
+        u, v, bound = _result_coo(E)
+        return bound[np.searchsorted(u * n + v, pr[:, 0] * n + pr[:, 1])], info
+    finally:
+        _close_all(device, (P, E))
+
+
+def factorize(rows, cols, vals, shape, rank, steps, lr, reg=0.0, U0=None, V0=None, seed=0, dup="error", *, dtype=np.float64, ctx=None):
+    """A rank-``rank`` factorisation  S ~ U V^T  of the M x N sparse matrix with the observed entries (rows[t], cols[t],
+    vals[t]) (``shape`` = (M, N); repeats combined by ``dup``, ``Context.build``'s operators) by ``steps`` steps of gradient
+    descent on  1/2 sum e^2 + reg/2 (|U|^2 + |V|^2)  over the OBSERVED entries, everything sparse on the GPU.  A step is
+    ``E = S.sddmm(U, V, accum="minus")``  (e = s - u.v on S's pattern),  ``gU = E.mxd(V)``,  ``gV = E.transpose().mxd(U)``,
+    then  U += lr (gU - reg U)  and  V += lr (gV - reg V),  both from the old U and V; the dense updates are torch's.
+    ``U0`` (M x rank) and ``V0`` (N x rank) default to  numpy.random.default_rng(seed).standard_normal / sqrt(rank),  U first.
+
+    Returns (U numpy (M, rank), V numpy (N, rank), info): info = nnz, steps, loss (a list: the sum of e^2 of every step's E,
+    that is BEFORE the step's update, summed in float64 on the device), launches, ms_sddmm and ms_mxd (lists, per step).
+    ``rank == 0``, ``steps == 0`` and an empty list are legal."""
+    M, N = (int(x) for x in shape)
+    rank, steps = int(rank), int(steps)
+    if M < 0 or N < 0 or rank < 0 or steps < 0:
+        raise ValueError("shape, rank and steps must not be negative")
+    ctx, device, dtype = _setup(dtype, ctx)
+    td = _torch_dtype(dtype)
+    rng = np.random.default_rng(seed)
+    init = [None, None]
+    for i, (given, m, what) in enumerate(((U0, M, "U0"), (V0, N, "V0"))):
+        a = np.asarray(given, dtype) if given is not None else (rng.standard_normal((m, rank)) / np.sqrt(max(rank, 1))).astype(dtype)
+        if a.shape != (m, rank):
+            raise ValueError(f"{what} must have shape ({m}, {rank})")
+        init[i] = torch.as_tensor(np.ascontiguousarray(a), device=device)
+    U, V = init
+    from .distributed import _as_tensor
+    info = {"nnz": 0, "steps": 0, "loss": [], "launches": 0, "ms_sddmm": [], "ms_mxd": []}
+    S = None
+    losses = []
+    try:
+        S, _ = ctx.build(M, N, rows, cols, vals, dup=dup, dtype=dtype, space="host")
+        info["nnz"] = S.nnz
+        for _ in range(steps):
+            E = Et = None
+            try:
+                torch.cuda.synchronize(device)   # the library works on its own stream
+                E, st = S.sddmm(U, V, accum="minus")
+                gU, su = E.mxd(V)
+                Et, _ = E.transpose()
+                gV, sv = Et.mxd(U)
+                e = _as_tensor(E.device_ptrs()[2], E.nnz, "<f4" if dtype == np.float32 else "<f8", device, td)
+                losses.append(e.double().pow(2).sum())
+                U, V = U + lr * (gU - reg * U), V + lr * (gV - reg * V)
+                del e
+            finally:
+                _close_all(device, (E, Et))
+            info["steps"] += 1
+            info["launches"] += st["launches"] + su["launches"] + sv["launches"]
+            info["ms_sddmm"].append(st["ms_total"])
+            info["ms_mxd"].append(su["ms_total"] + sv["ms_total"])
+        info["loss"] = [float(x) for x in torch.stack(losses).cpu()] if losses else []
+        return U.cpu().numpy(), V.cpu().numpy(), info
+    finally:
+        _close_all(device, (S,))

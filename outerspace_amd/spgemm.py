@@ -421,6 +421,50 @@ class CsrResult:
         _lib.check(_lib.lib().osp_csr_mxd(self._h, C.byref(sr), xp, k, yp, sp, C.byref(stats)))   # (keep_x and buf live until here)
         return ret, stats.as_dict()
 
+    def sddmm(self, X, Y, add="plus", mul="times", accum="second", space="device", k=None):
+        """The sampled dense-dense product on this CSR's (M x N) pattern as a new CSR result on the device
+        (``osp_csr_sddmm``): entry (i, j) gets ``accum(c, d)`` with c this result's value there and d the reduction, in
+        ``reduce``'s bit-defined order, of ``mul(X[i, c], Y[j, c])`` over c in [0, k) -- equal in bits to ``mxv`` of the
+        one-row CSR that holds ``X[i, :]`` with the vector ``Y[j, :]``.  ``X`` is M x k and ``Y`` N x k, row-major and
+        contiguous (``Y is X`` is allowed): 2-D torch tensors or device addresses (``space="device"``; an address carries no
+        shape, so ``k`` is needed) or array-likes (``space="host"``).  ``add`` is ``"plus" "min" "max"``, ``mul`` is ``"times"
+        "plus" "min" "max" "first" "second"``; ``"first"`` reads no ``Y`` and ``"second"`` no ``X`` (which may then be None).
+        ``accum`` is ``"plus" "times" "minus" "div" "min" "max" "second"`` with this result's value in a's place, or None,
+        which means ``"second"``: the value is d alone and no value of this result is read.  k == 0 gives the identity of
+        ``add`` for d.  Returns (result, stats dict): nnz_in, nnz_out, cols, lanes_per_entry, launches, ms_total."""
+        sr = _lib.Semiring()
+        sr.add, sr.mul = _enum(_lib.MXV_ADD_OPS, add, "add"), _enum(_lib.MXM_MUL_OPS, mul, "mul")
+        acc = _lib.VECTOR_NONE if accum is None else _enum(_lib.SDDMM_ACCUM_OPS, accum, "accum")
+        sp = _space(space)
+        M, N = self.shape
+        if X is None and mul != "second":
+            raise OspError(_lib.ERR_ARG, 'X may be None only when mul is "second"')
+        if Y is None and mul != "first":
+            raise OspError(_lib.ERR_ARG, 'Y may be None only when mul is "first"')
+        X, Y = (None if mul == "second" else X), (None if mul == "first" else Y)   # (an operand mul does not read is not looked at)
+        ks = {}   # the number of columns of every operand that carries a shape
+        for what, v, n in (("X", X, "M"), ("Y", Y, "N")):
+            shape = None if v is None else tuple(v.shape) if hasattr(v, "shape") else np.shape(v) if space == "host" else None
+            if shape is not None and len(shape) != 2:
+                raise OspError(_lib.ERR_ARG, f"{what} must be 2-D ({n} x k)")
+            if shape is not None:
+                ks[what] = shape[1]
+        if len(set(ks.values())) > 1:
+            raise OspError(_lib.ERR_ARG, f"X and Y must have the same number of columns (got {ks['X']} and {ks['Y']})")
+        if k is None:
+            if not ks:
+                raise OspError(_lib.ERR_ARG, "X and Y must be 2-D; with device addresses, pass k")
+            k = next(iter(ks.values()))
+        elif ks and next(iter(ks.values())) != int(k):
+            raise OspError(_lib.ERR_ARG, f"k = {k} differs from the operands' number of columns")
+        k = int(k)
+        if not 0 <= k <= _lib.MXD_MAX_COLS:
+            raise OspError(_lib.ERR_ARG, f"k must lie in [0, {_lib.MXD_MAX_COLS}] (got {k})")
+        xp, keep_x = _dense_arg(X, (M, k), self.dtype, space, "X", floating=True)
+        # (Y is X: one conversion, and the library sees one address)
+        yp, keep_y = (xp, keep_x) if Y is X and M == N else _dense_arg(Y, (N, k), self.dtype, space, "Y", floating=True)
+        return _call(self._ctx, "osp_csr_sddmm", self._h, C.byref(sr), acc, xp, yp, k, sp, stats=_lib.SddmmStats(), keep=(keep_x, keep_y))
+
     def apply_vectors(self, rows=None, row_op=None, cols=None, col_op=None, space="device"):
         """This CSR's pattern with every value ``col_op(row_op(c, rows[i]), cols[j])`` as a new CSR result on the device
         (``osp_csr_apply_vectors``).  Each op is ``"plus" "times" "minus" "div" "min" "max" "second"`` -- one IEEE operation
