@@ -58,7 +58,7 @@ typedef struct osp_mxm_stats {
  * osp_result_info(out): M, K, N of the call, row_begin = 0, row_end = M, nnz_a, nnz_b, nnz_c, partials = the number of
  * products, dtype and ms_total; every other field is 0.
  *
- * Rows are processed in consecutive batches of at most OSP_MXM_BATCH products (environment, read per call; default 2^24);
+ * Rows are processed in consecutive batches of at most OSP_MXM_BATCH products (environment, read per call: INTEGRATION.md section 7; default 2^24);
  * a single row with more is a batch of its own.  Temporary memory follows the batch, not the product count.  An output row
  * of at most OSP_MXM_SHORT_CAP products (default 1024, at most 1024) is SHORT: one wave forms, sorts and folds it in LDS.
  * A row with more is LONG: its products are expanded to a pool buffer, sorted by (row, column) with the library's stable

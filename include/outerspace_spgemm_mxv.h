@@ -51,7 +51,7 @@ typedef struct osp_mxv_stats {
  * without entries launches nothing: y is then M identities.
  *
  * Rows of at most g entries are packed 64 / g to a wave, g in {4, 8, 16, 32, 64} chosen per call from nnz / M (no
- * read-back); OSP_MXV_GROUP (environment, read per call) forces g.  g changes no bit of y.  Everything runs on the context's
+ * read-back); OSP_MXV_GROUP (environment, read per call: INTEGRATION.md section 7) forces g.  g changes no bit of y.  Everything runs on the context's
  * stream with temporary buffers from its pool; no float atomics, no waiting between workgroups; the only read-back is the
  * number of rows of more than 2048 entries per level, and only when `in` has more than 2048 entries.
  *

@@ -46,7 +46,7 @@ typedef struct osp_transpose_stats {
  * output row is the popcount of the word below its row's bit.  Nothing is sorted.  Everything else takes the SORT path: a
  * stable radix sort of the entries by column with 8-bit digits, ceil(bits(N - 1) / 8) passes and at least one; the input is
  * in row order, so a stable sort leaves ascending rows inside every column.  Both paths give the same three arrays.
- * Environment, read per call: OSP_TRANSPOSE_PATH=sort takes the sort path whatever M is (any other value: automatic);
+ * Environment, read per call (INTEGRATION.md section 7): OSP_TRANSPOSE_PATH=sort takes the sort path whatever M is (any other value: automatic);
  * OSP_TRANSPOSE_GATHER=bisect lets the sort's last pass find an entry's row by a bisection of in's row pointer and fetch its
  * value separately, where the default packs (row, value) records before the sort and fetches one record per entry.
  *

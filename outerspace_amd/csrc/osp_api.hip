@@ -174,7 +174,7 @@ static void spgemm_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
 
     // ---- k shard ----
     const uint64_t k0 = cfg.k_begin, k1 = cfg.k_end ? cfg.k_end : K;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] spgemm M=%llu K=%llu N=%llu nnzA=%lld nnzB=%lld k=[%llu,%llu) %s operands\n", (unsigned long long)M,
                 (unsigned long long)K, (unsigned long long)N, (long long)nnz_a, (long long)nnz_b, (unsigned long long)k0,
                 (unsigned long long)k1, space == OSP_HOST ? "host" : "device");
@@ -255,20 +255,20 @@ static void spgemm_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
     // Small products keep the split: the plan costs a handful of launches and a read-back, which a product of a few
     // milliseconds does not earn back (web-Google shape: 2.3 ms with the split, 2.7 with direct rows).  OSP_DIRECT_MIN_NNZ
     // moves that boundary (the tests set it to 0, so that their small inputs take the direct path).
-    const uint64_t direct_min_nnz = getenv("OSP_DIRECT_MIN_NNZ") ? strtoull(getenv("OSP_DIRECT_MIN_NNZ"), nullptr, 10) : ((getenv("OSP_GATHER") && atoi(getenv("OSP_GATHER")) == 0) ? (8ull << 20) : (2ull << 20));
+    const Settings &env = ctx->env;
+    const uint64_t direct_min_nnz = env.direct_min_nnz.or_((env.gather.set && env.gather.value == 0) ? (8ull << 20) : (2ull << 20));
     // ... unless its output rows are dense on average (at least 0.375 partial products per entry of the M x N result -- three times the
     // density from which a long row's column ranges are capped at the dense accumulators' width, plan_panel): such rows are
     // written in a few wide ranges, long runs, and summed without a sort -- 4096^2 with 880 entries per row (3.6 M non-zeros,
     // 3.2 G partial products) 44.4 -> 26.4 ms, Graph500 scale 14 ef 512 100 -> 79 ms.
     const bool dense_avg = (long double)p_all * 8.0L >= 3.0L * (long double)M * (long double)N;
     const bool direct = nnz && (nnz >= direct_min_nnz || dense_avg) && (uint64_t)nnz_b < 0xffffffffull && nnz < 0xffffffffull && !partials_only &&
-                        !(getenv("OSP_DIRECT") && atoi(getenv("OSP_DIRECT")) == 0);
-    const uint64_t direct_max = std::min<uint64_t>(getenv("OSP_DIRECT_MAX") ? strtoull(getenv("OSP_DIRECT_MAX"), nullptr, 10) : kSplitRowMax,
-                                                   kDirectDenseMax);   // (the planner counts a row's products in 21 bits)
+                        env.direct.on;
+    const uint64_t direct_max = std::min<uint64_t>(env.direct_max.or_(kSplitRowMax), kDirectDenseMax);   // (the planner counts a row's products in 21 bits)
     // Gathered rows (osp_kernels.h): the merge kernel forms the partial products of planned long rows and of short rows itself,
     // from run descriptors; on unless OSP_GATHER=0 (debugging aid, A/B timing: every row is then written by the multiply, as
     // until round 4) or the row-wise variant runs (its tile kernel is another instantiation).  OSP_GATHER=1: long rows only.
-    const int gather_env = getenv("OSP_GATHER") ? atoi(getenv("OSP_GATHER")) : 2;
+    const int gather_env = env.gather.or_(2);
     const bool gather_ok = nnz && !rowwise && !partials_only && (uint64_t)nnz_b < 0xffffffffull && nnz < 0xffffffffull;
     // (short rows: only where long rows are planned too -- a product of a few million non-zeros does not earn the tables back:
     // web-Google shape 2.09 -> 2.50 ms with them)
@@ -303,7 +303,7 @@ static void spgemm_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
         sym_row_offsets_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(rows_sorted, offs_sorted, nnz, M, row_off, rowfirst);
         const uint64_t rw_cap = (rowwise || gather_short) ? (uint64_t)TileCap<T>::value : 0ull;   // rows the multiply skips
         // (lazily where only rows written through cells would read them: DirectSrc::ensure_chunk_off)
-        const bool expand_rows_on = gather_short && !(getenv("OSP_EXPAND_ROWS") && atoi(getenv("OSP_EXPAND_ROWS")) == 0);
+        const bool expand_rows_on = gather_short && env.expand_rows.on;
         if (!expand_rows_on) sym_scatter_offsets_kernel<<<grid_for(nnz, 256), 256, 0, s>>>(perm, offs_sorted, rows_sorted, row_off, rw_cap, nnz, chunk_off);
         // (the product proper reads P together with the size of the result, merge_pipeline: one stream round trip less)
         if (partials_only || rowwise || row_sharded) P = d2h(offs_sorted + nnz, s);
@@ -392,7 +392,7 @@ static void spgemm_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
         copy_d2h(gs, dsrc.gstat, sizeof(gs), s);
         res->info.gathered_rows = gs[0]; res->info.gathered_partials = gs[1]; res->info.gathered_runs = gs[2];
     }
-    if (getenv("OSP_VERBOSE")) {
+    if (ctx->env.verbose) {
         fprintf(stderr, "[osp] product done in %.1f ms; pool misses so far: %llu hipMalloc calls, %.1f GB, %.1f ms\n", res->info.ms_total,
                 (unsigned long long)ctx->malloc_calls, ctx->malloc_bytes / 1e9, ctx->malloc_ms);
     }
@@ -524,7 +524,7 @@ static void merge_parts_impl(Context *ctx, Result *res, uint64_t M, uint64_t N, 
         nnz_in += nnz;
     }
     res->info.nnz_a = nnz_in;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] merge_csr_parts M=%llu N=%llu parts=%d entries=%llu %s operands\n", (unsigned long long)M,
                 (unsigned long long)N, nparts, (unsigned long long)nnz_in, space == OSP_HOST ? "host" : "device");
     const int64_t **d_rp = (const int64_t **)sc.get<void *>(nparts);
@@ -624,11 +624,12 @@ static void with_type(int dtype, F &&body) {
     if (dtype == OSP_F32) body(float{});
     else body(double{});
 }
-// Runs `body` on ctx's device.  When it throws, the stream is drained before the exception travels on: no buffer goes back
-// to the pool while work queued on it may still use it.
+// Runs `body` on ctx's device, under one snapshot of the environment's settings (ctx->env).  When it throws, the stream is
+// drained before the exception travels on: no buffer goes back to the pool while work queued on it may still use it.
 template <class F>
 static void on_device(Context *ctx, F &&body) {
     try {
+        ctx->begin_call();
         OSP_HIP(hipSetDevice(ctx->device));
         body();
     } catch (...) {
@@ -745,9 +746,10 @@ static int context_create(int device, void *stream, bool own, osp_context_t *out
             // Which stable rank this context uses.  The atomic one needs a property of LDS atomics that is not documented, so
             // it is tested here on THIS device; when the test fails the context falls back to the ballot instantiations of the
             // same kernels (slower -- merge +20 % -- and just as exact) instead of refusing to work.
-            const char *force = getenv("OSP_RANK");   // "ballot" | "atomic": debugging and tests/test_gpu_parity.py
-            if (force && strcmp(force, "ballot") == 0) c->rank_atomic = false;
-            else if (force && strcmp(force, "atomic") == 0) c->rank_atomic = true;
+            const Settings &env = c->env;
+            // OSP_RANK "ballot" | "atomic": debugging and tests/test_gpu_parity.py
+            if (env.rank.is("ballot")) c->rank_atomic = false;
+            else if (env.rank.is("atomic")) c->rank_atomic = true;
             if (c->rank_atomic) {
                 Scratch sc(c);
                 uint32_t *bad = sc.get<uint32_t>(1);
@@ -755,13 +757,12 @@ static int context_create(int device, void *stream, bool own, osp_context_t *out
                 rank_order_selftest_kernel<<<64, 256, 0, c->stream>>>(bad);
                 if (d2h(bad, c->stream) != 0) {
                     c->rank_atomic = false;
-                    if (getenv("OSP_VERBOSE")) fprintf(stderr, "[osp] LDS atomics do not return old values in lane order on this device: using ballot ranks\n");
+                    if (env.verbose) fprintf(stderr, "[osp] LDS atomics do not return old values in lane order on this device: using ballot ranks\n");
                 }
             }
-            const char *fadd = getenv("OSP_DENSE_ADD");
             for (int wide = 0; wide < 2; wide++) {
-                if (fadd && strcmp(fadd, "ballot") == 0) c->dense_atomic[wide] = false;
-                else if (fadd && strcmp(fadd, "atomic") == 0) c->dense_atomic[wide] = true;
+                if (env.dense_add.is("ballot")) c->dense_atomic[wide] = false;
+                else if (env.dense_add.is("atomic")) c->dense_atomic[wide] = true;
                 if (!c->dense_atomic[wide]) continue;
                 Scratch sc(c);
                 uint32_t *bad = sc.get<uint32_t>(1);
@@ -770,7 +771,7 @@ static int context_create(int device, void *stream, bool own, osp_context_t *out
                 else fadd_order_selftest_kernel<float><<<64, 256, 0, c->stream>>>(bad);
                 if (d2h(bad, c->stream) != 0) {
                     c->dense_atomic[wide] = false;
-                    if (getenv("OSP_VERBOSE"))
+                    if (env.verbose)
                         fprintf(stderr, "[osp] LDS %s atomics do not add in lane order (or flush subnormals) on this device: dense segments by ballot ranks\n",
                                 wide ? "f64" : "f32");
                 }
@@ -798,6 +799,7 @@ int osp_context_alloc(osp_context_t c_, uint64_t bytes, void **device_ptr) {
     Context *c = (Context *)c_;
     if (!c || !device_ptr) return fail(OSP_ERR_ARG, "null argument");
     return guard([&] {
+        c->begin_call();
         OSP_HIP(hipSetDevice(c->device));
         *device_ptr = c->alloc((size_t)bytes);
         return OSP_OK;
@@ -1255,6 +1257,7 @@ int osp_stream_copy_probe(osp_context_t ctx_, uint64_t bytes, int reps, double *
     if (!ctx || !gbps) return fail(OSP_ERR_ARG, "null argument");
     if (bytes < 4096 || reps < 1 || reps > 1000) return fail(OSP_ERR_ARG, "bytes >= 4096, 1 <= reps <= 1000");
     return guard([&]() -> int {
+        ctx->begin_call();
         OSP_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
         Scratch sc(ctx);
@@ -1345,6 +1348,7 @@ int osp_multi_operands_create(osp_multi_context_t mc_, osp_dtype_t dtype, uint64
         for (uint64_t k = 0; k < K; k++)
             if (a_colptr[k + 1] < a_colptr[k] || b_rowptr[k + 1] < b_rowptr[k] || a_colptr[0] != 0 || b_rowptr[0] != 0)
                 return fail(OSP_ERR_ARG, "pointer array is not a monotone 0..nnz sequence");
+        mc->begin_call();
         std::unique_ptr<MultiOperands> ops(new MultiOperands);
         ops->mc = mc; ops->dtype = dtype; ops->M = M; ops->K = K; ops->N = N;
         with_type(dtype, [&](auto tag) {
@@ -1367,6 +1371,7 @@ int osp_spgemm_multi(osp_multi_context_t mc_, osp_multi_operands_t ops_, const o
     if (ops->mc != mc) return fail(OSP_ERR_ARG, "operands belong to another multi-GPU context");
     return guard([&] {
         const osp_config_t cfg = config_or_default(cfg_);
+        mc->begin_call();
         std::unique_ptr<MultiResult> res(new MultiResult);
         res->mc = mc;
         res->dtype = ops->dtype;

@@ -4,6 +4,11 @@
 
 // ---- context: device, stream, buffer pool ------------------------------------------------------
 struct Context {
+    // the environment's settings (osp_settings.h) as the call in progress found them: taken when the context is constructed
+    // (OSP_RANK, OSP_DENSE_ADD) and again by every entry point that reaches device work (begin_call); everything below
+    // reads this, never the environment
+    Settings env = Settings::read();
+    void begin_call() { env = Settings::read(); }
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -60,12 +65,12 @@ struct Context {
     static constexpr size_t kGuard = 4096;
     struct GuardRec { char *base; size_t total, bytes; };
     std::map<void *, GuardRec> guarded;
-    static bool guard_mode() { static const bool g = getenv("OSP_GUARD") != nullptr; return g; }
+    static bool guard_mode() { return Settings::process().guard.set; }
     // OSP_GUARD=2 ("electric fence"): every buffer is mapped through the virtual-memory API so that it ENDS at the end
     // of its mapping, with the address range behind it left unmapped -- an access past the end of a buffer, READS
     // included, faults on the spot.  Nothing is ever unmapped or reused in this mode (small test inputs only): early
     // experiments that did unmap showed stale translations, which look like bugs and are not.
-    static bool fence_mode() { static const bool g = getenv("OSP_GUARD") && atoi(getenv("OSP_GUARD")) == 2; return g; }
+    static bool fence_mode() { return Settings::process().guard.set && Settings::process().guard.value == 2; }
     void *alloc_fenced(size_t bytes) {
         hipMemAllocationProp prop{};
         prop.type = hipMemAllocationTypePinned;
@@ -85,7 +90,7 @@ struct Context {
         OSP_HIP(hipMemSetAccess(va, map_size, &acc, 1));
         char *user = va + (map_size - bytes) / 16 * 16;
         OSP_HIP(hipMemsetAsync(va, 0xA5, map_size, stream));
-        if (getenv("OSP_VERBOSE")) fprintf(stderr, "[osp] fence: %zu bytes at [%p, %p), mapping ends at %p\n", bytes, (void *)user, (void *)(user + bytes), (void *)(va + map_size));
+        if (env.verbose) fprintf(stderr, "[osp] fence: %zu bytes at [%p, %p), mapping ends at %p\n", bytes, (void *)user, (void *)(user + bytes), (void *)(va + map_size));
         return user;
     }
     void *alloc_guarded(size_t bytes) {
@@ -177,15 +182,14 @@ struct Context {
             malloc_bytes += b;
             const double dt = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             malloc_ms += dt;
-            if (b >= (1ull << 30) && getenv("OSP_VERBOSE"))
+            if (b >= (1ull << 30) && env.verbose)
                 fprintf(stderr, "[osp]   pool miss: hipMalloc of %.2f GB took %.0f ms (pooled %.1f GB in %zu blocks, live %zu blocks)\n", b / 1e9, dt,
                         pooled_bytes / 1e9, free_list.size(), live.size());
         }
         live[p] = b;
         // debugging aid: OSP_POISON=1 fills every buffer with 0xFF bytes, so that a read of memory nobody
         // wrote fails the same way on every run instead of depending on what the pool hands back
-        static const bool poison = getenv("OSP_POISON") != nullptr;
-        if (poison) (void)hipMemsetAsync(p, 0xff, b, stream);
+        if (Settings::process().poison) (void)hipMemsetAsync(p, 0xff, b, stream);
         return p;
     }
     void release(void *p) {
@@ -311,8 +315,7 @@ static void crumbs_dump(const char *what) {
 }
 #endif
 static inline void dbg_sync(hipStream_t s, const char *what) {
-    static const bool on = getenv("OSP_SYNC") != nullptr;
-    if (!on) return;
+    if (!Settings::process().sync) return;
     const hipError_t e1 = hipStreamSynchronize(s), e2 = hipGetLastError();
 #ifdef OSP_CHECK_DESC
     if (e1 != hipSuccess || e2 != hipSuccess) crumbs_dump(what);

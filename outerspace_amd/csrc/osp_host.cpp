@@ -136,7 +136,8 @@ int osp_mtx_read(const char *path, int symmetric, uint64_t *nrow, uint64_t *ncol
         }
         const size_t body = (size_t)(end - p);
         unsigned nthreads = 1;
-        if (const char *env = getenv("OSP_PARSE_THREADS")) nthreads = (unsigned)std::max(1, atoi(env));
+        const osp::Settings env = osp::Settings::read();
+        if (env.parse_threads.set) nthreads = (unsigned)std::max(1, env.parse_threads.value);
         else nthreads = (unsigned)std::min<size_t>(std::min<size_t>(32, std::max(1u, std::thread::hardware_concurrency())), body / (4u << 20) + 1);
         std::vector<MtxPiece> pieces(nthreads);
         // an entry takes at least four bytes of the file ("1 1\n"): a header that announces more than the file can hold

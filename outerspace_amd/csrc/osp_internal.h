@@ -5,6 +5,7 @@
 #include <string>
 
 #include "../../include/outerspace_spgemm.h"
+#include "osp_settings.h"
 
 namespace osp {
 

@@ -47,6 +47,12 @@ struct MultiContext {
     std::vector<Context *> ctx;        // one context (stream + pool) per rank: symbolic phase, multiply
     std::vector<Context *> mctx;       // a second one per rank for the merge of what arrives: it runs beside the multiply
     std::vector<std::vector<hipStream_t>> copy;   // copy[g][h]: the stream of rank g's copies to rank h (one per link)
+    // one snapshot of the environment's settings per call, shared by all its contexts (the rank threads only read it)
+    void begin_call() {
+        const Settings env = Settings::read();
+        for (Context *c : ctx) c->env = env;
+        for (Context *c : mctx) c->env = env;
+    }
     ~MultiContext() {
         for (size_t g = 0; g < ctx.size(); g++) {
             if (!ctx[g]) continue;
@@ -423,7 +429,7 @@ static void multi_rank_main(MultiContext *mc, const MultiOperands *ops, MultiSha
 template <class T>
 static void multi_product(MultiContext *mc, const MultiOperands *ops, MultiResult *out, const osp_config_t &cfg) {
     const int G = (int)mc->ctx.size();
-    int R = getenv("OSP_MULTI_SUBPANELS") ? atoi(getenv("OSP_MULTI_SUBPANELS")) : 4;
+    int R = mc->ctx[0]->env.multi_subpanels.or_(4);
     R = std::max(1, std::min(R, 64));
     if (ops->M < (uint64_t)G * R) R = 1;
     MultiShared<T> sh(G, R);

@@ -198,16 +198,14 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
     // OSP_PLAN_SMALL_CHUNKS move the limits (measurements; tests reach both sides of them).
     uint8_t *hsmall = sc.get<uint8_t>(nlong);
     SmallLimits small_lim{};
-    if (want_gather && !(getenv("OSP_PLAN_SMALL") && atoi(getenv("OSP_PLAN_SMALL")) == 0) &&
-        !(getenv("OSP_GATHER_OVER") && atoi(getenv("OSP_GATHER_OVER")) == 0)) {
-        small_lim.cells = (uint32_t)std::clamp<long>(getenv("OSP_PLAN_SMALL_CELLS") ? atol(getenv("OSP_PLAN_SMALL_CELLS")) : (long)kSmallCells,
-                                                     (long)kSmallCellsMin, (long)kSmallCellsMax);
-        small_lim.chunks = (uint32_t)std::clamp<long>(getenv("OSP_PLAN_SMALL_CHUNKS") ? atol(getenv("OSP_PLAN_SMALL_CHUNKS")) : (long)kSmallChunks,
-                                                      1L, (long)kSmallChunks);
+    const Settings &env = ctx->env;
+    if (want_gather && env.plan_small.on && env.gather_over.on) {
+        small_lim.cells = (uint32_t)std::clamp<long>(env.plan_small_cells.or_((long)kSmallCells), (long)kSmallCellsMin, (long)kSmallCellsMax);
+        small_lim.chunks = (uint32_t)std::clamp<long>(env.plan_small_chunks.or_((long)kSmallChunks), 1L, (long)kSmallChunks);
     }
     uint64_t nsmall = 0;
     // debugging aid: OSP_SPLIT_ROW_MAX moves the boundary between the two split kernels (tests run both on small inputs)
-    const uint64_t row_max = getenv("OSP_SPLIT_ROW_MAX") ? strtoull(getenv("OSP_SPLIT_ROW_MAX"), nullptr, 10) : kSplitRowMax;
+    const uint64_t row_max = env.split_row_max.or_(kSplitRowMax);
     // no more ranges than make a range as narrow as the dense accumulators take (osp_split.h, kDenseBits): beyond that
     // a finer split only shortens the runs the scatter writes -- whatever a range of <= 2048 columns holds is summed
     // without a sort.  It bites for rows with more than one product per 8 columns of B (kSplitTarget = 256 per 2048 columns).  (Until late in round 3 the cap
@@ -219,7 +217,7 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
     // being moved by the stretch split afterwards.  It needs the lane order of LDS atomics (the context's self-test) and B's
     // run table; OSP_HUB=0 keeps the stretch split (debugging aid, A/B timing).
     const int hub_b_want = std::min(kSplitMaxBits, bits_cap);
-    const bool hub_env = !(getenv("OSP_HUB") && atoi(getenv("OSP_HUB")) == 0);
+    const bool hub_env = env.hub.on;
     int hub_b = 0;
     uint64_t ndcell = 0, tot[6] = {0, 0, 0, 0, 0, 0};
     // ... and it pays only where such rows hold a good part of the panel's products: the multiply of a panel with hub rows is
@@ -228,7 +226,7 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
     // more than half of the products); R-MAT-22 "mild" (2 %) 236 -> 250 ms.  OSP_HUB_MIN_SHARE moves the threshold.
     // fine bins of the direct rows' planner: 2^direct_fine per kSplitTarget products (osp_split.h, split_params_kernel)
     const int direct_fine = 2;   // (0 = the bins of round 3; measured in round 4, MEASUREMENTS 1.x: the ranges fill their tiles to 97 % instead of 92)
-    const double hub_min_share = getenv("OSP_HUB_MIN_SHARE") ? atof(getenv("OSP_HUB_MIN_SHARE")) : 0.2;
+    const double hub_min_share = env.hub_min_share.or_(0.2);
     bool hub_decided = false;
     for (int attempt = 0; attempt < 3; attempt++) {
         const bool hub_possible = ds && ds->b_rowptr && ds->keep && ctx->rank_atomic && hub_env && !ds->hub_refused;
@@ -274,7 +272,7 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
     res->info.direct_partials += pl.mode_partials[kModeDirect];
     if (pl.ncell >= 0xffffffffull || pl.nblocks >= 0x7fffffffull || pl.nvirt >= 0xffffffffull || ndcell >= 0xffffffffull)
         throw Error(OSP_ERR_CAPACITY, "split histogram too large");
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp]   panel rows [%llu,%llu): %u tiles, %u long rows with %llu partial products -> %llu segments; direct: %llu rows, %llu "
                         "partial products, %llu cells\n",
                 (unsigned long long)r0, (unsigned long long)r1, pl.p0.ntiles, nlong, (unsigned long long)pl.nh, (unsigned long long)pl.nvirt,
@@ -291,7 +289,7 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
         RunDesc<T> *runs = nullptr;
         // (the run table is addressed with 32 bits; a panel whose bound does not fit writes its direct rows as before)
         // (debugging aid: OSP_GATHER_MAX_RUNS lowers that limit, so that a test reaches the fallback)
-        static const uint64_t max_runs = getenv("OSP_GATHER_MAX_RUNS") ? strtoull(getenv("OSP_GATHER_MAX_RUNS"), nullptr, 10) : 0xffffffffull;
+        const uint64_t max_runs = env.gather_max_runs.or_(0xffffffffull);
         if (ds->gather && nrund && nrd < max_runs) {
             runs = sc.get<RunDesc<T>>(std::max<uint64_t>(nrd, 1));
             pl.vrun_off = sc.get<uint32_t>(pl.nvirt + 1);
@@ -302,7 +300,7 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
             // kNoRuns: segments / rows that are not gathered (ONE kernel: a hipMemsetAsync costs the host tens of microseconds)
             fill_async(s, {{pl.vrun_off, (pl.nvirt + 1) * sizeof(uint32_t), kNoRuns}, {gp.rowruns, (uint64_t)nlong * sizeof(uint32_t), kNoRuns},
                            {pl.nwritten, sizeof(uint32_t), 0u}});
-            gp.over = !(getenv("OSP_GATHER_OVER") && atoi(getenv("OSP_GATHER_OVER")) == 0);
+            gp.over = env.gather_over.on;
             gp.av_in_order = ds->av_in_order ? 1u : 0u;
             pl.may_write = !gp.over;
             pl.ga.runs = runs; pl.ga.b_colidx = ds->b_colidx; pl.ga.b_vals = (const T *)ds->b_vals;
@@ -315,7 +313,7 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
         const bool plan_small = runs != nullptr && gp.over && nsmall != 0;
         const bool plan_big = !plan_small || nsmall < pl.mode_rows[kModeDirect];
         if (plan_small) gp.small = hsmall;
-        if (getenv("OSP_VERBOSE"))
+        if (ctx->env.verbose)
             fprintf(stderr, "[osp]   small planner: %llu of %llu direct rows (at most %u chunks, %u cells)\n", (unsigned long long)(plan_small ? nsmall : 0),
                     (unsigned long long)pl.mode_rows[kModeDirect], small_lim.chunks, small_lim.cells);
         tm.begin(PH_PLAN_K, s);
@@ -336,7 +334,7 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
         tm.end(PH_PLAN_K);
         if (gp.rowruns && ds->gstat) gather_stats_kernel<<<std::min(grid_for(nlong, 256), 64u), 256, 0, s>>>(pl.p0.long_rows, nlong, row_off, gp.rowruns, ds->gstat);
 #ifdef OSP_PLAN_PROF
-        if (getenv("OSP_VERBOSE")) {
+        if (ctx->env.verbose) {
             unsigned long long hp[8] = {0}, z[8] = {0};
             OSP_HIP(hipStreamSynchronize(s));
             (void)hipMemcpyFromSymbol(hp, HIP_SYMBOL(osp_plan_prof), sizeof(hp));
@@ -400,11 +398,11 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
         // lost -- 324-354 against 315 ms -- and the threshold was six, or 4.5 where the stretch split's rounds were shorter still.)
         // Otherwise the panel -- and the rest of the product -- keeps the stretch split (with the blocks already chosen: its
         // histogram has the same layout).
-        if (getenv("OSP_VERBOSE"))
+        if (ctx->env.verbose)
             fprintf(stderr, "[osp]   hub rows: %llu rows, %llu products in %llu runs (%.2f records per run), %llu jobs, 2^%d blocks\n",
                     (unsigned long long)pl.mode_rows[kModeStretch], (unsigned long long)pl.mode_partials[kModeStretch], (unsigned long long)ncells,
                     ncells ? (double)pl.mode_partials[kModeStretch] / (double)ncells : 0.0, (unsigned long long)pl.nblocks, hub_b);
-        const double min_run = getenv("OSP_HUB_MIN_RUN") ? atof(getenv("OSP_HUB_MIN_RUN")) : 4.0;
+        const double min_run = env.hub_min_run.or_(4.0);
         const double run = ncells ? (double)pl.mode_partials[kModeStretch] / (double)ncells : 0.0;
         const bool accept = run >= min_run;
         if (!accept) {
@@ -435,7 +433,7 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
     if (ds && ds->expand_rows) {
         pl.expand_ok = true;
         const bool hubs = pl.hub.cells != nullptr;
-        const int from_b_env = getenv("OSP_SPLIT_FROM_B") ? atoi(getenv("OSP_SPLIT_FROM_B")) : 1;
+        const int from_b_env = env.split_from_b.or_(1);
         if (!hubs && pl.nblocks != 0 && from_b_env != 0) pl.split_from_b = ds;
         // (2: from B, but where the split of records runs -- in merge_panel, after the join.  Kept, like OSP_PLAN_OVERLAP=0, as the
         // A/B switch of the placement alone: what the overlap gains depends on how full the next panel's plan keeps the CUs, which
@@ -444,7 +442,7 @@ static void plan_panel(Context *ctx, Result *res, PhaseTimer &tm, PanelPlan<T> &
         const bool stretch_x = !hubs && !pl.split_from_b;   // the stretch rows are expanded too
         const uint64_t rows_x = pl.mode_rows[kModeSplitRow] + (stretch_x ? pl.mode_rows[kModeStretch] : 0);
         pl.xpartials = pl.mode_partials[kModeSplitRow] + (stretch_x ? pl.mode_partials[kModeStretch] : 0);
-        if (getenv("OSP_VERBOSE") && pl.nblocks && !hubs)
+        if (ctx->env.verbose && pl.nblocks && !hubs)
             fprintf(stderr, "[osp]   stretch rows: %llu rows, %llu partial products split %s\n", (unsigned long long)pl.mode_rows[kModeStretch],
                     (unsigned long long)pl.mode_partials[kModeStretch], pl.split_from_b ? (pl.split_beside ? "from B" : "from B, after the join") : "from staged records");
         if (rows_x) {
@@ -568,7 +566,7 @@ static void merge_panel(Context *ctx, Result *res, PhaseTimer &tm, const MergeIO
             uint32_t *hscan = sc.get<uint32_t>((uint64_t)nseg_long + 1);
             uint64_t *sscan_tmp = sc.get<uint64_t>(scan_scratch_entries(nseg_long));  // NOT hscan_tmp: that one is sized for nlong
             {
-                const SegDenseFlag df{p1.long_rows, pl.vcol0, pl.vcol1, getenv("OSP_DENSE_SEG") ? atoi(getenv("OSP_DENSE_SEG")) : 1};
+                const SegDenseFlag df{p1.long_rows, pl.vcol0, pl.vcol1, ctx->env.dense_seg.or_(1)};
                 device_exclusive_scan<SegDenseFlag, uint32_t>(df, nseg_long, hscan, (uint32_t *)sscan_tmp, s);
                 const uint32_t ndense = d2h(hscan + nseg_long, s);
                 if (ndense) {
@@ -588,8 +586,7 @@ static void merge_panel(Context *ctx, Result *res, PhaseTimer &tm, const MergeIO
             dbg_sync(s, "over-long segments: dense accumulation");
             // the rest by length: up to kBigTileCap -> one big LDS tile each, reduced in place; beyond -> global sort
             // (debugging aid: OSP_BIGTILE_CAP=0 sends every such segment down the global-sort path)
-            const uint32_t big_cap = getenv("OSP_BIGTILE_CAP") ? std::min<uint32_t>((uint32_t)strtoul(getenv("OSP_BIGTILE_CAP"), nullptr, 10), kBigTileCap)
-                                                                : (uint32_t)kBigTileCap;
+            const uint32_t big_cap = std::min<uint32_t>((uint32_t)ctx->env.bigtile_cap.or_(kBigTileCap), kBigTileCap);
             uint32_t nhuge = 0, nmid = 0;
             uint32_t *huge_list = nullptr, *mid_list = nullptr;
             if (nrest) {
@@ -684,7 +681,7 @@ static void merge_panel(Context *ctx, Result *res, PhaseTimer &tm, const MergeIO
     tm.end(PH_MERGE_K);
     dbg_sync(s, "merge tiles");
 #ifdef OSP_MERGE_PROF
-    if (getenv("OSP_VERBOSE")) {   // the tiles by sort passes (key bits) and fill
+    if (ctx->env.verbose) {   // the tiles by sort passes (key bits) and fill
         std::vector<TileDesc> hd(ntot);
         copy_d2h(hd.data(), desc, (size_t)ntot * sizeof(TileDesc), s);
         uint64_t byp[5] = {0}, ent[5] = {0}, gt = 0, ge = 0, gr = 0, bits[33] = {0};
@@ -716,7 +713,7 @@ static void merge_panel(Context *ctx, Result *res, PhaseTimer &tm, const MergeIO
                 slots ? 100.0 * run / slots : 0.0, lpt, kTileRoundClasses);
         fprintf(stderr, "\n");
     }
-    if (getenv("OSP_VERBOSE")) {   // (`make prof`: cycles of thread 0 of every workgroup between the kernel's marks)
+    if (ctx->env.verbose) {   // (`make prof`: cycles of thread 0 of every workgroup between the kernel's marks)
         unsigned long long hp[16] = {0}, z[16] = {0};
         OSP_HIP(hipStreamSynchronize(s));
         (void)hipMemcpyFromSymbol(hp, HIP_SYMBOL(osp_merge_prof), sizeof(hp));
@@ -832,7 +829,7 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
     const double per_record = sink ? 3.7 : (ds && ds->gather) ? 2.5 : 2.6;
     if (cap == 0) cap = std::max<uint64_t>((uint64_t)(free_b * 0.85 / (per_record * E)), 1ull << 20);
     cap = std::min<uint64_t>(cap, 0xfffffff0ull);  // staging positions are u32
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] M=%llu N=%llu P=%llu nnzC<=%llu (%.1f GB) free %.1f GB -> staging capacity %llu partial products (%.1f GB)\n",
                 (unsigned long long)M, (unsigned long long)N, (unsigned long long)P, (unsigned long long)cap_c, cap_c * E / 1e9,
                 free_b / 1e9, (unsigned long long)cap, cap * E / 1e9);
@@ -884,7 +881,7 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
     // plan takes from the pool are no longer in use by panel p-1's merge); join: the first stream waits for the plan before
     // panel p's merge (whose scratch may be what the plan has just given back).  OSP_PLAN_OVERLAP=0 plans every panel in
     // line, before its own multiply (debugging aid, A/B timing).
-    const bool overlap = npanels > 1 && !(getenv("OSP_PLAN_OVERLAP") && atoi(getenv("OSP_PLAN_OVERLAP")) == 0);
+    const bool overlap = npanels > 1 && ctx->env.plan_overlap.on;
     if (overlap) ctx->need_aux();
     struct AuxScope {   // ctx->stream is the second stream while this lives
         Context *c; hipStream_t main;
@@ -1033,7 +1030,7 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
     // keeps its bound-sized arrays until it is destroyed, and they go back to the pool whole.
     const uint64_t waste = (Context::bucket(std::max<uint64_t>(cap_c, 1) * sizeof(T)) - Context::bucket(std::max<uint64_t>(nnz_total, 1) * sizeof(T))) +
                            (Context::bucket(std::max<uint64_t>(cap_c, 1) * sizeof(uint32_t)) - Context::bucket(std::max<uint64_t>(nnz_total, 1) * sizeof(uint32_t)));
-    const uint64_t min_waste = getenv("OSP_COMPACT_MIN_WASTE") ? strtoull(getenv("OSP_COMPACT_MIN_WASTE"), nullptr, 10) : (uint64_t)(total_b / 10);
+    const uint64_t min_waste = ctx->env.compact_min_waste.or_((uint64_t)(total_b / 10));
     res->info.output_slack_bytes = waste;
     if (Context::bucket(std::max<uint64_t>(nnz_total, 1) * sizeof(T)) * 10 < Context::bucket(std::max<uint64_t>(cap_c, 1) * sizeof(T)) * 7 &&
         waste >= min_waste) {

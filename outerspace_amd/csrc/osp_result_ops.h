@@ -284,12 +284,6 @@ static void masked_view(Context *ctx, Scratch &sc, uint64_t nseg_minor, uint64_t
     OSP_HIP(hipStreamSynchronize(s));   // (ss goes back to the pool)
 }
 
-// unsigned setting from the environment, or `dflt`
-static uint64_t env_u64(const char *name, uint64_t dflt) {
-    const char *v = getenv(name);
-    return v && *v ? strtoull(v, nullptr, 10) : dflt;
-}
-
 template <class T>
 static void masked_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint64_t N, const int64_t *a_colptr_in, const uint32_t *a_rowidx_in,
                         const T *a_vals_in, const int64_t *b_rowptr_in, const uint32_t *b_colidx_in, const T *b_vals_in,
@@ -361,8 +355,8 @@ static void masked_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
     zero_async(s, {{products, sizeof(uint64_t)}, {count, kMaskedBuckets * sizeof(uint32_t)}});
     uint32_t launches = 0;
     if (nm) {
-        const uint32_t heavy_min = (uint32_t)std::min<uint64_t>(env_u64("OSP_MASKED_HEAVY_MIN", kMaskedHeavyMin), 0xffffffffull);
-        const int bucketed = env_u64("OSP_MASKED_BUCKET", 1) ? 1 : 0;
+        const uint32_t heavy_min = (uint32_t)std::min<uint64_t>(ctx->env.masked_heavy_min.or_(kMaskedHeavyMin), 0xffffffffull);
+        const int bucketed = ctx->env.masked_bucket.or_(1) ? 1 : 0;
         Scratch ss(ctx);
         uint32_t *key = ss.get<uint32_t>(nm), *order = ss.get<uint32_t>(nm);
         csr_expand_rows_kernel<<<grid_for(M * kWave, 256), 256, 0, s>>>(m_rowptr, M, m_row);
@@ -403,7 +397,7 @@ static void masked_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
     res->info.ms_ingest = ev_in.ms();
     res->info.ms_multiply_kernel = ev_k.ms();
     res->info.multiply_launches = launches;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] masked M=%llu K=%llu N=%llu nnzA=%lld nnzB=%lld nnzM=%lld nnzC=%llu products=%llu launches=%u %.3f ms\n",
                 (unsigned long long)M, (unsigned long long)K, (unsigned long long)N, (long long)nnz_a, (long long)nnz_b, (long long)nnz_m,
                 (unsigned long long)nnz_c, (unsigned long long)P, launches, res->info.ms_total);
@@ -420,7 +414,7 @@ static void inflate_prune_impl(Context *ctx, const Result *in, Result *res, cons
     const T *val = (const T *)in->vals;
     const T thr = (T)step.threshold, power = (T)step.power;
     const int mode = step.power == 1.0 ? MCL_POW_ONE : step.power == 2.0 ? MCL_POW_SQUARE : MCL_POW_GENERAL;
-    const uint32_t long_min = (uint32_t)std::min<uint64_t>(env_u64("OSP_MCL_LONG_MIN", kMclLongMin), 0xffffffffull);
+    const uint32_t long_min = (uint32_t)std::min<uint64_t>(ctx->env.mcl_long_min.or_(kMclLongMin), 0xffffffffull);
     uint32_t launches = 0;
 
     unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MCL_COUNTERS);
@@ -504,7 +498,7 @@ static void inflate_prune_impl(Context *ctx, const Result *in, Result *res, cons
     st->ms_total = res->info.ms_total;
     st->ms_select_kernel = ev_k.ms();
     st->launches = launches + 1;   // (the counters' zeroing)
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] inflate_prune M=%llu nnz %llu -> %llu capped=%llu rescued=%llu long=%llu chaos=%.3e %.3f ms (select %.3f)\n",
                 (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)nnz, (unsigned long long)capped, (unsigned long long)rescued,
                 (unsigned long long)n_long, st->chaos, st->ms_total, st->ms_select_kernel);
@@ -575,7 +569,7 @@ static void apply_mask_impl(Context *ctx, const Result *in, Result *res, const i
     st->nnz_out = c.nnz;
     st->ms_total = res->info.ms_total;
     st->launches = launches;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] apply_mask%s M=%llu nnz %llu -> %llu (mask %llu) launches=%u %.3f ms\n", complement ? " (complement)" : "",
                 (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)c.nnz, (unsigned long long)nnz_m, launches, st->ms_total);
 }
@@ -626,7 +620,7 @@ static void select_impl(Context *ctx, const Result *in, Result *res, const osp_s
     st->nnz_out = c.nnz;
     st->ms_total = res->info.ms_total;
     st->launches = c.launches;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] select op=%d%s M=%llu nnz %llu -> %llu launches=%u %.3f ms\n", sel.op, sel.fill ? " (fill)" : "",
                 (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)c.nnz, c.launches, st->ms_total);
 }
@@ -714,7 +708,7 @@ static void ewise_impl(Context *ctx, const Result *a, const Result *b, Result *r
     st->nnz_out = nnz_out;
     st->ms_total = res->info.ms_total;
     st->launches = launches;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] ewise %s op=%d M=%llu nnz %llu , %llu -> %llu (both %llu) launches=%u %.3f ms\n", uni ? "union" : "intersect", ew.op,
                 (unsigned long long)M, (unsigned long long)nnz_a, (unsigned long long)nnz_b, (unsigned long long)nnz_out,
                 (unsigned long long)nnz_both, launches, st->ms_total);
@@ -785,8 +779,8 @@ static void mxm_impl(Context *ctx, const Result *a, const Result *b, Result *res
     if (products == 0) {
         empty_result<T>(res, M, s);
     } else {
-        const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(env_u64("OSP_MXM_SHORT_CAP", kMxmShortMax), 1), kMxmShortMax);
-        const uint64_t budget = std::min<uint64_t>(std::max<uint64_t>(env_u64("OSP_MXM_BATCH", kMxmBatchDefault), 1), 0xfffffffeull);
+        const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ctx->env.mxm_short_cap.or_(kMxmShortMax), 1), kMxmShortMax);
+        const uint64_t budget = std::min<uint64_t>(std::max<uint64_t>(ctx->env.mxm_batch.or_(kMxmBatchDefault), 1), 0xfffffffeull);
         const MxmOperands op{a->rowptr, a->colidx, a->vals, b->rowptr, b->colidx, b->vals, wscan};
         // ---- the rows' classes and the batches ----
         // (two consecutive batches hold more than `budget` products between them, or the cut would not lie there)
@@ -901,7 +895,7 @@ static void mxm_impl(Context *ctx, const Result *a, const Result *b, Result *res
     st->batches = nb;
     st->launches = launches;
     st->ms_total = res->info.ms_total;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] mxm add=%d mul=%d M=%llu K=%llu N=%llu nnz %llu , %llu -> %llu products=%llu short=%llu long=%llu batches=%u launches=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
                 sr.add, sr.mul, (unsigned long long)M, (unsigned long long)K, (unsigned long long)N, (unsigned long long)nnz_a,
                 (unsigned long long)nnz_b, (unsigned long long)nnz_out, (unsigned long long)products, (unsigned long long)n_short,
@@ -909,11 +903,6 @@ static void mxm_impl(Context *ctx, const Result *a, const Result *b, Result *res
 }
 
 // ---- the transpose of a CSR result (osp_transpose.h) ----
-static bool env_is(const char *name, const char *value) {
-    const char *e = getenv(name);
-    return e && strcmp(e, value) == 0;
-}
-
 template <class T>
 static void transpose_impl(Context *ctx, const Result *in, Result *res, osp_transpose_stats_t *st) {
     typedef ValueBits<T> V;
@@ -927,7 +916,7 @@ static void transpose_impl(Context *ctx, const Result *in, Result *res, osp_tran
     uint32_t path = 0, passes = 0, launches = 0;
     if (nnz == 0) {
         empty_result<T>(res, N, s);
-    } else if (M <= kTrMaskRows && !env_is("OSP_TRANSPOSE_PATH", "sort")) {
+    } else if (M <= kTrMaskRows && !ctx->env.transpose_path.is("sort")) {
         path = 1;
         alloc_rowptr(res, N);
         alloc_entries<T>(res, nnz);
@@ -949,7 +938,7 @@ static void transpose_impl(Context *ctx, const Result *in, Result *res, osp_tran
         passes = (uint32_t)rs_passes(nbits);
         const RowSort rs(sc, nnz, nbits);
         uint32_t *sorted_cols = sc.get<uint32_t>(nnz);
-        if (env_is("OSP_TRANSPOSE_GATHER", "bisect")) {
+        if (ctx->env.transpose_gather.is("bisect")) {
             const TrEpilogue<V, false> epi{nullptr, in->rowptr, (const V *)in->vals, M, res->colidx, sorted_cols, (V *)res->vals};
             launches += rs.sort(in->colidx, epi);
         } else {
@@ -969,7 +958,7 @@ static void transpose_impl(Context *ctx, const Result *in, Result *res, osp_tran
     st->passes = passes;
     st->launches = launches;
     st->ms_total = res->info.ms_total;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] transpose M=%llu N=%llu nnz=%llu path=%u passes=%u launches=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
                 (unsigned long long)M, (unsigned long long)N, (unsigned long long)nnz, path, passes, launches, st->ms_total,
                 (unsigned long long)ctx->malloc_calls);
@@ -1073,7 +1062,7 @@ static void reduce_impl(Context *ctx, const Result *in, int axis, int op, void *
     st->long_segments = long_segments;
     st->ms_total = ms;
     st->launches = launches;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] reduce axis=%d op=%d M=%llu N=%llu nnz=%llu long=%llu launches=%u %.3f ms\n", axis, op, (unsigned long long)M,
                 (unsigned long long)N, (unsigned long long)nnz, (unsigned long long)long_segments, launches, st->ms_total);
 }
@@ -1097,8 +1086,8 @@ static void mxv_with_ops(int add, int mul, F &&body) {
 // log2 of the lanes a packed row gets.  OSP_MXV_GROUP = 4, 8, 16, 32 or 64 forces it (any other value: automatic).
 // Automatic: the smallest g of at least the mean row length, the fastest of the five on the R-MAT adjacency that was measured
 // (by 2-4 % over g = 64, MEASUREMENTS.md section 0l; means below 4 and other distributions: not measured).
-static uint32_t mxv_group_log2(uint64_t M, uint64_t nnz) {
-    const uint64_t forced = env_u64("OSP_MXV_GROUP", 0);
+static uint32_t mxv_group_log2(const Settings &env, uint64_t M, uint64_t nnz) {
+    const uint64_t forced = env.mxv_group.or_(0);
     for (uint32_t lg = 2; lg <= 6; lg++)
         if (forced == (1ull << lg)) return lg;
     uint32_t lg = 2;
@@ -1114,7 +1103,7 @@ static void mxv_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, c
     Scratch &sc = fr.sc;
     const uint64_t M = in->info.M, N = in->info.N, nnz = in->info.nnz_c;
     const int add = sr.add == OSP_EWISE_PLUS ? RED_PLUS : sr.add == OSP_EWISE_MIN ? RED_MIN : RED_MAX;
-    const uint32_t lg = mxv_group_log2(M, nnz);
+    const uint32_t lg = mxv_group_log2(ctx->env, M, nnz);
     uint64_t long_segments = 0;
     uint32_t launches = 0;
     // (the vector is formed in a pool buffer and copied out last: x may be y, and a call that fails leaves y as it was)
@@ -1177,7 +1166,7 @@ static void mxv_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, c
     st->group = 1u << lg;
     st->launches = launches;
     st->ms_total = ms;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] mxv add=%d mul=%d M=%llu N=%llu nnz=%llu group=%u long=%llu launches=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
                 sr.add, sr.mul, (unsigned long long)M, (unsigned long long)N, (unsigned long long)nnz, 1u << lg, (unsigned long long)long_segments,
                 launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
@@ -1257,7 +1246,7 @@ static void mxd_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, c
     st->lanes_per_row = 1u << lgk;
     st->launches = launches;
     st->ms_total = ms;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] mxd add=%d mul=%d M=%llu N=%llu k=%llu nnz=%llu lanes=%u long=%llu launches=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
                 sr.add, sr.mul, (unsigned long long)M, (unsigned long long)N, (unsigned long long)k, (unsigned long long)nnz, 1u << lgk,
                 (unsigned long long)long_segments, launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
@@ -1302,7 +1291,7 @@ static void sddmm_impl(Context *ctx, const Result *in, Result *res, const osp_se
     st->lanes_per_entry = 1u << lgk;
     st->launches = launches;
     st->ms_total = res->info.ms_total;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] sddmm add=%d mul=%d accum=%d M=%llu N=%llu k=%llu nnz=%llu lanes=%u launches=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
                 sr.add, sr.mul, accum, (unsigned long long)M, (unsigned long long)N, (unsigned long long)k, (unsigned long long)nnz, 1u << lgk, launches,
                 st->ms_total, (unsigned long long)ctx->malloc_calls);
@@ -1364,7 +1353,7 @@ static void apply_vectors_impl(Context *ctx, const Result *in, Result *res, cons
     st->nnz_in = st->nnz_out = nnz;
     st->ms_total = res->info.ms_total;
     st->launches = launches;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] apply_vectors row_op=%d col_op=%d M=%llu nnz=%llu launches=%u %.3f ms\n", ap.row_op, ap.col_op, (unsigned long long)M,
                 (unsigned long long)nnz, launches, st->ms_total);
 }
@@ -1389,7 +1378,7 @@ static void select_vertices_impl(Context *ctx, const Result *in, Result *res, co
     st->nnz_out = c.nnz;
     st->ms_total = res->info.ms_total;
     st->launches = c.launches;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] select_vertices rows=%d cols=%d M=%llu nnz %llu -> %llu launches=%u %.3f ms\n", kr != nullptr, kc != nullptr,
                 (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)c.nnz, c.launches, st->ms_total);
 }
@@ -1444,7 +1433,7 @@ static void extract_impl(Context *ctx, const Result *in, Result *res, const osp_
         if (has_cols) {
             const uint32_t *cols = to_device(sc, ex.cols, n, space, s);
             uint32_t *tmp = sc.get<uint32_t>(scan_scratch_entries(nwc));
-            if (env_is("OSP_EXTRACT_DENSE_MAP", "1")) dense = sc.get<uint32_t>(N);
+            if (ctx->env.extract_dense_map.is("1")) dense = sc.get<uint32_t>(N);
             extract_colmap_kernel<<<grid_for(n, 256), 256, 0, s>>>(cols, n, N, (unsigned long long *)colbits, dense, err);
             launches += 1 + device_exclusive_scan<LoadPopc64, uint32_t>(LoadPopc64{colbits}, nwc, cpos, tmp, s);
         }
@@ -1502,7 +1491,7 @@ static void extract_impl(Context *ctx, const Result *in, Result *res, const osp_
     st->ms_total = res->info.ms_total;
     st->launches = launches;
     st->readbacks = readbacks;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] extract rows=%d cols=%d %llu x %llu of %llu x %llu nnz %llu -> %llu -> %llu launches=%u readbacks=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
                 has_rows, has_cols, (unsigned long long)m, (unsigned long long)n, (unsigned long long)M, (unsigned long long)N,
                 (unsigned long long)nnz_in, (unsigned long long)nnz_g, (unsigned long long)nnz_out, launches, readbacks, st->ms_total,
@@ -1595,7 +1584,7 @@ static void build_impl(Context *ctx, Result *res, const osp_build_t &b, osp_buil
     st->ms_total = res->info.ms_total;
     st->launches = launches;
     st->readbacks = readbacks;
-    if (getenv("OSP_VERBOSE"))
+    if (ctx->env.verbose)
         fprintf(stderr, "[osp] build dup=%d vals=%d %llu x %llu nnz %llu -> %llu long_runs=%llu launches=%u readbacks=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
                 dup, b.vals != nullptr, (unsigned long long)M, (unsigned long long)N, (unsigned long long)nnz, (unsigned long long)nnz_out,
                 (unsigned long long)long_runs, launches, readbacks, st->ms_total, (unsigned long long)ctx->malloc_calls);

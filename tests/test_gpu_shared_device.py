@@ -79,7 +79,7 @@ def test_plan_overlap_under_poison_and_guard(mode, port):
     env = dict(os.environ, OSP_TEST_ROOT=ROOT, OSP_DIRECT_MIN_NNZ="0", OSP_PLAN_OVERLAP="1")
     env[mode] = "1"
     if mode == "OSP_GATHER_MAX_RUNS":
-        # not a checking mode but a limit (read once per process): panels whose run table would hold 300 descriptors or more
+        # not a checking mode but a limit (read per call, like its neighbours): panels whose run table would hold 300 descriptors or more
         # write their planned rows through the multiply's cells while the short rows stay gathered -- the fallback of a panel
         # whose run table does not fit 32-bit addressing
         env[mode] = "300"
