@@ -159,6 +159,15 @@ class MxvStats(_Stats):
     _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("long_segments", C.c_uint64), ("group", C.c_uint32),
                 ("launches", C.c_uint32), ("ms_total", C.c_float), ("reserved", C.c_uint32 * 7)]
 
+# the add operators osp_csr_mxv_arg takes: the two of MXV_ADD_OPS under which a product has a position (mul: MXM_MUL_OPS)
+MXV_ARG_ADD_OPS = {name: EWISE_OPS[name] for name in ("min", "max")}
+
+
+class MxvArgStats(_Stats):
+    """osp_mxv_arg_stats_t"""
+    _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("long_segments", C.c_uint64), ("rows_without", C.c_uint64),
+                ("group", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float), ("reserved", C.c_uint32 * 7)]
+
 MXD_MAX_COLS = 65536   # OSP_MXD_MAX_COLS
 
 
@@ -279,6 +288,9 @@ TRANSPOSE_EXPORTS = ["osp_csr_transpose"]
 # every symbol include/outerspace_spgemm_mxv.h declares
 MXV_EXPORTS = ["osp_csr_mxv"]
 
+# every symbol include/outerspace_spgemm_mxv_arg.h declares
+MXV_ARG_EXPORTS = ["osp_csr_mxv_arg"]
+
 # every symbol include/outerspace_spgemm_mxd.h declares
 MXD_EXPORTS = ["osp_csr_mxd"]
 
@@ -378,6 +390,7 @@ def lib():
     L.osp_csr_mxm.argtypes = [vp, vp, C.POINTER(Semiring), C.POINTER(vp), C.POINTER(MxmStats)]
     L.osp_csr_transpose.argtypes = [vp, C.POINTER(Transpose), C.POINTER(vp), C.POINTER(TransposeStats)]
     L.osp_csr_mxv.argtypes = [vp, C.POINTER(Semiring), vp, vp, i32, C.POINTER(MxvStats)]
+    L.osp_csr_mxv_arg.argtypes = [vp, C.POINTER(Semiring), vp, vp, vp, i32, C.POINTER(MxvArgStats)]
     L.osp_csr_mxd.argtypes = [vp, C.POINTER(Semiring), vp, u64, vp, i32, C.POINTER(MxdStats)]
     L.osp_csr_sddmm.argtypes = [vp, C.POINTER(Semiring), i32, vp, vp, u64, i32, C.POINTER(vp), C.POINTER(SddmmStats)]
     L.osp_csr_extract.argtypes = [vp, C.POINTER(Extract), C.POINTER(vp), C.POINTER(ExtractStats)]

@@ -30,6 +30,7 @@
 #include "../../include/outerspace_spgemm_mxm.h"
 #include "../../include/outerspace_spgemm_transpose.h"
 #include "../../include/outerspace_spgemm_mxv.h"
+#include "../../include/outerspace_spgemm_mxv_arg.h"
 #include "../../include/outerspace_spgemm_mxd.h"
 #include "../../include/outerspace_spgemm_sddmm.h"
 #include "../../include/outerspace_spgemm_extract.h"
@@ -49,6 +50,7 @@
 #include "osp_mxm.h"
 #include "osp_transpose.h"
 #include "osp_mxv.h"
+#include "osp_mxv_arg.h"
 #include "osp_mxd.h"
 #include "osp_sddmm.h"
 #include "osp_extract.h"
@@ -950,6 +952,18 @@ int osp_csr_mxv(osp_result_t in_, const osp_semiring_t *sr, const void *x, void 
         check_reserved(sr->reserved, "mxv");
         if (!x && sr->mul != OSP_EWISE_FIRST) throw Error(OSP_ERR_ARG, "mxv: x may be null only when mul is FIRST");
     }, [&](auto tag, osp_mxv_stats_t *st) { mxv_impl<decltype(tag)>(in->ctx, in, *sr, x, y, space, st); });
+}
+
+int osp_csr_mxv_arg(osp_result_t in_, const osp_semiring_t *sr, const void *x, void *y, int64_t *arg, osp_memspace_t space,
+                    osp_mxv_arg_stats_t *stats) {
+    Result *in = (Result *)in_;
+    return csr_vector_op(in, sr && arg, stats, [&] {
+        check_space(space);
+        if (sr->add != OSP_EWISE_MIN && sr->add != OSP_EWISE_MAX) throw Error(OSP_ERR_ARG, "mxv_arg: add is not one of MIN, MAX");
+        if (sr->mul < OSP_EWISE_PLUS || sr->mul > OSP_EWISE_SECOND) throw Error(OSP_ERR_ARG, "mxv_arg: mul is not one of TIMES, PLUS, MIN, MAX, FIRST, SECOND");
+        check_reserved(sr->reserved, "mxv_arg");
+        if (!x && sr->mul != OSP_EWISE_FIRST) throw Error(OSP_ERR_ARG, "mxv_arg: x may be null only when mul is FIRST");
+    }, [&](auto tag, osp_mxv_arg_stats_t *st) { mxv_arg_impl<decltype(tag)>(in->ctx, in, *sr, x, y, arg, space, st); });
 }
 
 int osp_csr_mxd(osp_result_t in_, const osp_semiring_t *sr, const void *x, uint64_t k, void *y, osp_memspace_t space, osp_mxd_stats_t *stats) {

@@ -1172,6 +1172,143 @@ static void mxv_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, c
                 launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
 }
 
+// ---- mxv with the winner's column (osp_mxv_arg.h) ----
+// reduce_segments on pairs: the pair of every segment of (ptr, vals, cols) into (out, arg)[map[seg]], level by level.  Every
+// level lists, cuts and folds as reduce_segments does, so the value side has its bits.
+template <class T, int ADD>
+static void arg_segments(Scratch &sc, hipStream_t s, const int64_t *ptr, const T *vals, const uint32_t *cols, uint64_t nseg, uint64_t nent, T *out,
+                         int64_t *arg, uint32_t &launches, const uint32_t *map) {
+    for (;;) {
+        arg_short_kernel<T, ADD><<<grid_for(nseg, kReduceWaves), kReduceWaves * kWave, 0, s>>>(ptr, vals, cols, nseg, map, out, arg);
+        launches++;
+        if (nent <= kReduceBlock) return;   // (no segment can be long)
+        unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MCL_COUNTERS);
+        zero_async(s, {{counters, MCL_COUNTERS * sizeof(uint64_t)}});
+        uint32_t *long_segs = sc.get<uint32_t>(nent / ((uint64_t)kReduceBlock + 1) + 1);
+        mcl_classify_kernel<<<grid_for(nseg, 256), 256, 0, s>>>(ptr, nseg, kReduceBlock, long_segs, counters);
+        launches += 2;
+        const uint64_t n_long = d2h((const uint64_t *)counters + MCL_NLONG, s);
+        if (!n_long) return;
+        const uint64_t max_blocks = nent / kReduceBlock + n_long;
+        uint32_t *nblk = sc.get<uint32_t>(n_long + 1), *next_map = sc.get<uint32_t>(n_long);
+        int64_t *blkptr = sc.get<int64_t>(n_long + 1);
+        uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(n_long + 1));
+        T *partial = sc.get<T>(max_blocks);
+        uint32_t *pcol = sc.get<uint32_t>(max_blocks);
+        reduce_long_setup_kernel<<<grid_for(n_long, 256), 256, 0, s>>>(ptr, long_segs, n_long, map, nblk, next_map);
+        launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{nblk}, n_long, (uint64_t *)blkptr, tmp, s);
+        arg_blocks_kernel<T, ADD><<<grid_for(max_blocks, kReduceWaves), kReduceWaves * kWave, 0, s>>>(ptr, vals, cols, long_segs, blkptr, n_long, partial,
+                                                                                                      pcol);
+        launches++;
+        ptr = blkptr;
+        vals = partial;
+        cols = pcol;
+        nseg = n_long;
+        nent = max_blocks;
+        map = next_map;
+    }
+}
+
+template <class T>
+static void mxv_arg_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, const void *x_in, void *y_out, int64_t *arg_out,
+                         osp_memspace_t space, osp_mxv_arg_stats_t *st) {
+    OpFrame fr(ctx);
+    hipStream_t s = fr.s;
+    Scratch &sc = fr.sc;
+    const uint64_t M = in->info.M, N = in->info.N, nnz = in->info.nnz_c;
+    const int add = sr.add == OSP_EWISE_MIN ? RED_MIN : RED_MAX;
+    const uint32_t lg = mxv_group_log2(ctx->env, M, nnz);
+    uint64_t long_segments = 0, rows_without = M;
+    uint32_t launches = 0;
+    // (both vectors are formed in pool buffers and copied out last: x may be y, and a call that fails leaves y and arg as they
+    // were.  y is formed whether the caller wants it or not: the kernels do not branch on it)
+    T *out = sc.get<T>(M);
+    int64_t *arg = sc.get<int64_t>(M);
+    std::vector<T> ids;
+    if (M && nnz) {
+        const T *x = sr.mul == OSP_EWISE_FIRST ? nullptr : to_device(sc, (const T *)x_in, N, space, s);
+        const int64_t *rowptr = in->rowptr;
+        const uint32_t *col = in->colidx;
+        const T *vals = (const T *)in->vals;
+        mxv_with_mul<RED_MIN>(sr.mul, [&](auto, auto m) {   // (the mul alone: the add is one of two)
+            constexpr int MUL = decltype(m)::value;
+            const auto with_add = [&](auto a) {
+                constexpr int ADD = decltype(a)::value;
+                const uint64_t waves = (M + (kWave >> lg) - 1) >> (6 - lg);
+                mxv_arg_rows_kernel<T, ADD, MUL><<<grid_for(waves, kReduceWaves), kReduceWaves * kWave, 0, s>>>(rowptr, col, vals, x, M, lg, out, arg);
+                launches++;
+                if (nnz <= kReduceBlock) return;   // (no row can be long)
+                // the long rows, listed and cut into blocks as mxv_impl lists and cuts them
+                unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MCL_COUNTERS);
+                zero_async(s, {{counters, MCL_COUNTERS * sizeof(uint64_t)}});
+                uint32_t *long_rows = sc.get<uint32_t>(nnz / ((uint64_t)kReduceBlock + 1) + 1);
+                mcl_classify_kernel<<<grid_for(M, 256), 256, 0, s>>>(rowptr, M, kReduceBlock, long_rows, counters);
+                launches += 2;
+                const uint64_t n_long = d2h((const uint64_t *)counters + MCL_NLONG, s);
+                long_segments = n_long;
+                if (!n_long) return;
+                const uint64_t max_blocks = nnz / kReduceBlock + n_long;
+                uint32_t *nblk = sc.get<uint32_t>(n_long + 1), *map = sc.get<uint32_t>(n_long);
+                int64_t *blkptr = sc.get<int64_t>(n_long + 1);
+                uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(n_long + 1));
+                T *partial = sc.get<T>(max_blocks);
+                uint32_t *pcol = sc.get<uint32_t>(max_blocks);
+                reduce_long_setup_kernel<<<grid_for(n_long, 256), 256, 0, s>>>(rowptr, long_rows, n_long, nullptr, nblk, map);
+                launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{nblk}, n_long, (uint64_t *)blkptr, tmp, s);
+                mxv_arg_blocks_kernel<T, ADD, MUL><<<grid_for(max_blocks, kReduceWaves), kReduceWaves * kWave, 0, s>>>(rowptr, col, vals, x, long_rows,
+                                                                                                                       blkptr, n_long, partial, pcol);
+                launches++;
+                arg_segments<T, ADD>(sc, s, blkptr, partial, pcol, n_long, max_blocks, out, arg, launches, map);
+            };
+            if (add == RED_MIN) with_add(std::integral_constant<int, RED_MIN>{});
+            else with_add(std::integral_constant<int, RED_MAX>{});
+        });
+        // the stats' rows_without (few workgroups: each ends in one atomic on one word)
+        unsigned long long *without = (unsigned long long *)sc.get<uint64_t>(1);
+        zero_async(s, {{without, sizeof(uint64_t)}});
+        arg_count_kernel<<<(unsigned)std::min<uint64_t>(grid_for(M, 256), 256), 256, 0, s>>>(arg, M, without);
+        launches += 2;
+        rows_without = d2h((const uint64_t *)without, s);
+    } else if (M) {
+        const T inf = std::numeric_limits<T>::infinity();
+        ids.assign(M, add == RED_MIN ? inf : -inf);   // every row is empty: no kernel
+    }
+    const float ms = fr.stop();
+    if (M) {
+        if (!ids.empty()) {
+            const std::vector<int64_t> none(M, -1);
+            if (space == OSP_DEVICE) {
+                if (y_out) copy_h2d(y_out, ids.data(), M * sizeof(T), s);
+                copy_h2d(arg_out, none.data(), M * sizeof(int64_t), s);
+            } else {
+                if (y_out) memcpy(y_out, ids.data(), M * sizeof(T));
+                memcpy(arg_out, none.data(), M * sizeof(int64_t));
+            }
+        } else if (space == OSP_DEVICE) {
+            if (y_out) OSP_HIP(hipMemcpyAsync(y_out, out, M * sizeof(T), hipMemcpyDeviceToDevice, s));
+            OSP_HIP(hipMemcpyAsync(arg_out, arg, M * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        } else {
+            if (y_out) copy_d2h(y_out, out, M * sizeof(T), s);
+            copy_d2h(arg_out, arg, M * sizeof(int64_t), s);
+        }
+        OSP_HIP(hipStreamSynchronize(s));
+    }
+    *st = osp_mxv_arg_stats_t{};
+    st->nnz_in = nnz;
+    st->nnz_out = M;
+    st->long_segments = long_segments;
+    st->rows_without = rows_without;
+    st->group = 1u << lg;
+    st->launches = launches;
+    st->ms_total = ms;
+    if (ctx->env.verbose)
+        fprintf(stderr,
+                "[osp] mxv_arg add=%d mul=%d M=%llu N=%llu nnz=%llu group=%u long=%llu without=%llu launches=%u %.3f ms; pool misses so far: %llu "
+                "hipMalloc calls\n",
+                sr.add, sr.mul, (unsigned long long)M, (unsigned long long)N, (unsigned long long)nnz, 1u << lg, (unsigned long long)long_segments,
+                (unsigned long long)rows_without, launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
+}
+
 // ---- a CSR result times a dense matrix under a semiring (osp_mxd.h) ----
 template <class T>
 static void mxd_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, const void *x_in, uint64_t k, void *y_out, osp_memspace_t space,

@@ -14,7 +14,9 @@ which need the transpose of a result ``osp_csr_transpose`` (``strongly_connected
 one ``osp_csr_build`` (``adjacency_matrix``, ``laplacian``, ``incidence_matrix``, ``line_graph``), and label spreading and
 feature propagation on the product of a result with a dense matrix ``osp_csr_mxd`` (``label_spreading``,
 ``propagate_features``), and edge scores, landmark distance bounds and a factorisation of the observed entries on the sampled
-dense-dense product ``osp_csr_sddmm`` (``edge_scores``, ``landmark_bounds``, ``factorize``, at the end).
+dense-dense product ``osp_csr_sddmm`` (``edge_scores``, ``landmark_bounds``, ``factorize``), and a minimum spanning forest
+and a greedy weighted matching on mxv with the winner's column ``osp_csr_mxv_arg`` (``minimum_spanning_forest``,
+``greedy_matching``, at the end).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -1732,3 +1734,166 @@ def factorize(rows, cols, vals, shape, rank, steps, lr, reg=0.0, U0=None, V0=Non
         return U.cpu().numpy(), V.cpu().numpy(), info
     finally:
         _close_all(device, (S,))
+
+
+# ---- mxv with the winner's column (osp_csr_mxv_arg): spanning forest, matching ------------------------------
+def _arg_setup(rows, cols, n, weights, keep, dtype, ctx):
+    """What the two functions below share: the checks of the arguments (before the context: a bad argument is a Python error
+    without a GPU as well), the context (without a GPU this is where they fail), the weighted adjacency on its device with
+    the weights as ``dtype`` holds them, and the guard of float32's exact range (vertex ids are held as values).  Returns
+    (ctx, device, dtype, n, W): W a CSR result, None when the graph has no edge."""
+    dtype = _value_dtype(dtype)
+    if weights is not None:
+        w = np.asarray(weights.cpu() if torch.is_tensor(weights) else weights, np.float64)
+        if np.isnan(w).any():
+            raise ValueError("weights must not be NaN")
+    if dtype == np.float32 and n is not None and int(n) > 1 << 24:
+        raise ValueError("float32 holds vertex ids exactly only up to n = 2^24: use float64")
+    ctx, device, dtype = _setup(dtype, ctx)
+    n, rowptr, colidx, vals = weighted_adjacency(rows, cols, n, weights, keep=keep, device=device)
+    if dtype == np.float32 and n > 1 << 24:
+        raise ValueError("float32 holds vertex ids exactly only up to n = 2^24: use float64")
+    if colidx.numel() == 0:
+        return ctx, device, dtype, n, None
+    return ctx, device, dtype, n, _csr_result(ctx, dtype, n, n, rowptr, colidx.to(torch.int32), vals.to(_torch_dtype(dtype)), device)
+
+
+def minimum_spanning_forest(rows, cols, n=None, weights=None, *, dtype=np.float64, ctx=None):
+    """The minimum spanning forest of the undirected graph with edges (rows[e], cols[e]) on vertices [0, n) (any direction,
+    self loops dropped, duplicate edges keep their smallest weight; ``weights=None``: 1.0 each), under the STRICT TOTAL ORDER
+    on edges (w, min(u, v), max(u, v)) with w the weight as ``dtype`` holds it.  Under a strict total order the minimum
+    spanning forest is unique, so the result is defined exactly, ties included: it is what Kruskal's algorithm gives on the
+    edges sorted by that key.
+
+    Boruvka, the matrix on the device in every round.  Labels l start as the vertices' own ids, held as values of ``dtype``
+    (float32: n <= 2^24).  A ROUND:
+      the cross edges  D = Wc.apply_vectors(rows=l, row_op="second", cols=l, col_op="minus")  (l[i] - l[j] on Wc's pattern),
+      mask = D.select("ne", 0),  Wc = Wc.apply_mask(mask)  -- Wc only ever shrinks, so each round filters the previous
+      round's (the first round's Wc is W: without self loops every edge is a cross edge); it stops when Wc has no entries;
+      (y, arg) = Wc.mxv_arg(None, "min", "first")  -- the lightest cross edge of every vertex;
+      the best edge of every component, the hooking and the pointer jumping in torch, on length-n vectors.
+    ``arg[v]`` is the SMALLEST column among v's lightest cross edges, and that is v's smallest edge under the total order:
+    for two neighbours j1 < j2 of v with equal weight, either j1 < j2 < v, and the keys are (j1, v) < (j2, v); or
+    j1 < v < j2, and (j1, v) < (v, j2) because j1 < v; or v < j1 < j2, and (v, j1) < (v, j2).  A component's best edge is
+    the smallest (y, min, max) among its vertices.  Two components may choose the same edge (it is then taken once and the
+    smaller label becomes the root); under a strict order the chosen edges form no other cycle.
+
+    Returns (u, v, w, info): the forest's edges, u < v, ascending by (u, v), int64 and ``dtype``; info = rounds,
+    components (n - the number of edges), ms_mxv_arg (a list: device time per round), launches (kernels of all library
+    calls).  n == 0 and a graph without edges launch nothing."""
+    ctx, device, dtype, n, W = _arg_setup(rows, cols, n, weights, "min", dtype, ctx)
+    info = {"rounds": 0, "components": n, "ms_mxv_arg": [], "launches": 0}
+    if W is None:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, dtype), info
+    td = _torch_dtype(dtype)
+    Wc, keys, wts = W, [], []
+    try:
+        lab = torch.arange(n, dtype=torch.int64, device=device)
+        while True:
+            if info["rounds"]:
+                labv = lab.to(td)
+                torch.cuda.synchronize(device)   # the library works on its own stream
+                D, sd = Wc.apply_vectors(rows=labv, row_op="second", cols=labv, col_op="minus")
+                try:
+                    mask, sm = D.select("ne", 0)
+                finally:
+                    D.close()
+                try:
+                    new, sa = Wc.apply_mask(mask)
+                finally:
+                    mask.close()
+                info["launches"] += sd["launches"] + sm["launches"] + sa["launches"]
+                if Wc is not W:
+                    Wc.close()
+                Wc = new
+            if Wc.nnz == 0:
+                break
+            torch.cuda.synchronize(device)
+            y, arg, st = Wc.mxv_arg(None, "min", "first")
+            info["rounds"] += 1
+            info["ms_mxv_arg"].append(st["ms_total"])
+            info["launches"] += st["launches"]
+            # the best edge of every component: the smallest y, then the smallest key min * n + max among those
+            v = torch.nonzero(arg >= 0).squeeze(1)
+            o, comp, yv = arg[v], lab[v], y[v]
+            best = torch.full((n,), float("inf"), dtype=td, device=device)
+            best.scatter_reduce_(0, comp, yv, reduce="amin", include_self=True)
+            tie = yv == best[comp]
+            v, o, comp, yv = v[tie], o[tie], comp[tie], yv[tie]
+            key = torch.minimum(v, o) * n + torch.maximum(v, o)
+            kbest = torch.full((n,), torch.iinfo(torch.int64).max, dtype=torch.int64, device=device)
+            kbest.scatter_reduce_(0, comp, key, reduce="amin", include_self=True)
+            won = key == kbest[comp]
+            o, comp, yv, key = o[won], comp[won], yv[won], key[won]     # one edge per component that has a cross edge
+            # hooking: a component points at the one its edge leads to; of two that chose the same edge the smaller label stays a root
+            parent = torch.arange(n, dtype=torch.int64, device=device)
+            parent[comp] = lab[o]
+            root = (parent[parent[comp]] == comp) & (comp < parent[comp])
+            parent[comp[root]] = comp[root]
+            keys.append(key[~root])
+            wts.append(yv[~root])
+            while True:   # pointer jumping
+                nxt = parent[parent]
+                if torch.equal(nxt, parent):
+                    break
+                parent = nxt
+            lab = parent[lab]
+        key = torch.cat(keys) if keys else torch.zeros(0, dtype=torch.int64, device=device)
+        wt = torch.cat(wts) if wts else torch.zeros(0, dtype=td, device=device)
+        order = torch.argsort(key)
+        key, wt = key[order].cpu().numpy(), wt[order].cpu().numpy()
+    finally:
+        _close_all(device, (W, Wc))   # (closing twice is closing once)
+    info["components"] = n - len(key)
+    return key // n, key % n, wt, info
+
+
+def greedy_matching(rows, cols, n=None, weights=None, *, dtype=np.float64, ctx=None):
+    """The greedy weighted matching of the undirected graph with edges (rows[e], cols[e]) on vertices [0, n) (any direction,
+    self loops dropped, duplicate edges keep their largest weight; ``weights=None``: 1.0 each): the matching a sequential
+    pass over the edges in the STRICT TOTAL ORDER (larger w first, then min(u, v), then max(u, v)) builds, w the weight as
+    ``dtype`` holds it, computed by handshake rounds with the matrix on the device.  A ROUND:
+      Wf = Wf.select_vertices(free, free)  (the edges between free vertices; the first round's Wf is W); stop when it is empty;
+      (y, arg) = Wf.mxv_arg(None, "max", "first")  -- every free vertex's heaviest free neighbour, the smallest id among
+      ties, which is its best edge under the total order (the three cases of ``minimum_spanning_forest``);
+      the pairs with arg[arg[v]] == v are matched.
+    An edge is locally dominant when it is the best edge of both its ends; under a strict total order the locally dominant
+    edges of every round are exactly edges the sequential greedy pass takes, and the round's best edge overall is one of
+    them, so every round matches a pair and the result is the sequential one: defined exactly, and MAXIMAL (no edge has both
+    ends free).  With non-negative weights its weight is at least half the optimum (Preis 1999).
+
+    Returns (mate int64[n], info): mate[v] is v's partner, -1 for a free vertex; info = rounds, pairs, ms_mxv_arg (a list:
+    device time per round), launches (kernels of all library calls).  n == 0 and a graph without edges launch nothing."""
+    ctx, device, dtype, n, W = _arg_setup(rows, cols, n, weights, "max", dtype, ctx)
+    info = {"rounds": 0, "pairs": 0, "ms_mxv_arg": [], "launches": 0}
+    if W is None:
+        return np.full(n, -1, np.int64), info
+    Wf = W
+    try:
+        mate = torch.full((n,), -1, dtype=torch.int64, device=device)
+        ids = torch.arange(n, dtype=torch.int64, device=device)
+        while True:
+            if info["rounds"]:
+                free = (mate < 0).to(torch.uint8)
+                torch.cuda.synchronize(device)   # the library works on its own stream
+                new, ss = Wf.select_vertices(free, free)
+                info["launches"] += ss["launches"]
+                if Wf is not W:
+                    Wf.close()
+                Wf = new
+            if Wf.nnz == 0:
+                break
+            torch.cuda.synchronize(device)
+            _, arg, st = Wf.mxv_arg(None, "max", "first", values=False)
+            info["rounds"] += 1
+            info["ms_mxv_arg"].append(st["ms_total"])
+            info["launches"] += st["launches"]
+            has = arg >= 0
+            back = arg[torch.where(has, arg, ids)]
+            shake = has & (back == ids)
+            mate = torch.where(shake, arg, mate)
+        mate = mate.cpu().numpy()
+    finally:
+        _close_all(device, (W, Wf))   # (closing twice is closing once)
+    info["pairs"] = int((mate >= 0).sum()) // 2
+    return mate, info

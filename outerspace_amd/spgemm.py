@@ -327,26 +327,30 @@ class CsrResult:
             if at is not self:
                 at.close()
 
-    def _out_arg(self, out, shape, space):
-        """The output of ``mxv`` (``shape`` (M,)) and ``mxd`` ((M, k)): (pointer, buffer the pointer points into, what the
-        method returns).  ``out=None`` allocates -- numpy on the host, torch on the context's device --, else ``out`` is checked
-        and filled.  The pointer is never null."""
+    def _out_arg(self, out, shape, space, dtype=None, what="out"):
+        """The output of ``mxv`` (``shape`` (M,)) and ``mxd`` ((M, k)), and with ``dtype=np.int64`` the positions of
+        ``mxv_arg``: (pointer, buffer the pointer points into, what the method returns).  ``out=None`` allocates -- numpy on
+        the host, torch on the context's device --, else ``out`` is checked and filled.  The pointer is never null."""
         size = math.prod(shape)
+        dtype = self.dtype if dtype is None else dtype
         if out is None and space == "host":
-            ret = np.empty(shape, self.dtype)
-            buf = ret if size else np.empty(1, self.dtype)
+            ret = np.empty(shape, dtype)
+            buf = ret if size else np.empty(1, dtype)
             return C.c_void_p(buf.ctypes.data), buf, ret
         if out is None:
             import torch
-            buf = torch.empty(max(size, 1), dtype=_torch_dtype(self.dtype), device=f"cuda:{self._ctx.device}")
+            tdt = torch.int64 if np.dtype(dtype) == np.int64 else _torch_dtype(dtype)
+            buf = torch.empty(max(size, 1), dtype=tdt, device=f"cuda:{self._ctx.device}")
             return C.c_void_p(buf.data_ptr()), buf, buf[:size].view(shape)
         if space == "host":
-            if not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.shape == shape and out.flags.c_contiguous):
-                raise OspError(_lib.ERR_ARG, f"out must be a contiguous numpy array of {size} values of {np.dtype(self.dtype)}" if len(shape) == 1
-                               else f"out must be a contiguous ({shape[0]}, {shape[1]}) numpy array of {np.dtype(self.dtype)}")
-            buf = out if size else np.empty(1, self.dtype)
+            if not (isinstance(out, np.ndarray) and out.dtype == dtype and out.shape == shape and out.flags.c_contiguous):
+                raise OspError(_lib.ERR_ARG, f"{what} must be a contiguous numpy array of {size} values of {np.dtype(dtype)}" if len(shape) == 1
+                               else f"{what} must be a contiguous ({shape[0]}, {shape[1]}) numpy array of {np.dtype(dtype)}")
+            buf = out if size else np.empty(1, dtype)
             return C.c_void_p(buf.ctypes.data), buf, out
-        ptr, buf = _dense_arg(out, shape, self.dtype, "device", "out", floating=len(shape) == 2)
+        if np.dtype(dtype) == np.int64 and hasattr(out, "is_floating_point") and out.is_floating_point():
+            raise OspError(_lib.ERR_ARG, f"{what} must be a contiguous tensor of {size} values of int64")
+        ptr, buf = _dense_arg(out, shape, dtype, "device", what, floating=len(shape) == 2)
         return ptr, buf, out
 
     def reduce(self, axis, op, out=None):
@@ -389,6 +393,33 @@ class CsrResult:
         stats = _lib.MxvStats()
         _lib.check(_lib.lib().osp_csr_mxv(self._h, C.byref(sr), xp, yp, sp, C.byref(stats)))   # (keep_x and buf live until here)
         return ret, stats.as_dict()
+
+    def mxv_arg(self, x, add="min", mul="times", out=None, out_arg=None, space="device", values=True):
+        """``mxv`` under ``add`` ``"min"`` or ``"max"`` together with WHERE the winner is (``osp_csr_mxv_arg``): ``y`` is
+        ``mxv(x, add, mul)`` bit for bit, and ``arg[i]`` is the smallest column j among row i's products
+        ``mul(self[i, j], x[j])`` that are not NaN and that no other non-NaN product beats under the IEEE comparison (so
+        -0.0 and +0.0 tie, and the tie goes to the smaller column); -1 for a row that is empty or whose products are all NaN.
+        ``arg`` depends neither on the order of the reduction nor on ``OSP_MXV_GROUP``.  ``mul`` is ``"times" "plus" "min"
+        "max" "first" "second"``; with ``"first"`` ``x`` may be None and the call is the arg-reduce of this result's rows.
+        ``x``, ``out`` and ``space`` as in ``mxv``; ``out_arg``: None, or M int64 values to fill -- a device address or torch
+        tensor, a numpy array with ``space="host"``; ``values=False`` asks for positions only (``out`` must be None).  For the
+        column axis, ``transpose()`` first.  Returns (y or None, arg, stats dict): ``arg`` is a torch int64 tensor on the
+        context's device or a numpy int64 array (``space="host"``).  Stats: nnz_in, nnz_out, long_segments, rows_without
+        (rows whose arg is -1), group, launches, ms_total."""
+        sr = _lib.Semiring()
+        sr.add, sr.mul = _enum(_lib.MXV_ARG_ADD_OPS, add, "add"), _enum(_lib.MXM_MUL_OPS, mul, "mul")
+        sp = _space(space)
+        M, N = self.shape
+        if x is None and mul != "first":
+            raise OspError(_lib.ERR_ARG, 'x may be None only when mul is "first"')
+        if not values and out is not None:
+            raise OspError(_lib.ERR_ARG, "values=False returns no y: out must be None")
+        xp, keep_x = _dense_arg(x if mul != "first" else None, (N,), self.dtype, space, "x")
+        yp, buf, ret = self._out_arg(out, (M,), space) if values else (None, None, None)
+        ap, abuf, aret = self._out_arg(out_arg, (M,), space, np.int64, "out_arg")
+        stats = _lib.MxvArgStats()
+        _lib.check(_lib.lib().osp_csr_mxv_arg(self._h, C.byref(sr), xp, yp, ap, sp, C.byref(stats)))   # (keep_x, buf and abuf live until here)
+        return ret, aret, stats.as_dict()
 
     def mxd(self, X, add="plus", mul="times", out=None, space="device", k=None):
         """This CSR (M x N) times the dense matrix ``X`` (N x k, row-major, contiguous) under the semiring ``(add, mul)``
