@@ -32,7 +32,7 @@ namespace osp {
 
 constexpr uint32_t kMxdMaxCols = 65536;   // the largest k (OSP_MXD_MAX_COLS): the column tiles fit gridDim.y
 
-// mul(A's value at p, x[col[p], c]) as a T: mxv_product with a row of x where it has one value
+// mul(A's value at p, x[col[p], c]) as a T: osp_mxv.h's Products::value with a row of x where it has one value
 template <class T, int MUL>
 __device__ __forceinline__ T mxd_product(const uint32_t *__restrict__ col, const T *__restrict__ vals, const T *__restrict__ x, uint64_t p,
                                          uint64_t k, uint64_t c) {
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kReduceWaves *kWave) void mxd_rows_kernel(const int
 }
 
 // ---- rows of more than kReduceBlock entries, first level: partial[w, c] = R(the products of block w in column c) -----------------
-// (mxv_blocks_kernel's cut: block w belongs to the long row r with blkptr[r] <= w < blkptr[r + 1])
+// (segments_blocks_kernel's cut: block w belongs to the long row r with blkptr[r] <= w < blkptr[r + 1])
 template <class T, int ADD, int MUL>
 __global__ __launch_bounds__(kReduceWaves *kWave) void mxd_blocks_kernel(const int64_t *__restrict__ rowptr, const uint32_t *__restrict__ col,
                                                                          const T *__restrict__ vals, const T *__restrict__ x,

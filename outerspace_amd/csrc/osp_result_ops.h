@@ -965,40 +965,96 @@ static void transpose_impl(Context *ctx, const Result *in, Result *res, osp_tran
 }
 
 // ---- a CSR result and dense vectors: reduce, apply, vertex select (osp_vector.h) ----
-// R over every segment of (ptr, vals) into out[0, nseg): the short segments by a wave each, the long ones block by block
-// into a pool buffer whose segments (one per long segment) are the next level's input.  nent: an upper bound of the level's
-// entries.  One read-back per level that can hold a long segment (the number of long segments).  map: where a segment's
-// result goes in out (null: at its own number).
-template <class T, int OP>
-static void reduce_segments(Scratch &sc, hipStream_t s, const int64_t *ptr, const T *vals, uint64_t nseg, uint64_t nent, T *out,
+// The long segments of a level, listed and cut into blocks of kReduceBlock: segment long_segs[k] owns the blocks
+// [blkptr[k], blkptr[k + 1]) and its result goes to next_map[k].  (blkptr, one stored accumulator per block) are the next
+// level's segments.
+struct LongCut {
+    uint64_t n_long = 0, max_blocks = 0;
+    const uint32_t *long_segs = nullptr, *next_map = nullptr;
+    const int64_t *blkptr = nullptr;
+};
+// nent: an upper bound of the level's entries; map: where a segment's result goes (null: at its own number).  n_long is 0
+// when no segment can be long (no kernel then) or none is; one read-back otherwise.  The one frame of reduce, mxv, mxv_arg
+// and mxd.
+static LongCut cut_long_segments(Scratch &sc, hipStream_t s, const int64_t *ptr, uint64_t nseg, uint64_t nent, const uint32_t *map, uint32_t &launches) {
+    LongCut cut;
+    if (nent <= kReduceBlock) return cut;
+    unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MCL_COUNTERS);
+    zero_async(s, {{counters, MCL_COUNTERS * sizeof(uint64_t)}});
+    uint32_t *long_segs = sc.get<uint32_t>(nent / ((uint64_t)kReduceBlock + 1) + 1);
+    mcl_classify_kernel<<<grid_for(nseg, 256), 256, 0, s>>>(ptr, nseg, kReduceBlock, long_segs, counters);
+    launches += 2;
+    cut.n_long = d2h((const uint64_t *)counters + MCL_NLONG, s);
+    if (!cut.n_long) return cut;
+    // the long segments' blocks: sum ceil(m / block) <= nent / block + n_long, the exact number stays on the device
+    cut.max_blocks = nent / kReduceBlock + cut.n_long;
+    uint32_t *nblk = sc.get<uint32_t>(cut.n_long + 1), *next_map = sc.get<uint32_t>(cut.n_long);
+    int64_t *blkptr = sc.get<int64_t>(cut.n_long + 1);
+    uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(cut.n_long + 1));
+    reduce_long_setup_kernel<<<grid_for(cut.n_long, 256), 256, 0, s>>>(ptr, long_segs, cut.n_long, map, nblk, next_map);
+    launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{nblk}, cut.n_long, (uint64_t *)blkptr, tmp, s);
+    cut.long_segs = long_segs;
+    cut.next_map = next_map;
+    cut.blkptr = blkptr;
+    return cut;
+}
+
+// n stored accumulators from the pool: where a level's blocks kernel writes and the next level reads
+template <class T>
+static void get_stored(Scratch &sc, uint64_t n, Values<T> &v) {
+    v.vals = sc.get<T>(n);
+}
+template <class T>
+static void get_stored(Scratch &sc, uint64_t n, Pairs<T> &v) {
+    v.vals = sc.get<T>(n);
+    v.cols = sc.get<uint32_t>(n);
+}
+
+// R over every segment of (ptr, src) into out: the short segments by a wave each, the long ones block by block into a pool
+// buffer whose segments (one per long segment) are the next level's input.  Acc is PlainAcc for reduce and mxv's upper
+// levels, PairAcc for mxv_arg's.  long_segments: the first level's.
+template <class Acc, class Sink>
+static void reduce_segments(Scratch &sc, hipStream_t s, const int64_t *ptr, typename Acc::Stored src, uint64_t nseg, uint64_t nent, Sink out,
                             uint64_t &long_segments, uint32_t &launches, const uint32_t *map = nullptr) {
     for (int level = 0;; level++) {
-        reduce_short_kernel<T, OP><<<grid_for(nseg, kReduceWaves), kReduceWaves * kWave, 0, s>>>(ptr, vals, nseg, map, out);
+        segments_short_kernel<Acc><<<grid_for(nseg, kReduceWaves), kReduceWaves * kWave, 0, s>>>(ptr, src, nseg, map, out);
         launches++;
-        if (nent <= kReduceBlock) return;   // (no segment can be long)
-        unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MCL_COUNTERS);
-        zero_async(s, {{counters, MCL_COUNTERS * sizeof(uint64_t)}});
-        uint32_t *long_segs = sc.get<uint32_t>(nent / ((uint64_t)kReduceBlock + 1) + 1);
-        mcl_classify_kernel<<<grid_for(nseg, 256), 256, 0, s>>>(ptr, nseg, kReduceBlock, long_segs, counters);
-        launches += 2;
-        const uint64_t n_long = d2h((const uint64_t *)counters + MCL_NLONG, s);
-        if (level == 0) long_segments = n_long;
-        if (!n_long) return;
-        // the long segments' blocks: sum ceil(m / block) <= nent / block + n_long, the exact number stays on the device
-        const uint64_t max_blocks = nent / kReduceBlock + n_long;
-        uint32_t *nblk = sc.get<uint32_t>(n_long + 1), *next_map = sc.get<uint32_t>(n_long);
-        int64_t *blkptr = sc.get<int64_t>(n_long + 1);
-        uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(n_long + 1));
-        T *partial = sc.get<T>(max_blocks);
-        reduce_long_setup_kernel<<<grid_for(n_long, 256), 256, 0, s>>>(ptr, long_segs, n_long, map, nblk, next_map);
-        launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{nblk}, n_long, (uint64_t *)blkptr, tmp, s);
-        reduce_blocks_kernel<T, OP><<<grid_for(max_blocks, kReduceWaves), kReduceWaves * kWave, 0, s>>>(ptr, vals, long_segs, blkptr, n_long, partial);
+        const LongCut cut = cut_long_segments(sc, s, ptr, nseg, nent, map, launches);
+        if (level == 0) long_segments = cut.n_long;
+        if (!cut.n_long) return;
+        typename Acc::Stored partial;
+        get_stored(sc, cut.max_blocks, partial);
+        segments_blocks_kernel<Acc><<<grid_for(cut.max_blocks, kReduceWaves), kReduceWaves * kWave, 0, s>>>(ptr, src, cut.long_segs, cut.blkptr, cut.n_long,
+                                                                                                            partial);
         launches++;
-        ptr = blkptr;
-        vals = partial;
-        nseg = n_long;
-        nent = max_blocks;
-        map = next_map;
+        ptr = cut.blkptr;
+        src = partial;
+        nseg = cut.n_long;
+        nent = cut.max_blocks;
+        map = cut.next_map;
+    }
+}
+
+// the identity of the add `red` (RED_*; COUNT's, above them, is PLUS's) as a T
+template <class T>
+static T red_identity(int red) {
+    const T inf = std::numeric_limits<T>::infinity();
+    return red == RED_MIN ? inf : red == RED_MAX ? -inf : T(0);
+}
+
+// The last step of a dense result: the n values of the pool buffer `from` go to `to` in `space` -- or, when no kernel ran
+// because every segment is empty, n times `fill`.  A null `to` is a vector the caller does not want.  The caller synchronises.
+template <class T>
+static void finish_dense(hipStream_t s, const T *from, void *to, uint64_t n, osp_memspace_t space, bool empty, T fill) {
+    if (!n || !to) return;
+    if (empty) {
+        const std::vector<T> fills(n, fill);
+        if (space == OSP_DEVICE) copy_h2d(to, fills.data(), n * sizeof(T), s);
+        else memcpy(to, fills.data(), n * sizeof(T));
+    } else if (space == OSP_DEVICE) {
+        OSP_HIP(hipMemcpyAsync(to, from, n * sizeof(T), hipMemcpyDeviceToDevice, s));
+    } else {
+        copy_d2h(to, from, n * sizeof(T), s);
     }
 }
 
@@ -1013,12 +1069,9 @@ static void reduce_impl(Context *ctx, const Result *in, int axis, int op, void *
     uint32_t launches = 0;
     // (the vector is formed in a pool buffer and copied out last: a call that fails leaves out_vec as it was)
     T *out = sc.get<T>(nout);
-    const T inf = std::numeric_limits<T>::infinity();
-    const T id = op == OSP_REDUCE_MIN ? inf : op == OSP_REDUCE_MAX ? -inf : T(0);
-    std::vector<T> ids;
     if (nout && nnz) {
         const int64_t *ptr = in->rowptr;
-        const T *vals = (const T *)in->vals;
+        T *vals = (T *)in->vals;
         if (axis == OSP_AXIS_COLS) {
             // the column-major view: entries of one column keep ascending row order (its kernels are not counted below)
             int64_t *vptr;
@@ -1034,28 +1087,17 @@ static void reduce_impl(Context *ctx, const Result *in, int axis, int op, void *
             reduce_count_kernel<T><<<grid_for(nout, 256), 256, 0, s>>>(ptr, nout, out, counter);
             launches = 2;
             long_segments = d2h((const uint64_t *)counter, s);
-        } else if (op == OSP_REDUCE_PLUS) {
-            reduce_segments<T, RED_PLUS>(sc, s, ptr, vals, nout, nnz, out, long_segments, launches);
+        } else if (op == OSP_REDUCE_PLUS) {   // (vals is read only: Values is the sinks' type as well)
+            reduce_segments<PlainAcc<RED_PLUS, T>>(sc, s, ptr, Values<T>{vals}, nout, nnz, Values<T>{out}, long_segments, launches);
         } else if (op == OSP_REDUCE_MIN) {
-            reduce_segments<T, RED_MIN>(sc, s, ptr, vals, nout, nnz, out, long_segments, launches);
+            reduce_segments<PlainAcc<RED_MIN, T>>(sc, s, ptr, Values<T>{vals}, nout, nnz, Values<T>{out}, long_segments, launches);
         } else {
-            reduce_segments<T, RED_MAX>(sc, s, ptr, vals, nout, nnz, out, long_segments, launches);
+            reduce_segments<PlainAcc<RED_MAX, T>>(sc, s, ptr, Values<T>{vals}, nout, nnz, Values<T>{out}, long_segments, launches);
         }
-    } else if (nout) {
-        ids.assign(nout, id);   // every segment is empty: no kernel
     }
     const float ms = fr.stop();
-    if (nout) {
-        if (!ids.empty()) {
-            if (space == OSP_DEVICE) copy_h2d(out_vec, ids.data(), nout * sizeof(T), s);
-            else memcpy(out_vec, ids.data(), nout * sizeof(T));
-        } else if (space == OSP_DEVICE) {
-            OSP_HIP(hipMemcpyAsync(out_vec, out, nout * sizeof(T), hipMemcpyDeviceToDevice, s));
-        } else {
-            copy_d2h(out_vec, out, nout * sizeof(T), s);
-        }
-        OSP_HIP(hipStreamSynchronize(s));
-    }
+    finish_dense(s, out, out_vec, nout, space, !nnz, red_identity<T>(op));
+    if (nout) OSP_HIP(hipStreamSynchronize(s));
     *st = osp_vector_stats_t{};
     st->nnz_in = nnz;
     st->nnz_out = nout;
@@ -1095,6 +1137,27 @@ static uint32_t mxv_group_log2(const Settings &env, uint64_t M, uint64_t nnz) {
     return lg;
 }
 
+// R over every row of (rowptr, products) into out, for mxv (PlainAcc) and mxv_arg (PairAcc): the rows of at most
+// kReduceBlock entries packed, the long ones block by block into stored accumulators, whose every further level is
+// reduce_segments'.
+template <class Acc, class Src, class Sink>
+static void mxv_levels(Scratch &sc, hipStream_t s, const int64_t *rowptr, Src products, uint64_t M, uint64_t nnz, uint32_t lg, Sink out,
+                       uint64_t &long_segments, uint32_t &launches) {
+    const uint64_t waves = (M + (kWave >> lg) - 1) >> (6 - lg);
+    segments_rows_kernel<Acc><<<grid_for(waves, kReduceWaves), kReduceWaves * kWave, 0, s>>>(rowptr, products, M, lg, out);
+    launches++;
+    const LongCut cut = cut_long_segments(sc, s, rowptr, M, nnz, nullptr, launches);
+    long_segments = cut.n_long;
+    if (!cut.n_long) return;
+    typename Acc::Stored partial;
+    get_stored(sc, cut.max_blocks, partial);
+    segments_blocks_kernel<Acc><<<grid_for(cut.max_blocks, kReduceWaves), kReduceWaves * kWave, 0, s>>>(rowptr, products, cut.long_segs, cut.blkptr,
+                                                                                                        cut.n_long, partial);
+    launches++;
+    uint64_t deeper = 0;
+    reduce_segments<Acc>(sc, s, cut.blkptr, partial, cut.n_long, cut.max_blocks, out, deeper, launches, cut.next_map);
+}
+
 template <class T>
 static void mxv_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, const void *x_in, void *y_out, osp_memspace_t space,
                      osp_mxv_stats_t *st) {
@@ -1108,57 +1171,17 @@ static void mxv_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, c
     uint32_t launches = 0;
     // (the vector is formed in a pool buffer and copied out last: x may be y, and a call that fails leaves y as it was)
     T *out = sc.get<T>(M);
-    std::vector<T> ids;
     if (M && nnz) {
         const T *x = sr.mul == OSP_EWISE_FIRST ? nullptr : to_device(sc, (const T *)x_in, N, space, s);
-        const int64_t *rowptr = in->rowptr;
-        const uint32_t *col = in->colidx;
-        const T *vals = (const T *)in->vals;
         mxv_with_ops(add, sr.mul, [&](auto a, auto m) {
             constexpr int ADD = decltype(a)::value, MUL = decltype(m)::value;
-            const uint64_t waves = (M + (kWave >> lg) - 1) >> (6 - lg);
-            mxv_rows_kernel<T, ADD, MUL><<<grid_for(waves, kReduceWaves), kReduceWaves * kWave, 0, s>>>(rowptr, col, vals, x, M, lg, out);
-            launches++;
-            if (nnz <= kReduceBlock) return;   // (no row can be long)
-            // the long rows, listed and cut into blocks as reduce_segments lists and cuts a level's long segments
-            unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MCL_COUNTERS);
-            zero_async(s, {{counters, MCL_COUNTERS * sizeof(uint64_t)}});
-            uint32_t *long_rows = sc.get<uint32_t>(nnz / ((uint64_t)kReduceBlock + 1) + 1);
-            mcl_classify_kernel<<<grid_for(M, 256), 256, 0, s>>>(rowptr, M, kReduceBlock, long_rows, counters);
-            launches += 2;
-            const uint64_t n_long = d2h((const uint64_t *)counters + MCL_NLONG, s);
-            long_segments = n_long;
-            if (!n_long) return;
-            const uint64_t max_blocks = nnz / kReduceBlock + n_long;
-            uint32_t *nblk = sc.get<uint32_t>(n_long + 1), *map = sc.get<uint32_t>(n_long);
-            int64_t *blkptr = sc.get<int64_t>(n_long + 1);
-            uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(n_long + 1));
-            T *partial = sc.get<T>(max_blocks);
-            reduce_long_setup_kernel<<<grid_for(n_long, 256), 256, 0, s>>>(rowptr, long_rows, n_long, nullptr, nblk, map);
-            launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{nblk}, n_long, (uint64_t *)blkptr, tmp, s);
-            mxv_blocks_kernel<T, ADD, MUL><<<grid_for(max_blocks, kReduceWaves), kReduceWaves * kWave, 0, s>>>(rowptr, col, vals, x, long_rows, blkptr,
-                                                                                                               n_long, partial);
-            launches++;
-            // the blocks' results are plain values: every further level is osp_csr_reduce's
-            uint64_t deeper = 0;
-            reduce_segments<T, ADD>(sc, s, blkptr, partial, n_long, max_blocks, out, deeper, launches, map);
+            const Products<T, MUL> products{in->colidx, (const T *)in->vals, x};
+            mxv_levels<PlainAcc<ADD, T>>(sc, s, in->rowptr, products, M, nnz, lg, Values<T>{out}, long_segments, launches);
         });
-    } else if (M) {
-        const T inf = std::numeric_limits<T>::infinity();
-        ids.assign(M, add == RED_MIN ? inf : add == RED_MAX ? -inf : T(0));   // every row is empty: no kernel
     }
     const float ms = fr.stop();
-    if (M) {
-        if (!ids.empty()) {
-            if (space == OSP_DEVICE) copy_h2d(y_out, ids.data(), M * sizeof(T), s);
-            else memcpy(y_out, ids.data(), M * sizeof(T));
-        } else if (space == OSP_DEVICE) {
-            OSP_HIP(hipMemcpyAsync(y_out, out, M * sizeof(T), hipMemcpyDeviceToDevice, s));
-        } else {
-            copy_d2h(y_out, out, M * sizeof(T), s);
-        }
-        OSP_HIP(hipStreamSynchronize(s));
-    }
+    finish_dense(s, out, y_out, M, space, !nnz, red_identity<T>(add));
+    if (M) OSP_HIP(hipStreamSynchronize(s));
     *st = osp_mxv_stats_t{};
     st->nnz_in = nnz;
     st->nnz_out = M;
@@ -1173,42 +1196,6 @@ static void mxv_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, c
 }
 
 // ---- mxv with the winner's column (osp_mxv_arg.h) ----
-// reduce_segments on pairs: the pair of every segment of (ptr, vals, cols) into (out, arg)[map[seg]], level by level.  Every
-// level lists, cuts and folds as reduce_segments does, so the value side has its bits.
-template <class T, int ADD>
-static void arg_segments(Scratch &sc, hipStream_t s, const int64_t *ptr, const T *vals, const uint32_t *cols, uint64_t nseg, uint64_t nent, T *out,
-                         int64_t *arg, uint32_t &launches, const uint32_t *map) {
-    for (;;) {
-        arg_short_kernel<T, ADD><<<grid_for(nseg, kReduceWaves), kReduceWaves * kWave, 0, s>>>(ptr, vals, cols, nseg, map, out, arg);
-        launches++;
-        if (nent <= kReduceBlock) return;   // (no segment can be long)
-        unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MCL_COUNTERS);
-        zero_async(s, {{counters, MCL_COUNTERS * sizeof(uint64_t)}});
-        uint32_t *long_segs = sc.get<uint32_t>(nent / ((uint64_t)kReduceBlock + 1) + 1);
-        mcl_classify_kernel<<<grid_for(nseg, 256), 256, 0, s>>>(ptr, nseg, kReduceBlock, long_segs, counters);
-        launches += 2;
-        const uint64_t n_long = d2h((const uint64_t *)counters + MCL_NLONG, s);
-        if (!n_long) return;
-        const uint64_t max_blocks = nent / kReduceBlock + n_long;
-        uint32_t *nblk = sc.get<uint32_t>(n_long + 1), *next_map = sc.get<uint32_t>(n_long);
-        int64_t *blkptr = sc.get<int64_t>(n_long + 1);
-        uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(n_long + 1));
-        T *partial = sc.get<T>(max_blocks);
-        uint32_t *pcol = sc.get<uint32_t>(max_blocks);
-        reduce_long_setup_kernel<<<grid_for(n_long, 256), 256, 0, s>>>(ptr, long_segs, n_long, map, nblk, next_map);
-        launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{nblk}, n_long, (uint64_t *)blkptr, tmp, s);
-        arg_blocks_kernel<T, ADD><<<grid_for(max_blocks, kReduceWaves), kReduceWaves * kWave, 0, s>>>(ptr, vals, cols, long_segs, blkptr, n_long, partial,
-                                                                                                      pcol);
-        launches++;
-        ptr = blkptr;
-        vals = partial;
-        cols = pcol;
-        nseg = n_long;
-        nent = max_blocks;
-        map = next_map;
-    }
-}
-
 template <class T>
 static void mxv_arg_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, const void *x_in, void *y_out, int64_t *arg_out,
                          osp_memspace_t space, osp_mxv_arg_stats_t *st) {
@@ -1224,44 +1211,13 @@ static void mxv_arg_impl(Context *ctx, const Result *in, const osp_semiring_t &s
     // were.  y is formed whether the caller wants it or not: the kernels do not branch on it)
     T *out = sc.get<T>(M);
     int64_t *arg = sc.get<int64_t>(M);
-    std::vector<T> ids;
     if (M && nnz) {
         const T *x = sr.mul == OSP_EWISE_FIRST ? nullptr : to_device(sc, (const T *)x_in, N, space, s);
-        const int64_t *rowptr = in->rowptr;
-        const uint32_t *col = in->colidx;
-        const T *vals = (const T *)in->vals;
         mxv_with_mul<RED_MIN>(sr.mul, [&](auto, auto m) {   // (the mul alone: the add is one of two)
-            constexpr int MUL = decltype(m)::value;
-            const auto with_add = [&](auto a) {
-                constexpr int ADD = decltype(a)::value;
-                const uint64_t waves = (M + (kWave >> lg) - 1) >> (6 - lg);
-                mxv_arg_rows_kernel<T, ADD, MUL><<<grid_for(waves, kReduceWaves), kReduceWaves * kWave, 0, s>>>(rowptr, col, vals, x, M, lg, out, arg);
-                launches++;
-                if (nnz <= kReduceBlock) return;   // (no row can be long)
-                // the long rows, listed and cut into blocks as mxv_impl lists and cuts them
-                unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MCL_COUNTERS);
-                zero_async(s, {{counters, MCL_COUNTERS * sizeof(uint64_t)}});
-                uint32_t *long_rows = sc.get<uint32_t>(nnz / ((uint64_t)kReduceBlock + 1) + 1);
-                mcl_classify_kernel<<<grid_for(M, 256), 256, 0, s>>>(rowptr, M, kReduceBlock, long_rows, counters);
-                launches += 2;
-                const uint64_t n_long = d2h((const uint64_t *)counters + MCL_NLONG, s);
-                long_segments = n_long;
-                if (!n_long) return;
-                const uint64_t max_blocks = nnz / kReduceBlock + n_long;
-                uint32_t *nblk = sc.get<uint32_t>(n_long + 1), *map = sc.get<uint32_t>(n_long);
-                int64_t *blkptr = sc.get<int64_t>(n_long + 1);
-                uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(n_long + 1));
-                T *partial = sc.get<T>(max_blocks);
-                uint32_t *pcol = sc.get<uint32_t>(max_blocks);
-                reduce_long_setup_kernel<<<grid_for(n_long, 256), 256, 0, s>>>(rowptr, long_rows, n_long, nullptr, nblk, map);
-                launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{nblk}, n_long, (uint64_t *)blkptr, tmp, s);
-                mxv_arg_blocks_kernel<T, ADD, MUL><<<grid_for(max_blocks, kReduceWaves), kReduceWaves * kWave, 0, s>>>(rowptr, col, vals, x, long_rows,
-                                                                                                                       blkptr, n_long, partial, pcol);
-                launches++;
-                arg_segments<T, ADD>(sc, s, blkptr, partial, pcol, n_long, max_blocks, out, arg, launches, map);
-            };
-            if (add == RED_MIN) with_add(std::integral_constant<int, RED_MIN>{});
-            else with_add(std::integral_constant<int, RED_MAX>{});
+            const Products<T, decltype(m)::value> products{in->colidx, (const T *)in->vals, x};
+            const ArgSink<T> sink{out, arg};
+            if (add == RED_MIN) mxv_levels<PairAcc<RED_MIN, T>>(sc, s, in->rowptr, products, M, nnz, lg, sink, long_segments, launches);
+            else mxv_levels<PairAcc<RED_MAX, T>>(sc, s, in->rowptr, products, M, nnz, lg, sink, long_segments, launches);
         });
         // the stats' rows_without (few workgroups: each ends in one atomic on one word)
         unsigned long long *without = (unsigned long long *)sc.get<uint64_t>(1);
@@ -1269,30 +1225,11 @@ static void mxv_arg_impl(Context *ctx, const Result *in, const osp_semiring_t &s
         arg_count_kernel<<<(unsigned)std::min<uint64_t>(grid_for(M, 256), 256), 256, 0, s>>>(arg, M, without);
         launches += 2;
         rows_without = d2h((const uint64_t *)without, s);
-    } else if (M) {
-        const T inf = std::numeric_limits<T>::infinity();
-        ids.assign(M, add == RED_MIN ? inf : -inf);   // every row is empty: no kernel
     }
     const float ms = fr.stop();
-    if (M) {
-        if (!ids.empty()) {
-            const std::vector<int64_t> none(M, -1);
-            if (space == OSP_DEVICE) {
-                if (y_out) copy_h2d(y_out, ids.data(), M * sizeof(T), s);
-                copy_h2d(arg_out, none.data(), M * sizeof(int64_t), s);
-            } else {
-                if (y_out) memcpy(y_out, ids.data(), M * sizeof(T));
-                memcpy(arg_out, none.data(), M * sizeof(int64_t));
-            }
-        } else if (space == OSP_DEVICE) {
-            if (y_out) OSP_HIP(hipMemcpyAsync(y_out, out, M * sizeof(T), hipMemcpyDeviceToDevice, s));
-            OSP_HIP(hipMemcpyAsync(arg_out, arg, M * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-        } else {
-            if (y_out) copy_d2h(y_out, out, M * sizeof(T), s);
-            copy_d2h(arg_out, arg, M * sizeof(int64_t), s);
-        }
-        OSP_HIP(hipStreamSynchronize(s));
-    }
+    finish_dense(s, out, y_out, M, space, !nnz, red_identity<T>(add));
+    finish_dense(s, arg, arg_out, M, space, !nnz, (int64_t)-1);
+    if (M) OSP_HIP(hipStreamSynchronize(s));
     *st = osp_mxv_arg_stats_t{};
     st->nnz_in = nnz;
     st->nnz_out = M;
@@ -1325,7 +1262,6 @@ static void mxd_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, c
     uint32_t launches = 0;
     // (the matrix is formed in a pool buffer and copied out last: x may be y, and a call that fails leaves y as it was)
     T *out = sc.get<T>(M * k);
-    std::vector<T> ids;
     if (M && k && nnz) {
         const T *x = sr.mul == OSP_EWISE_FIRST ? nullptr : to_device(sc, (const T *)x_in, N * k, space, s);
         const int64_t *rowptr = in->rowptr;
@@ -1337,44 +1273,20 @@ static void mxd_impl(Context *ctx, const Result *in, const osp_semiring_t &sr, c
             constexpr int ADD = decltype(a)::value, MUL = decltype(m)::value;
             mxd_rows_kernel<T, ADD, MUL><<<grid(M), kReduceWaves * kWave, 0, s>>>(rowptr, col, vals, x, M, k, lgk, out);
             launches++;
-            if (nnz <= kReduceBlock) return;   // (no row can be long)
-            // the long rows, listed and cut into blocks as mxv_impl lists and cuts them
-            unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(MCL_COUNTERS);
-            zero_async(s, {{counters, MCL_COUNTERS * sizeof(uint64_t)}});
-            uint32_t *long_rows = sc.get<uint32_t>(nnz / ((uint64_t)kReduceBlock + 1) + 1);
-            mcl_classify_kernel<<<grid_for(M, 256), 256, 0, s>>>(rowptr, M, kReduceBlock, long_rows, counters);
-            launches += 2;
-            const uint64_t n_long = d2h((const uint64_t *)counters + MCL_NLONG, s);
-            long_segments = n_long;
-            if (!n_long) return;
-            const uint64_t max_blocks = nnz / kReduceBlock + n_long;
-            uint32_t *nblk = sc.get<uint32_t>(n_long + 1), *map = sc.get<uint32_t>(n_long);
-            int64_t *blkptr = sc.get<int64_t>(n_long + 1);
-            uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(n_long + 1));
-            T *partial = sc.get<T>(max_blocks * k);
-            reduce_long_setup_kernel<<<grid_for(n_long, 256), 256, 0, s>>>(rowptr, long_rows, n_long, nullptr, nblk, map);
-            launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{nblk}, n_long, (uint64_t *)blkptr, tmp, s);
-            mxd_blocks_kernel<T, ADD, MUL><<<grid(max_blocks), kReduceWaves * kWave, 0, s>>>(rowptr, col, vals, x, long_rows, blkptr, n_long, k, lgk,
-                                                                                             partial);
-            mxd_upper_kernel<T, ADD><<<grid(n_long), kReduceWaves * kWave, 0, s>>>(long_rows, blkptr, n_long, partial, k, lgk, out);
+            // the long rows, listed and cut into blocks as mxv lists and cuts them
+            const LongCut cut = cut_long_segments(sc, s, rowptr, M, nnz, nullptr, launches);
+            long_segments = cut.n_long;
+            if (!cut.n_long) return;
+            T *partial = sc.get<T>(cut.max_blocks * k);
+            mxd_blocks_kernel<T, ADD, MUL><<<grid(cut.max_blocks), kReduceWaves * kWave, 0, s>>>(rowptr, col, vals, x, cut.long_segs, cut.blkptr, cut.n_long, k,
+                                                                                                 lgk, partial);
+            mxd_upper_kernel<T, ADD><<<grid(cut.n_long), kReduceWaves * kWave, 0, s>>>(cut.long_segs, cut.blkptr, cut.n_long, partial, k, lgk, out);
             launches += 2;
         });
-    } else if (M && k) {
-        const T inf = std::numeric_limits<T>::infinity();
-        ids.assign(M * k, add == RED_MIN ? inf : add == RED_MAX ? -inf : T(0));   // every row is empty: no kernel
     }
     const float ms = fr.stop();
-    if (M && k) {
-        if (!ids.empty()) {
-            if (space == OSP_DEVICE) copy_h2d(y_out, ids.data(), M * k * sizeof(T), s);
-            else memcpy(y_out, ids.data(), M * k * sizeof(T));
-        } else if (space == OSP_DEVICE) {
-            OSP_HIP(hipMemcpyAsync(y_out, out, M * k * sizeof(T), hipMemcpyDeviceToDevice, s));
-        } else {
-            copy_d2h(y_out, out, M * k * sizeof(T), s);
-        }
-        OSP_HIP(hipStreamSynchronize(s));
-    }
+    finish_dense(s, out, y_out, M * k, space, !nnz, red_identity<T>(add));
+    if (M && k) OSP_HIP(hipStreamSynchronize(s));
     *st = osp_mxd_stats_t{};
     st->nnz_in = nnz;
     st->nnz_out = M * k;

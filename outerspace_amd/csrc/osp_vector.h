@@ -3,9 +3,9 @@
 //
 // Reduce.  The order of a segment's reduction R is part of the interface (wave_ordered_reduce, osp_prims.h: the order of
 // osp_csr_inflate_prune's row sums) and depends on the segment's length alone, so the work may be cut freely:
-//   * a segment of at most kReduceBlock entries is ONE wave's R, four waves to a workgroup (reduce_short_kernel);
+//   * a segment of at most kReduceBlock entries is ONE wave's R, four waves to a workgroup (segments_short_kernel);
 //   * a longer segment is cut into blocks of kReduceBlock: one wave per BLOCK writes r_b = R(block b) to a pool buffer
-//     (reduce_blocks_kernel), and the blocks' results of one segment are a segment of the next level, reduced by the same
+//     (segments_blocks_kernel), and the blocks' results of one segment are a segment of the next level, reduced by the same
 //     two kernels until nothing is long (three levels reach 2^33 entries).  A frontier's one row of 2^20 entries is 512
 //     waves, a product's 2^22 rows of a dozen are 2^22: neither is one workgroup's loop.
 // Long segments are listed by mcl_classify_kernel (any order: every segment is handled on its own).  The column axis runs
@@ -27,18 +27,104 @@ constexpr uint32_t kReduceBlock = 2048;   // entries of one block of R: the long
 constexpr int kReduceWaves = 4;           // waves (segments or blocks) per workgroup
 static_assert(kReduceBlock == kMclLongMin, "mcl_classify_kernel's threshold and R's block are one number in the documents");
 
-// ---- reduce: segments of at most kReduceBlock entries, a wave each ---------------------------------------------------------
-// out[map ? map[seg] : seg] = R(segment seg); longer segments are left to the block path
-template <class T, int OP>
-__global__ __launch_bounds__(kReduceWaves *kWave) void reduce_short_kernel(const int64_t *__restrict__ ptr, const T *__restrict__ vals, uint64_t nseg,
-                                                                           const uint32_t *__restrict__ map, T *__restrict__ out) {
+// ---- the skeleton of R: three pieces, all template parameters (no branch on any of them in a kernel) -----------------------------
+//   the accumulator, what a lane carries: PlainAcc (p), PairAcc (p and the winner's column, osp_mxv_arg.h).  It starts as the
+//     identity, takes an entry of a source (take), another accumulator (combine) and hands out the one of the lane d above
+//     (down); Acc::Stored is the array form of its kind;
+//   the source, where entries come from: Values, Pairs (osp_mxv_arg.h), Products (osp_mxv.h).  value(i) is entry i's value; the
+//     sources a PairAcc reads have column(i) and value(i, that column) as well;
+//   the sink, where lane 0 stores: Values (out[i]; a level's partial results as well), Pairs (partial[i], pcol[i]) and ArgSink
+//     (out[i], arg[i]; both osp_mxv_arg.h).
+// DESIGN.md section 26 lists which operation runs which combination.
+
+// stored values: a source, and the sink of plain accumulators
+template <class T>
+struct Values {
+    T *vals;
+    __device__ __forceinline__ T value(uint64_t i) const { return vals[i]; }
+    template <class Acc>
+    __device__ __forceinline__ void store(uint64_t i, const Acc &a) const {
+        vals[i] = a.p;
+    }
+};
+
+template <int OP, class T>
+struct PlainAcc {
+    typedef Values<T> Stored;
+    T p = ordered_identity<OP, T>();
+    __device__ __forceinline__ void combine(const PlainAcc &o) { p = ordered_combine<OP>(p, o.p); }
+    // (asks the source for no column: Products then loads none under FIRST)
+    template <class Src>
+    __device__ __forceinline__ void take(const Src &src, uint64_t i) {
+        combine(PlainAcc{src.value(i)});
+    }
+    __device__ __forceinline__ PlainAcc down(int d) const { return PlainAcc{__shfl_down(p, d, kWave)}; }
+};
+
+// the butterfly's steps d < below, the same in every lane (64: a whole wave; g: a packed row's g lanes, osp_mxv.h)
+template <class Acc>
+__device__ __forceinline__ void butterfly(Acc &a, uint32_t below) {
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1)
+        if ((uint32_t)d < below) a.combine(a.down(d));
+}
+
+// R of the entries [b, b + m) of src by ONE wave, m <= kReduceBlock: wave_ordered_reduce (osp_prims.h) on any accumulator and
+// source.  Lane 0 holds the result.
+template <class Acc, class Src>
+__device__ __forceinline__ Acc wave_reduce(const Src &src, uint64_t b, uint64_t m) {
+    Acc a;
+    for (uint64_t i = lane_id(); i < m; i += kWave) a.take(src, b + i);
+    butterfly(a, kWave);
+    return a;
+}
+
+// ---- segments of at most kReduceBlock entries, a wave each ------------------------------------------------------------------
+// sink[map ? map[seg] : seg] = R(segment seg); longer segments are left to the block path
+template <class Acc, class Src, class Sink>
+__global__ __launch_bounds__(kReduceWaves *kWave) void segments_short_kernel(const int64_t *__restrict__ ptr, Src src, uint64_t nseg,
+                                                                             const uint32_t *__restrict__ map, Sink sink) {
     const uint64_t seg = (uint64_t)blockIdx.x * kReduceWaves + (threadIdx.x >> 6);
     if (seg >= nseg) return;
     const int64_t b = ptr[seg];
     const uint64_t m = (uint64_t)(ptr[seg + 1] - b);
     if (m > kReduceBlock) return;
-    const T r = wave_ordered_reduce<OP>(vals + b, m);
-    if (lane_id() == 0) out[map ? map[seg] : seg] = r;
+    const Acc a = wave_reduce<Acc>(src, (uint64_t)b, m);
+    if (lane_id() == 0) sink.store(map ? map[seg] : seg, a);
+}
+
+// ---- rows of at most kReduceBlock entries, packed: 64 >> lg consecutive rows per wave, g = 1 << lg lanes each when all of them
+// fit (osp_mxv.h states why g lanes and log2(g) shuffles are the whole of R) ----------------------------------------------------
+template <class Acc, class Src, class Sink>
+__global__ __launch_bounds__(kReduceWaves *kWave) void segments_rows_kernel(const int64_t *__restrict__ rowptr, Src src, uint64_t M, uint32_t lg,
+                                                                            Sink sink) {
+    const uint32_t lane = lane_id(), g = 1u << lg;
+    const uint64_t r0 = ((uint64_t)blockIdx.x * kReduceWaves + (threadIdx.x >> 6)) << (6 - lg);   // the batch's first row
+    if (r0 >= M) return;
+    const uint64_t row = r0 + (lane >> lg);
+    int64_t b = 0;
+    uint64_t m = 0;
+    if (row < M) {
+        b = rowptr[row];
+        m = (uint64_t)(rowptr[row + 1] - b);
+    }
+    if (!__any(m > g)) {
+        // (a lane past its row's entries holds the identity, which changes no accumulator it is combined into; a shuffle reaches
+        // across a group's end only for lanes whose accumulator nobody uses)
+        const uint32_t k = lane & (g - 1);
+        Acc a;
+        if (k < m) a.take(src, (uint64_t)b + k);
+        butterfly(a, g);
+        if (k == 0 && row < M) sink.store(row, a);
+        return;
+    }
+    // a row of the batch does not fit its g lanes: the rows one after another, 64 lanes each
+    for (uint32_t r = 0; r < (kWave >> lg) && r0 + r < M; r++) {
+        const uint64_t rb = (uint64_t)__shfl((long long)b, (int)(r << lg), kWave), rm = (uint64_t)__shfl((long long)m, (int)(r << lg), kWave);
+        if (rm > kReduceBlock) continue;   // (the block path writes it)
+        const Acc a = wave_reduce<Acc>(src, rb, rm);
+        if (lane == 0) sink.store(r0 + r, a);
+    }
 }
 
 // ---- reduce: what a level's long segments hand to the next level -----------------------------------------------------------
@@ -55,17 +141,17 @@ __global__ __launch_bounds__(256) void reduce_long_setup_kernel(const int64_t *_
 
 // partial[w] = R(block w): block w belongs to the long segment k with blkptr[k] <= w < blkptr[k + 1] and is that
 // segment's block w - blkptr[k]; (blkptr, partial) are the next level's segments
-template <class T, int OP>
-__global__ __launch_bounds__(kReduceWaves *kWave) void reduce_blocks_kernel(const int64_t *__restrict__ ptr, const T *__restrict__ vals,
-                                                                            const uint32_t *__restrict__ long_segs, const int64_t *__restrict__ blkptr,
-                                                                            uint64_t n_long, T *__restrict__ partial) {
+template <class Acc, class Src, class Sink>
+__global__ __launch_bounds__(kReduceWaves *kWave) void segments_blocks_kernel(const int64_t *__restrict__ ptr, Src src,
+                                                                              const uint32_t *__restrict__ long_segs, const int64_t *__restrict__ blkptr,
+                                                                              uint64_t n_long, Sink partial) {
     const uint64_t w = (uint64_t)blockIdx.x * kReduceWaves + (threadIdx.x >> 6);
     if (w >= (uint64_t)blkptr[n_long]) return;   // (the grid covers the host's upper bound of the blocks)
     const uint64_t k = upper_bound_dev(blkptr, 0, n_long + 1, (int64_t)w) - 1;   // (same addresses in every lane)
     const uint32_t seg = long_segs[k];
     const uint64_t b = (uint64_t)ptr[seg] + (w - (uint64_t)blkptr[k]) * kReduceBlock, e = (uint64_t)ptr[seg + 1];
-    const T r = wave_ordered_reduce<OP>(vals + b, e - b < kReduceBlock ? e - b : (uint64_t)kReduceBlock);
-    if (lane_id() == 0) partial[w] = r;
+    const Acc a = wave_reduce<Acc>(src, b, e - b < kReduceBlock ? e - b : (uint64_t)kReduceBlock);
+    if (lane_id() == 0) partial.store(w, a);
 }
 
 // ---- reduce, COUNT: out[seg] = (T)length; reads no value.  counter += segments longer than kReduceBlock ---------------------

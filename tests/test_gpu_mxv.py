@@ -14,6 +14,7 @@ import torch
 from outerspace_amd import _lib
 from outerspace_amd import generators as gen
 from outerspace_amd import spgemm as S
+from tests import mxd_model
 from tests import mxv_model as model
 from tests import test_gpu_apply_mask as am   # the input builders only
 from tests import test_gpu_vector as tv       # its cached inputs and vectors only
@@ -142,6 +143,24 @@ def test_every_group_gives_the_same_bits(mctx, dt, monkeypatch):
                 assert np.array_equal(_bits(got[g]), _bits(got[None])), (add, mul, g)
     finally:
         src.close()
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_launches_follow_the_formula(mctx, dt):
+    """stats.launches is osp_csr_mxd's count (tests/mxd_model.py): the rows kernel; the zeroing and the listing of the long
+    rows; with a long row the setup, the scan (one launch for one entry), the blocks and the next level's short kernel."""
+    ncol = 1 << 12
+    x = np.random.default_rng(44).standard_normal(ncol).astype(dt)
+    for lengths, launches in zip(tv.LAUNCH_SHAPES, (1, 3, 7)):
+        csr = am._csr_from_lengths(lengths, ncol, dt, seed=43)
+        src = _upload(mctx, ncol, csr)
+        try:
+            for add, mul in [("plus", "times"), ("min", "plus")]:
+                got, st = src.mxv(x, add, mul, space="host")
+                _assert_vector(got, model.mxv(*csr, x, add, mul)[0], add)
+                assert st["launches"] == launches == mxd_model.expected_launches(csr[0], scan_launches=1), (lengths, add, mul)
+        finally:
+            src.close()
 
 
 def test_a_product_and_its_addition_are_two_roundings(mctx):

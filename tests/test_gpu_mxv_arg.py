@@ -12,6 +12,7 @@ import torch
 from outerspace_amd import _lib
 from outerspace_amd import generators as gen
 from outerspace_amd import spgemm as S
+from tests import mxd_model
 from tests import mxv_arg_model as model
 from tests import test_gpu_apply_mask as am   # the input builders only
 from tests import test_gpu_vector as tv       # its cached inputs and vectors only
@@ -101,6 +102,23 @@ def test_every_group_gives_the_same_arg_and_the_same_bits(mctx, dt, monkeypatch)
                 assert _same_bits(y, ref), (add, mul, g)
     finally:
         src.close()
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_launches_follow_the_formula(mctx, dt):
+    """stats.launches is osp_csr_mxv's count (tests/test_gpu_mxv.py) plus the two of the stats' rows_without."""
+    ncol = 1 << 12
+    x = np.random.default_rng(46).standard_normal(ncol).astype(dt)
+    for lengths, launches in zip(tv.LAUNCH_SHAPES, (1 + 2, 3 + 2, 7 + 2)):
+        csr = am._csr_from_lengths(lengths, ncol, dt, seed=45)
+        src = _upload(mctx, ncol, csr)
+        try:
+            for add, mul in [("min", "times"), ("max", "plus")]:
+                y, arg, st = src.mxv_arg(x, add, mul, space="host")
+                assert np.array_equal(arg, model.arg_rows(csr[0], csr[1], model.products(*csr, x, mul), add)), (lengths, add, mul)
+                assert st["launches"] == launches == mxd_model.expected_launches(csr[0], scan_launches=1) + 2, (lengths, add, mul)
+        finally:
+            src.close()
 
 
 # ---- rows with ties, written out by hand ------------------------------------------------------------------------------------------

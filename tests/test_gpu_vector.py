@@ -13,7 +13,7 @@ import torch
 from outerspace_amd import _lib
 from outerspace_amd import generators as gen
 from outerspace_amd import spgemm as S
-from tests import bfs_model, ewise_model, truss_model
+from tests import bfs_model, ewise_model, mxd_model, truss_model
 from tests import test_gpu_apply_mask as am   # the input builders only
 from tests import vector_model as model
 
@@ -98,6 +98,31 @@ def test_reduce_third_level(mctx):
         assert got.tolist() == [0.0, float(m), 0.0]
     finally:
         src.close()
+
+
+# row lengths around the block of 2048: nothing can be long, nnz > 2048 without a long row, one long row of two blocks
+LAUNCH_SHAPES = [[3, 0, 2000, 45], [2000, 0, 2000, 7], [2, 2049, 2]]
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_reduce_launches_follow_the_formula(mctx, dt):
+    """stats.launches of plus, min and max is osp_csr_mxd's count (tests/mxd_model.py) on the segments of the axis: the short
+    kernel; the zeroing and the listing of the long segments; with a long one the setup, the scan (one launch for one entry),
+    the blocks and the next level's short kernel."""
+    ncol = 1 << 12
+    for lengths, launches in zip(LAUNCH_SHAPES, (1, 3, 7)):
+        csr = am._csr_from_lengths(lengths, ncol, dt, seed=23)
+        assert mxd_model.expected_launches(csr[0], scan_launches=1) == launches
+        by_axis = {"rows": launches, "cols": mxd_model.expected_launches(model.column_view(*csr, ncol)[0], scan_launches=1)}
+        src = _upload(mctx, ncol, csr)
+        try:
+            for axis in model.AXES:
+                for op in ("plus", "min", "max"):
+                    got, st = src.reduce(axis, op)
+                    _assert_vector(got, model.reduce(*csr, ncol, axis, op)[0], op)
+                    assert st["launches"] == by_axis[axis], (lengths, axis, op)
+        finally:
+            src.close()
 
 
 @pytest.mark.parametrize("dt", DTYPES)
