@@ -186,6 +186,8 @@ const char *osp_status_string(int status);
  * `space` says where ALL six input arrays live.  cfg may be NULL (defaults).
  * Replaces cscMulcsr (SimSpGEMM.cpp:265-281) + deduplicateCOO (:519-535); the result has
  * ascending column indices per row and keeps entries that cancel to zero, as the reference does.
+ * M == 0, K == 0 and N == 0 are legal (the pointer arrays still hold K + 1 entries): no partial product exists, nothing is
+ * multiplied or merged, and C is an M x N result without entries.
  */
 int osp_spgemm_csc_csr(osp_context_t ctx, osp_dtype_t dtype, uint64_t M, uint64_t K, uint64_t N,
                        const int64_t *a_colptr, const uint32_t *a_rowidx, const void *a_vals,

@@ -58,7 +58,8 @@ typedef struct osp_mcl_stats {
  * Values must be finite and >= 0.  With validate != 0 a negative, NaN or infinite value is OSP_ERR_ARG, checked on the
  * device before anything is written; without it the result for such input is unspecified (no access leaves the arrays).
  * power < 1 or NaN, a NaN or negative threshold, a non-zero reserved word, a null in, step or out, or a result of
- * osp_spgemm_partials is OSP_ERR_ARG.  On any error *out and *stats are left as they were.
+ * osp_spgemm_partials is OSP_ERR_ARG.  On any error *out and *stats are left as they were.  An `in` without entries, M == 0
+ * and N == 0 included, is legal: out is an empty M x N result and every row counter is 0.
  *
  * stats (may be NULL): nnz_in / nnz_out, the row counters above, rows_long = the rows longer than the library's class
  * boundary (one workgroup each instead of one wave), ms_total = device time of the call, ms_select_kernel = the part of

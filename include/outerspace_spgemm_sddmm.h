@@ -52,8 +52,8 @@ typedef struct osp_sddmm_stats {
  * nothing is contracted.  Equivalently: take the one-row CSR that holds x[i, 0..k) at the columns 0..k-1; d at (i, j) equals
  * osp_csr_mxv of that CSR with the vector y[j, :], bit for bit.
  *
- * k == 0 is legal (d is the identity).  An `in` without entries is legal and launches nothing: out is an empty M x N
- * result.  out's rowptr and colidx are copies of in's.
+ * k == 0 is legal (d is the identity).  An `in` without entries (M == 0 and N == 0 included) is legal and launches nothing,
+ * and reads neither x nor y: out is an empty M x N result.  out's rowptr and colidx are copies of in's.
  *
  * A call that fails leaves *out and *stats as they were.  OSP_ERR_ARG: a null in, sr or out; a null x or y that mul needs;
  * an operator outside its list; a non-zero reserved word; a bad space; a result of osp_spgemm_partials;

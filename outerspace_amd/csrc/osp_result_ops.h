@@ -1052,6 +1052,9 @@ static void finish_dense(hipStream_t s, const T *from, void *to, uint64_t n, osp
         if (space == OSP_DEVICE) copy_h2d(to, fills.data(), n * sizeof(T), s);
         else memcpy(to, fills.data(), n * sizeof(T));
     } else if (space == OSP_DEVICE) {
+#ifdef OSP_TEST_DENSE_SHORT   // (defined only to show that tests/result_chain.py notices an element of a caller's output that nothing wrote)
+        n--;
+#endif
         OSP_HIP(hipMemcpyAsync(to, from, n * sizeof(T), hipMemcpyDeviceToDevice, s));
     } else {
         copy_d2h(to, from, n * sizeof(T), s);
