@@ -150,6 +150,13 @@ class MxmStats(_Stats):
                 ("short_rows", C.c_uint64), ("long_rows", C.c_uint64), ("batches", C.c_uint32), ("launches", C.c_uint32),
                 ("ms_total", C.c_float), ("reserved", C.c_uint32 * 7)]
 
+
+class MxmMaskedStats(_Stats):
+    """osp_mxm_masked_stats_t"""
+    _fields_ = [("nnz_a", C.c_uint64), ("nnz_b", C.c_uint64), ("nnz_mask", C.c_uint64), ("products", C.c_uint64),
+                ("products_kept", C.c_uint64), ("nnz_out", C.c_uint64), ("short_rows", C.c_uint64), ("long_rows", C.c_uint64),
+                ("batches", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float), ("reserved", C.c_uint32 * 7)]
+
 # the add operators osp_csr_mxv takes: the value operators of osp_csr_reduce (mul: MXM_MUL_OPS)
 MXV_ADD_OPS = {name: EWISE_OPS[name] for name in ("plus", "min", "max")}
 
@@ -282,6 +289,9 @@ VECTOR_EXPORTS = ["osp_csr_reduce", "osp_csr_apply_vectors", "osp_csr_select_ver
 # every symbol include/outerspace_spgemm_mxm.h declares
 MXM_EXPORTS = ["osp_csr_mxm"]
 
+# every symbol include/outerspace_spgemm_mxm_masked.h declares
+MXM_MASKED_EXPORTS = ["osp_csr_mxm_masked"]
+
 # every symbol include/outerspace_spgemm_transpose.h declares
 TRANSPOSE_EXPORTS = ["osp_csr_transpose"]
 
@@ -388,6 +398,7 @@ def lib():
     L.osp_csr_apply_vectors.argtypes = [vp, C.POINTER(VectorApply), vp, vp, i32, C.POINTER(vp), C.POINTER(VectorStats)]
     L.osp_csr_select_vertices.argtypes = [vp, vp, vp, i32, C.POINTER(vp), C.POINTER(VectorStats)]
     L.osp_csr_mxm.argtypes = [vp, vp, C.POINTER(Semiring), C.POINTER(vp), C.POINTER(MxmStats)]
+    L.osp_csr_mxm_masked.argtypes = [vp, vp, vp, i32, C.POINTER(Semiring), C.POINTER(vp), C.POINTER(MxmMaskedStats)]
     L.osp_csr_transpose.argtypes = [vp, C.POINTER(Transpose), C.POINTER(vp), C.POINTER(TransposeStats)]
     L.osp_csr_mxv.argtypes = [vp, C.POINTER(Semiring), vp, vp, i32, C.POINTER(MxvStats)]
     L.osp_csr_mxv_arg.argtypes = [vp, C.POINTER(Semiring), vp, vp, vp, i32, C.POINTER(MxvArgStats)]

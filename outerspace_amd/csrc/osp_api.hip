@@ -28,6 +28,7 @@
 #include "../../include/outerspace_spgemm_ewise.h"
 #include "../../include/outerspace_spgemm_vector.h"
 #include "../../include/outerspace_spgemm_mxm.h"
+#include "../../include/outerspace_spgemm_mxm_masked.h"
 #include "../../include/outerspace_spgemm_transpose.h"
 #include "../../include/outerspace_spgemm_mxv.h"
 #include "../../include/outerspace_spgemm_mxv_arg.h"
@@ -696,6 +697,19 @@ static int csr_vector_op(const Result *in, bool others_given, Stats *stats, Chec
     });
 }
 
+// what osp_csr_mxm and osp_csr_mxm_masked refuse of the semiring and the two operands, in this order
+static void check_mxm(const Result *a, const Result *b, const osp_semiring_t *sr, const char *op) {
+    const std::string o(op);
+    if (sr->add != OSP_EWISE_PLUS && sr->add != OSP_EWISE_MIN && sr->add != OSP_EWISE_MAX && sr->add != OSP_EWISE_FIRST)
+        throw Error(OSP_ERR_ARG, o + ": add is not one of PLUS, MIN, MAX, FIRST");
+    if (sr->mul < OSP_EWISE_PLUS || sr->mul > OSP_EWISE_SECOND) throw Error(OSP_ERR_ARG, o + ": mul is not one of TIMES, PLUS, MIN, MAX, FIRST, SECOND");
+    check_reserved(sr->reserved, op);
+    if (a->ctx != b->ctx) throw Error(OSP_ERR_ARG, o + ": the operands belong to different contexts");
+    if (a->dtype != b->dtype) throw Error(OSP_ERR_ARG, o + ": the operands' dtypes differ");
+    if (a->info.nnz_c >= 0xffffffffull || b->info.nnz_c >= 0xffffffffull)
+        throw Error(OSP_ERR_ARG, o + ": operands with >= 2^32 - 1 non-zeros are not supported");
+}
+
 }  // namespace osp
 
 #include "osp_multi.h"
@@ -911,16 +925,23 @@ int osp_csr_ewise(osp_result_t a_, osp_result_t b_, const osp_ewise_t *ew, osp_r
 int osp_csr_mxm(osp_result_t a_, osp_result_t b_, const osp_semiring_t *sr, osp_result_t *out, osp_mxm_stats_t *stats) {
     Result *a = (Result *)a_, *b = (Result *)b_;
     return csr_op({a, b}, sr != nullptr, out, stats, [&] {
-        if (sr->add != OSP_EWISE_PLUS && sr->add != OSP_EWISE_MIN && sr->add != OSP_EWISE_MAX && sr->add != OSP_EWISE_FIRST)
-            throw Error(OSP_ERR_ARG, "mxm: add is not one of PLUS, MIN, MAX, FIRST");
-        if (sr->mul < OSP_EWISE_PLUS || sr->mul > OSP_EWISE_SECOND) throw Error(OSP_ERR_ARG, "mxm: mul is not one of TIMES, PLUS, MIN, MAX, FIRST, SECOND");
-        check_reserved(sr->reserved, "mxm");
-        if (a->ctx != b->ctx) throw Error(OSP_ERR_ARG, "mxm: the operands belong to different contexts");
-        if (a->dtype != b->dtype) throw Error(OSP_ERR_ARG, "mxm: the operands' dtypes differ");
-        if (a->info.nnz_c >= 0xffffffffull || b->info.nnz_c >= 0xffffffffull)
-            throw Error(OSP_ERR_ARG, "mxm: operands with >= 2^32 - 1 non-zeros are not supported");
+        check_mxm(a, b, sr, "mxm");
         if (a->info.N != b->info.M) throw Error(OSP_ERR_DIM, "mxm: a's N differs from b's M");
     }, [&](auto tag, Result *res, osp_mxm_stats_t *st) { mxm_impl<decltype(tag)>(a->ctx, a, b, res, *sr, st); });
+}
+
+int osp_csr_mxm_masked(osp_result_t a_, osp_result_t b_, osp_result_t mask_, int complement, const osp_semiring_t *sr, osp_result_t *out,
+                       osp_mxm_masked_stats_t *stats) {
+    Result *a = (Result *)a_, *b = (Result *)b_, *mask = (Result *)mask_;
+    return csr_op({a, b, mask}, sr != nullptr, out, stats, [&] {
+        check_mxm(a, b, sr, "mxm_masked");
+        if (mask->ctx != a->ctx) throw Error(OSP_ERR_ARG, "mxm_masked: the mask belongs to a different context");
+        if (mask->info.nnz_c >= 0xffffffffull) throw Error(OSP_ERR_ARG, "mxm_masked: a mask with >= 2^32 - 1 entries is not supported");
+        if (a->info.N != b->info.M) throw Error(OSP_ERR_DIM, "mxm_masked: a's N differs from b's M");
+        if (mask->info.M != a->info.M || mask->info.N != b->info.N) throw Error(OSP_ERR_DIM, "mxm_masked: the mask's shape differs from (a's M, b's N)");
+    }, [&](auto tag, Result *res, osp_mxm_masked_stats_t *st) {
+        mxm_masked_impl<decltype(tag)>(a->ctx, a, b, mask, complement, res, *sr, st);
+    });
 }
 
 int osp_csr_transpose(osp_result_t in_, const osp_transpose_t *tp, osp_result_t *out, osp_transpose_stats_t *stats) {

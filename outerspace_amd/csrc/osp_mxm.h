@@ -26,7 +26,21 @@
 // loop.  The expansion is instantiated per mul, the folds per add; the short kernel is instantiated per add and selects its
 // product loop by a wave-uniform switch on mul.  Values that are only moved are moved as integers of their width.
 // No float atomics, no waiting between workgroups, no scratch.
+//
+// The MASKED form (osp_csr_mxm_masked, include/outerspace_spgemm_mxm_masked.h) drops a product whose
+// (row, column) a CSR pattern rejects where the product is formed.  The short kernel and the expansion are templated on it
+// (`if constexpr`: the unmasked instantiations run the instructions they ran; each takes one more by-value argument it never
+// reads, so the kernarg layout grew); everything after the expansion is the same code working on the kept products only.
+//   short rows the products are formed in rounds of 64 in (k, column) order; a lane bisects its product's column in mask row
+//              i (read by this one wave: it stays in cache), and the survivors go to LDS compacted in the same order (ballot,
+//              prefix popcount).  The key is (column << 32 | compact position): unique, so the sort stays stable by column,
+//              and its padded length follows the KEPT count.  A rejected product's values are not loaded.
+//   long rows  mxm_mask_flag_kernel (a lane per formed product, no value read) writes one verdict bit per product; the scan
+//              of the words' popcounts (osp_compact.h) and mxm_kept_list_kernel give the kept products' original positions
+//              and the long rows' KEPT offsets; the expansion takes a lane per kept product, and the sort, the fold and the
+//              counts see the kept offsets.  Positions stay 32 bits.
 #pragma once
+#include "osp_compact.h"
 #include "osp_ewise.h"
 
 namespace osp {
@@ -101,14 +115,33 @@ __device__ __forceinline__ uint64_t mxm_owner(const uint64_t *__restrict__ wscan
     return upper_bound_dev(wscan, e0, e1, x) - 1;
 }
 
+// The mask of the masked form, as the kernels take it: a CSR pattern with the output's shape, the sense, and the call's count
+// of kept products of short rows.  The unmasked instantiations never touch it.
+struct MxmMask {
+    const int64_t *rowptr;
+    const uint32_t *col;
+    int complement;
+    unsigned long long *kept_short;
+};
+// the verdict on a product at column j of output row i: the mask holds (i, j), or -- complemented -- does not
+__device__ __forceinline__ bool mxm_mask_admits(const MxmMask &m, uint64_t i, uint32_t j) {
+    const uint64_t m1 = (uint64_t)m.rowptr[i + 1];
+    const uint64_t at = lower_bound_dev(m.col, (uint64_t)m.rowptr[i], m1, j);
+    const bool member = at < m1 && m.col[at] == j;
+    return member != (m.complement != 0);
+}
+
 // ---- short rows: one wave per row of the batch ------------------------------------------------------------------------------
 // grid: the batch's rows; block: one wave.  A row without products gets its count 0 here, a long row is left to the long path.
-template <class T, int ADD>
+// MASKED: only the products the mask admits enter LDS, compacted in their order; U below is then the KEPT count (a row that
+// keeps nothing gets its count 0), and the slot is still the row's place among the FORMED products.
+template <class T, int ADD, bool MASKED>
 __global__ __launch_bounds__(kWave) void mxm_short_kernel(const int64_t *__restrict__ a_rowptr, const uint32_t *__restrict__ a_col,
                                                           const ValueBits<T> *__restrict__ a_val, const int64_t *__restrict__ b_rowptr,
                                                           const uint32_t *__restrict__ b_col, const ValueBits<T> *__restrict__ b_val,
                                                           const uint64_t *__restrict__ wscan, uint64_t r0, uint32_t cap, int mul, uint64_t p0,
-                                                          uint32_t *__restrict__ tcol, ValueBits<T> *__restrict__ tval, uint32_t *__restrict__ cnt) {
+                                                          uint32_t *__restrict__ tcol, ValueBits<T> *__restrict__ tval, uint32_t *__restrict__ cnt,
+                                                          MxmMask mask) {
 #pragma clang fp contract(off)
     typedef ValueBits<T> V;
     __shared__ uint64_t skey[kMxmShortMax];
@@ -122,19 +155,52 @@ __global__ __launch_bounds__(kWave) void mxm_short_kernel(const int64_t *__restr
         return;
     }
     if (u64 > cap) return;
-    const uint32_t U = (uint32_t)u64;
+    uint32_t U = (uint32_t)u64;
     uint32_t n2 = 1;   // the sorted length: a power of two, padded with keys above every real one
-    while (n2 < U) n2 <<= 1;
-    // 1. the products, in (k ascending, column ascending) order
-    for (uint32_t t = lane; t < n2; t += kWave) {
-        uint64_t key = ~0ull;
-        if (t < U) {
-            const uint64_t e = mxm_owner(wscan, e0, e1, w0 + t);
-            const uint64_t q = (uint64_t)b_rowptr[a_col[e]] + (w0 + t - wscan[e]);
-            key = ((uint64_t)b_col[q] << 32) | t;
-            sval[t] = mxm_mul<T, V>(mul, a_val[e], b_val[q]);
+    if constexpr (!MASKED) {
+        while (n2 < U) n2 <<= 1;
+        // 1. the products, in (k ascending, column ascending) order
+        for (uint32_t t = lane; t < n2; t += kWave) {
+            uint64_t key = ~0ull;
+            if (t < U) {
+                const uint64_t e = mxm_owner(wscan, e0, e1, w0 + t);
+                const uint64_t q = (uint64_t)b_rowptr[a_col[e]] + (w0 + t - wscan[e]);
+                key = ((uint64_t)b_col[q] << 32) | t;
+                sval[t] = mxm_mul<T, V>(mul, a_val[e], b_val[q]);
+            }
+            skey[t] = key;
         }
-        skey[t] = key;
+    } else {
+        // 1. the products the mask admits, in (k ascending, column ascending) order: rounds of 64 formed products, the
+        // survivors of a round behind those of the rounds before it (a compact position never exceeds the formed one)
+        uint32_t kept = 0;
+        for (uint32_t base = 0; base < U; base += kWave) {
+            const uint32_t t = base + lane;
+            bool keep = false;
+            uint64_t e = 0, q = 0;
+            uint32_t col = 0;
+            if (t < U) {
+                e = mxm_owner(wscan, e0, e1, w0 + t);
+                q = (uint64_t)b_rowptr[a_col[e]] + (w0 + t - wscan[e]);
+                col = b_col[q];
+                keep = mxm_mask_admits(mask, i, col);
+            }
+            const uint64_t keeps = __ballot(keep);
+            if (keep) {
+                const uint32_t c = kept + (uint32_t)__popcll(keeps & lanemask_lt());
+                skey[c] = ((uint64_t)col << 32) | c;
+                sval[c] = mxm_mul<T, V>(mul, a_val[e], b_val[q]);
+            }
+            kept += (uint32_t)__popcll(keeps);
+        }
+        U = kept;
+        if (U == 0) {
+            if (lane == 0) cnt[i] = 0;
+            return;
+        }
+        if (lane == 0) atomicAdd(mask.kept_short, (unsigned long long)U);
+        while (n2 < U) n2 <<= 1;
+        for (uint32_t t = U + lane; t < n2; t += kWave) skey[t] = ~0ull;
     }
     __syncthreads();
     // 2. bitonic sort of the unique keys (column, position): stable by column
@@ -201,22 +267,27 @@ __global__ __launch_bounds__(256) void mxm_long_list_kernel(const uint32_t *__re
         loff[rank[x]] = lpscan[x];
     }
 }
-// a lane per product of the long rows: key = (long-row rank << colbits) | column, payload = the product's position
-template <class T, int MUL>
+// a lane per product of the long rows: key = (long-row rank << colbits) | column, payload = the product's position.
+// MASKED: a lane per KEPT product x; kept_pos[x] is its position among the FORMED products of the long rows, which loff (the
+// formed offsets) decodes; keys, positions and values are written at x, so what follows sees the kept products only.
+template <class T, int MUL, bool MASKED>
 __global__ __launch_bounds__(256) void mxm_expand_kernel(const int64_t *__restrict__ a_rowptr, const uint32_t *__restrict__ a_col,
                                                          const ValueBits<T> *__restrict__ a_val, const int64_t *__restrict__ b_rowptr,
                                                          const uint32_t *__restrict__ b_col, const ValueBits<T> *__restrict__ b_val,
                                                          const uint64_t *__restrict__ wscan, const uint32_t *__restrict__ long_rows,
                                                          const uint64_t *__restrict__ loff, uint32_t nlong, uint64_t nprod, int colbits,
-                                                         uint64_t *__restrict__ key, uint32_t *__restrict__ pos, ValueBits<T> *__restrict__ pval) {
+                                                         uint64_t *__restrict__ key, uint32_t *__restrict__ pos, ValueBits<T> *__restrict__ pval,
+                                                         const uint32_t *__restrict__ kept_pos) {
 #pragma clang fp contract(off)
     typedef ValueBits<T> V;
     const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= nprod) return;
-    const uint64_t h = upper_bound_dev(loff, 0, (uint64_t)nlong + 1, x) - 1;
+    uint64_t y = x;   // the product's position among the formed products of the long rows
+    if constexpr (MASKED) y = kept_pos[x];
+    const uint64_t h = upper_bound_dev(loff, 0, (uint64_t)nlong + 1, y) - 1;
     const uint64_t i = long_rows[h];
     const uint64_t e0 = (uint64_t)a_rowptr[i], e1 = (uint64_t)a_rowptr[i + 1];
-    const uint64_t w = wscan[e0] + (x - loff[h]);
+    const uint64_t w = wscan[e0] + (y - loff[h]);
     const uint64_t e = mxm_owner(wscan, e0, e1, w);
     const uint64_t q = (uint64_t)b_rowptr[a_col[e]] + (w - wscan[e]);
     key[x] = (h << colbits) | (uint64_t)b_col[q];
@@ -224,6 +295,51 @@ __global__ __launch_bounds__(256) void mxm_expand_kernel(const int64_t *__restri
     // (FIRST reads no value of b, SECOND none of a: the unused load is gone with the constant MUL)
     pval[x] = ewise_apply<MUL, T, V>(MUL == EW_SECOND ? (V)0 : a_val[e], MUL == EW_FIRST ? (V)0 : b_val[q]);
 }
+// ---- the masked form's long rows: one verdict bit per formed product, then the kept products listed ------------------------------
+// a lane per formed product x of the batch's long rows (decoded as the expansion decodes it): the owner, the column, a
+// bisection in the mask row, a verdict.  No value is read.  The 64 verdicts of a wave are word x >> 6 of `bits`.
+__global__ __launch_bounds__(256) void mxm_mask_flag_kernel(const int64_t *__restrict__ a_rowptr, const uint32_t *__restrict__ a_col,
+                                                            const int64_t *__restrict__ b_rowptr, const uint32_t *__restrict__ b_col,
+                                                            const uint64_t *__restrict__ wscan, const uint32_t *__restrict__ long_rows,
+                                                            const uint64_t *__restrict__ loff, uint32_t nlong, uint64_t nprod, MxmMask mask,
+                                                            uint64_t *__restrict__ bits) {
+    const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool keep = false;
+    if (x < nprod) {
+        const uint64_t h = upper_bound_dev(loff, 0, (uint64_t)nlong + 1, x) - 1;
+        const uint64_t i = long_rows[h];
+        const uint64_t e0 = (uint64_t)a_rowptr[i], e1 = (uint64_t)a_rowptr[i + 1];
+        const uint64_t w = wscan[e0] + (x - loff[h]);
+        const uint64_t e = mxm_owner(wscan, e0, e1, w);
+        const uint64_t q = (uint64_t)b_rowptr[a_col[e]] + (w - wscan[e]);
+        keep = mxm_mask_admits(mask, i, b_col[q]);
+    }
+    store_verdicts(keep, x, nprod, bits);
+}
+// kpos: the exclusive scan of the words' popcounts.  kept_pos[c] = the formed position of the c-th kept product (a lane per
+// formed product), and kloff[h] = the kept products before long row h, kloff[nlong] = all of them (a lane per long row, the
+// expression of compact_rowptr_kernel).
+__global__ __launch_bounds__(256) void mxm_kept_list_kernel(const uint64_t *__restrict__ bits, const uint64_t *__restrict__ kpos, uint64_t nprod,
+                                                            const uint64_t *__restrict__ loff, uint32_t nlong, uint32_t *__restrict__ kept_pos,
+                                                            uint64_t *__restrict__ kloff) {
+    const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x < nprod) {
+        const uint64_t word = bits[x >> 6];
+        if ((word >> (x & 63)) & 1ull) kept_pos[kpos[x >> 6] + (uint64_t)__popcll(word & ((1ull << (x & 63)) - 1ull))] = (uint32_t)x;
+    }
+    if (x <= nlong) {
+        const uint64_t p = loff[x];
+        uint64_t o = kpos[p >> 6];
+        if (p & 63) o += (uint64_t)__popcll(bits[p >> 6] & ((1ull << (p & 63)) - 1ull));   // (p & 63 == 0: the word may not exist)
+        kloff[x] = o;
+    }
+}
+// the long rows of a batch in which no long row keeps a product: nothing is sorted, every count is 0
+__global__ __launch_bounds__(256) void mxm_long_empty_kernel(const uint32_t *__restrict__ long_rows, uint32_t nlong, uint32_t *__restrict__ cnt) {
+    const uint32_t h = blockIdx.x * blockDim.x + threadIdx.x;
+    if (h < nlong) cnt[long_rows[h]] = 0;
+}
+
 template <class V>
 __global__ __launch_bounds__(256) void mxm_sorted_values_kernel(const uint32_t *__restrict__ pos, const V *__restrict__ pval, uint64_t n,
                                                                 V *__restrict__ sorted_val) {

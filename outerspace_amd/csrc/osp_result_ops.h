@@ -714,18 +714,21 @@ static void ewise_impl(Context *ctx, const Result *a, const Result *b, Result *r
                 (unsigned long long)nnz_both, launches, st->ms_total);
 }
 
-// ---- the product of two CSR results under a semiring (osp_mxm.h) ----
+// ---- the product of two CSR results under a semiring, plain and at a mask (osp_mxm.h, DESIGN.md sections 15 and 27) ----
+// (mask.rowptr is null for the plain product)
 struct MxmOperands {
     const int64_t *a_rowptr; const uint32_t *a_col; const void *a_val;
     const int64_t *b_rowptr; const uint32_t *b_col; const void *b_val;
     const uint64_t *wscan;
+    MxmMask mask;
 };
 template <class T, int ADD>
 static void launch_mxm_short_add(const MxmOperands &op, hipStream_t s, uint64_t r0, uint64_t nrows, uint32_t cap, int mul, uint64_t p0, uint32_t *tcol,
                                  ValueBits<T> *tval, uint32_t *cnt) {
     typedef ValueBits<T> V;
-    mxm_short_kernel<T, ADD><<<(unsigned)nrows, kWave, 0, s>>>(op.a_rowptr, op.a_col, (const V *)op.a_val, op.b_rowptr, op.b_col, (const V *)op.b_val,
-                                                                op.wscan, r0, cap, mul, p0, tcol, tval, cnt);
+    const auto kernel = op.mask.rowptr ? mxm_short_kernel<T, ADD, true> : mxm_short_kernel<T, ADD, false>;
+    kernel<<<(unsigned)nrows, kWave, 0, s>>>(op.a_rowptr, op.a_col, (const V *)op.a_val, op.b_rowptr, op.b_col, (const V *)op.b_val, op.wscan, r0, cap,
+                                             mul, p0, tcol, tval, cnt, op.mask);
 }
 template <class T>
 static void launch_mxm_short(int add, const MxmOperands &op, hipStream_t s, uint64_t r0, uint64_t nrows, uint32_t cap, int mul, uint64_t p0,
@@ -737,14 +740,14 @@ static void launch_mxm_short(int add, const MxmOperands &op, hipStream_t s, uint
 }
 template <class T, int MUL = 0>
 static void launch_mxm_expand(int mul, const MxmOperands &op, hipStream_t s, const uint32_t *long_rows, const uint64_t *loff, uint32_t nlong,
-                              uint64_t nprod, int colbits, uint64_t *key, uint32_t *pos, ValueBits<T> *pval) {
+                              uint64_t nprod, int colbits, uint64_t *key, uint32_t *pos, ValueBits<T> *pval, const uint32_t *kept_pos) {
     typedef ValueBits<T> V;
     if constexpr (MUL <= EW_SECOND) {
-        if (mul == MUL)
-            mxm_expand_kernel<T, MUL><<<grid_for(nprod, 256), 256, 0, s>>>(op.a_rowptr, op.a_col, (const V *)op.a_val, op.b_rowptr, op.b_col,
-                                                                          (const V *)op.b_val, op.wscan, long_rows, loff, nlong, nprod, colbits, key,
-                                                                          pos, pval);
-        else launch_mxm_expand<T, MUL + 1>(mul, op, s, long_rows, loff, nlong, nprod, colbits, key, pos, pval);
+        if (mul == MUL) {
+            const auto kernel = kept_pos ? mxm_expand_kernel<T, MUL, true> : mxm_expand_kernel<T, MUL, false>;
+            kernel<<<grid_for(nprod, 256), 256, 0, s>>>(op.a_rowptr, op.a_col, (const V *)op.a_val, op.b_rowptr, op.b_col, (const V *)op.b_val, op.wscan,
+                                                        long_rows, loff, nlong, nprod, colbits, key, pos, pval, kept_pos);
+        } else launch_mxm_expand<T, MUL + 1>(mul, op, s, long_rows, loff, nlong, nprod, colbits, key, pos, pval, kept_pos);
     }
 }
 template <class T, int ADD>
@@ -754,8 +757,16 @@ static void launch_mxm_fold_add(const MxmOperands &op, hipStream_t s, const uint
     mxm_fold_kernel<T, ADD><<<grid_for(nprod, 256), 256, 0, s>>>(key, sorted_val, headscan, head_pos, nprod, op.a_rowptr, op.wscan, long_rows, loff,
                                                                  colbits, p0, tcol, tval);
 }
+// what a product counts, for the stats of either entry point
+struct MxmCounts {
+    uint64_t products = 0, kept = 0, nnz_out = 0, n_short = 0, n_long = 0;
+    uint32_t nb = 0, launches = 0;
+};
+// The product of both entry points: `mask` null is osp_csr_mxm, launch for launch; with a mask only the products it admits
+// (`complement`: rejects) are sorted and folded.  Fills res and its info and returns the counts; the caller writes its stats.
 template <class T>
-static void mxm_impl(Context *ctx, const Result *a, const Result *b, Result *res, const osp_semiring_t &sr, osp_mxm_stats_t *st) {
+static MxmCounts mxm_run(Context *ctx, const Result *a, const Result *b, const Result *mask, int complement, Result *res,
+                         const osp_semiring_t &sr) {
     typedef ValueBits<T> V;
     OpFrame fr(ctx);
     hipStream_t s = fr.s;
@@ -763,8 +774,11 @@ static void mxm_impl(Context *ctx, const Result *a, const Result *b, Result *res
     const uint64_t M = a->info.M, K = a->info.N, N = b->info.N, nnz_a = a->info.nnz_c, nnz_b = b->info.nnz_c;
     fresh_info(res, M, K, N);
     res->info.nnz_a = nnz_a; res->info.nnz_b = nnz_b;
-    uint64_t products = 0, nnz_out = 0, n_short = 0, n_long = 0;
+    uint64_t products = 0, nnz_out = 0, n_short = 0, n_long = 0, kept_long = 0;
     uint32_t nb = 0, launches = 0;
+    // (an empty mask that is not complemented admits nothing: the symbolic phase still counts, no numeric kernel runs)
+    const bool can_keep = !mask || complement || mask->info.nnz_c > 0;
+    unsigned long long *kept_short = nullptr;
 
     // ---- symbolic: the products of every entry of a, scanned ----
     uint64_t *wscan = nullptr;
@@ -781,7 +795,12 @@ static void mxm_impl(Context *ctx, const Result *a, const Result *b, Result *res
     } else {
         const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ctx->env.mxm_short_cap.or_(kMxmShortMax), 1), kMxmShortMax);
         const uint64_t budget = std::min<uint64_t>(std::max<uint64_t>(ctx->env.mxm_batch.or_(kMxmBatchDefault), 1), 0xfffffffeull);
-        const MxmOperands op{a->rowptr, a->colidx, a->vals, b->rowptr, b->colidx, b->vals, wscan};
+        if (mask) {
+            kept_short = (unsigned long long *)sc.get<uint64_t>(1);
+            zero_async(s, {{kept_short, sizeof(uint64_t)}});
+        }
+        const MxmOperands op{a->rowptr, a->colidx, a->vals, b->rowptr, b->colidx, b->vals, wscan,
+                             mask ? MxmMask{mask->rowptr, mask->colidx, complement, kept_short} : MxmMask{nullptr, nullptr, 0, nullptr}};
         // ---- the rows' classes and the batches ----
         // (two consecutive batches hold more than `budget` products between them, or the cut would not lie there)
         const uint32_t max_batches = (uint32_t)std::min<uint64_t>(M, 2 * (products / budget) + 3);
@@ -806,12 +825,12 @@ static void mxm_impl(Context *ctx, const Result *a, const Result *b, Result *res
         std::vector<uint64_t> cut((size_t)2 * (nb + 1));
         copy_d2h(cut.data(), cuts, cut.size() * sizeof(uint64_t), s);
 
-        alloc_rowptr(res, M);
+        if (can_keep) alloc_rowptr(res, M); else empty_result<T>(res, M, s);
         uint32_t *cnt = sc.get<uint32_t>(M + 1);
         const int colbits = bits_for(N);
         struct BatchOut { uint32_t *col; V *val; uint64_t nnz; };
         std::vector<BatchOut> outs;
-        for (uint32_t t = 0; t < nb; t++) {
+        for (uint32_t t = 0; t < nb && can_keep; t++) {
             const uint64_t r0 = cut[2 * t], p0 = cut[2 * t + 1], nrows = cut[2 * t + 2] - r0, pb = cut[2 * t + 3] - p0;
             Scratch sb(ctx);
             // a row's slot is its place in the batch's expansion: it holds at most as many entries as the row has products
@@ -832,19 +851,45 @@ static void mxm_impl(Context *ctx, const Result *a, const Result *b, Result *res
                     uint32_t *long_rows = sb.get<uint32_t>(nl);
                     uint64_t *loff = sb.get<uint64_t>(nl + 1);
                     mxm_long_list_kernel<<<grid_for(nrows + 1, 256), 256, 0, s>>>(flag, rank, lpscan, r0, nrows, long_rows, loff);
-                    SortedRuns runs(sb, pl);
-                    V *pval = sb.get<V>(pl), *sorted_val = sb.get<V>(pl);
-                    launch_mxm_expand<T>(sr.mul, op, s, long_rows, loff, (uint32_t)nl, pl, colbits, runs.keys[0], runs.poss[0], pval);
-                    launches += 2 + runs.sort(colbits + bits_for(nl));
-                    mxm_sorted_values_kernel<V><<<grid_for(pl, 256), 256, 0, s>>>(runs.poss[runs.cur], pval, pl, sorted_val);
-                    launches += 1 + runs.heads();
-                    const uint64_t *key = runs.keys[runs.cur], *headscan = runs.headscan, *head_pos = runs.head_pos();
-                    if (sr.add == EW_PLUS) launch_mxm_fold_add<T, EW_PLUS>(op, s, key, sorted_val, headscan, head_pos, pl, long_rows, loff, colbits, p0, tcol, tval);
-                    else if (sr.add == EW_MIN) launch_mxm_fold_add<T, EW_MIN>(op, s, key, sorted_val, headscan, head_pos, pl, long_rows, loff, colbits, p0, tcol, tval);
-                    else if (sr.add == EW_MAX) launch_mxm_fold_add<T, EW_MAX>(op, s, key, sorted_val, headscan, head_pos, pl, long_rows, loff, colbits, p0, tcol, tval);
-                    else launch_mxm_fold_add<T, EW_FIRST>(op, s, key, sorted_val, headscan, head_pos, pl, long_rows, loff, colbits, p0, tcol, tval);
-                    mxm_long_counts_kernel<<<grid_for(nl, 256), 256, 0, s>>>(long_rows, loff, (uint32_t)nl, headscan, cnt);
-                    launches += 2;   // (the list of run heads is counted by heads())
+                    launches++;
+                    // with a mask: a verdict per formed product, ONE scan and ONE read-back; from here on pl counts the KEPT
+                    // products, koff holds the long rows' kept offsets, and loff stays what decodes a formed position
+                    const uint64_t *koff = loff;
+                    const uint32_t *kept_pos = nullptr;
+                    if (mask) {
+                        const uint64_t formed = pl, nwords = (formed + 63) / 64;
+                        uint64_t *bits = sb.get<uint64_t>(nwords), *kpos = sb.get<uint64_t>(nwords + 1);
+                        uint64_t *ktmp = sb.get<uint64_t>(scan_scratch_entries(nwords));
+                        mxm_mask_flag_kernel<<<grid_for(formed, 256), 256, 0, s>>>(a->rowptr, a->colidx, b->rowptr, b->colidx, wscan, long_rows, loff,
+                                                                                   (uint32_t)nl, formed, op.mask, bits);
+                        launches += 1 + device_exclusive_scan<LoadPopc64, uint64_t>(LoadPopc64{bits}, nwords, kpos, ktmp, s);
+                        pl = d2h((const uint64_t *)kpos + nwords, s);
+                        uint32_t *list = sb.get<uint32_t>(std::max<uint64_t>(pl, 1));
+                        uint64_t *kloff = sb.get<uint64_t>(nl + 1);
+                        mxm_kept_list_kernel<<<grid_for(std::max(formed, nl + 1), 256), 256, 0, s>>>(bits, kpos, formed, loff, (uint32_t)nl, list, kloff);
+                        launches++;
+                        kept_long += pl;
+                        koff = kloff;
+                        kept_pos = list;
+                    }
+                    if (pl == 0) {   // (with a mask only) no long row of the batch keeps a product: no sort at all
+                        mxm_long_empty_kernel<<<grid_for(nl, 256), 256, 0, s>>>(long_rows, (uint32_t)nl, cnt);
+                        launches++;
+                    } else {
+                        SortedRuns runs(sb, pl);
+                        V *pval = sb.get<V>(pl), *sorted_val = sb.get<V>(pl);
+                        launch_mxm_expand<T>(sr.mul, op, s, long_rows, loff, (uint32_t)nl, pl, colbits, runs.keys[0], runs.poss[0], pval, kept_pos);
+                        launches += 1 + runs.sort(colbits + bits_for(nl));
+                        mxm_sorted_values_kernel<V><<<grid_for(pl, 256), 256, 0, s>>>(runs.poss[runs.cur], pval, pl, sorted_val);
+                        launches += 1 + runs.heads();
+                        const uint64_t *key = runs.keys[runs.cur], *headscan = runs.headscan, *head_pos = runs.head_pos();
+                        if (sr.add == EW_PLUS) launch_mxm_fold_add<T, EW_PLUS>(op, s, key, sorted_val, headscan, head_pos, pl, long_rows, koff, colbits, p0, tcol, tval);
+                        else if (sr.add == EW_MIN) launch_mxm_fold_add<T, EW_MIN>(op, s, key, sorted_val, headscan, head_pos, pl, long_rows, koff, colbits, p0, tcol, tval);
+                        else if (sr.add == EW_MAX) launch_mxm_fold_add<T, EW_MAX>(op, s, key, sorted_val, headscan, head_pos, pl, long_rows, koff, colbits, p0, tcol, tval);
+                        else launch_mxm_fold_add<T, EW_FIRST>(op, s, key, sorted_val, headscan, head_pos, pl, long_rows, koff, colbits, p0, tcol, tval);
+                        mxm_long_counts_kernel<<<grid_for(nl, 256), 256, 0, s>>>(long_rows, koff, (uint32_t)nl, headscan, cnt);
+                        launches += 2;   // (the list of run heads is counted by heads())
+                    }
                 }
             }
             // the batch's output at its exact size: the scan of its rows' counts, ONE read-back, the slots' entries gathered
@@ -869,7 +914,7 @@ static void mxm_impl(Context *ctx, const Result *a, const Result *b, Result *res
             nnz_out += nnz_b_out;
             OSP_HIP(hipStreamSynchronize(s));   // (sb goes back to the pool)
         }
-        if (nb > 1) {
+        if (nb > 1 && can_keep) {   // (nothing can be kept: empty_result made the whole result, no row has a count)
             // the result is the batches' outputs one after another, its row pointer the scan of all rows' counts
             uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(M + 1));
             launches += device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{cnt}, M, (uint64_t *)res->rowptr, tmp, s);
@@ -883,23 +928,61 @@ static void mxm_impl(Context *ctx, const Result *a, const Result *b, Result *res
             }
         }
     }
+    MxmCounts c;
+    if (kept_short) c.kept = (uint64_t)d2h((const uint64_t *)kept_short, s) + kept_long;
     fr.finish(res, nnz_out);
     res->info.partials = products;
+    c.products = products;
+    c.nnz_out = nnz_out;
+    c.n_short = n_short;
+    c.n_long = n_long;
+    c.nb = nb;
+    c.launches = launches;
+    return c;
+}
+template <class T>
+static void mxm_impl(Context *ctx, const Result *a, const Result *b, Result *res, const osp_semiring_t &sr, osp_mxm_stats_t *st) {
+    const MxmCounts c = mxm_run<T>(ctx, a, b, nullptr, 0, res, sr);
+    const uint64_t M = a->info.M, K = a->info.N, N = b->info.N, nnz_a = a->info.nnz_c, nnz_b = b->info.nnz_c;
     *st = osp_mxm_stats_t{};
     st->nnz_a = nnz_a;
     st->nnz_b = nnz_b;
-    st->products = products;
-    st->nnz_out = nnz_out;
-    st->short_rows = n_short;
-    st->long_rows = n_long;
-    st->batches = nb;
-    st->launches = launches;
+    st->products = c.products;
+    st->nnz_out = c.nnz_out;
+    st->short_rows = c.n_short;
+    st->long_rows = c.n_long;
+    st->batches = c.nb;
+    st->launches = c.launches;
     st->ms_total = res->info.ms_total;
     if (ctx->env.verbose)
         fprintf(stderr, "[osp] mxm add=%d mul=%d M=%llu K=%llu N=%llu nnz %llu , %llu -> %llu products=%llu short=%llu long=%llu batches=%u launches=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
                 sr.add, sr.mul, (unsigned long long)M, (unsigned long long)K, (unsigned long long)N, (unsigned long long)nnz_a,
-                (unsigned long long)nnz_b, (unsigned long long)nnz_out, (unsigned long long)products, (unsigned long long)n_short,
-                (unsigned long long)n_long, nb, launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
+                (unsigned long long)nnz_b, (unsigned long long)c.nnz_out, (unsigned long long)c.products, (unsigned long long)c.n_short,
+                (unsigned long long)c.n_long, c.nb, c.launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
+}
+// the same product at a mask (include/outerspace_spgemm_mxm_masked.h)
+template <class T>
+static void mxm_masked_impl(Context *ctx, const Result *a, const Result *b, const Result *mask, int complement, Result *res,
+                            const osp_semiring_t &sr, osp_mxm_masked_stats_t *st) {
+    const MxmCounts c = mxm_run<T>(ctx, a, b, mask, complement ? 1 : 0, res, sr);
+    *st = osp_mxm_masked_stats_t{};
+    st->nnz_a = a->info.nnz_c;
+    st->nnz_b = b->info.nnz_c;
+    st->nnz_mask = mask->info.nnz_c;
+    st->products = c.products;
+    st->products_kept = c.kept;
+    st->nnz_out = c.nnz_out;
+    st->short_rows = c.n_short;
+    st->long_rows = c.n_long;
+    st->batches = c.nb;
+    st->launches = c.launches;
+    st->ms_total = res->info.ms_total;
+    if (ctx->env.verbose)
+        fprintf(stderr, "[osp] mxm_masked add=%d mul=%d complement=%d M=%llu K=%llu N=%llu nnz %llu , %llu mask %llu -> %llu products=%llu kept=%llu short=%llu long=%llu batches=%u launches=%u %.3f ms\n",
+                sr.add, sr.mul, complement ? 1 : 0, (unsigned long long)a->info.M, (unsigned long long)a->info.N, (unsigned long long)b->info.N,
+                (unsigned long long)st->nnz_a, (unsigned long long)st->nnz_b, (unsigned long long)st->nnz_mask, (unsigned long long)c.nnz_out,
+                (unsigned long long)c.products, (unsigned long long)c.kept, (unsigned long long)c.n_short, (unsigned long long)c.n_long, c.nb,
+                c.launches, st->ms_total);
 }
 
 // ---- the transpose of a CSR result (osp_transpose.h) ----

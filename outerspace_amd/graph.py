@@ -16,7 +16,8 @@ feature propagation on the product of a result with a dense matrix ``osp_csr_mxd
 ``propagate_features``), and edge scores, landmark distance bounds and a factorisation of the observed entries on the sampled
 dense-dense product ``osp_csr_sddmm`` (``edge_scores``, ``landmark_bounds``, ``factorize``), and a minimum spanning forest
 and a greedy weighted matching on mxv with the winner's column ``osp_csr_mxv_arg`` (``minimum_spanning_forest``,
-``greedy_matching``, at the end).
+``greedy_matching``), and BFS parent trees on the semiring product of two results AT a mask ``osp_csr_mxm_masked``
+(``bfs_parents``, at the end): the first traversal here that never forms the part of a product it would throw away.
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -1897,3 +1898,76 @@ def greedy_matching(rows, cols, n=None, weights=None, *, dtype=np.float64, ctx=N
         _close_all(device, (W, Wf))   # (closing twice is closing once)
     info["pairs"] = int((mate >= 0).sum()) // 2
     return mate, info
+
+
+# ---- the semiring product at a mask (osp_csr_mxm_masked): BFS parent trees -------------------------------------
+def bfs_parents(rows, cols, n=None, sources=(0,), *, directed=False, max_levels=None, ctx=None):
+    """The breadth-first parent tree of every vertex of ``sources`` at once on the graph with edges (rows[e], cols[e]) on
+    vertices [0, n) (duplicates allowed; ``directed=False``: any direction, self loops dropped; ``directed=True``: an edge
+    leads from rows[e] to cols[e]), every level on the GPU.  With A the 0/1 adjacency, the frontier F and the parents found
+    so far P as S x n CSR results (one row per source), a level is
+
+        Nx = F.mxm(A, "min", "first", mask=P, complement=True)     next<NOT parents> = frontier (min.first) A
+        P  = P.ewise(Nx, "union", "first")                         (the patterns are disjoint)
+        F  = Nx.apply_vectors(col_op="second", cols=arange(n))     an entry at (s, k) carries the value k
+
+    so an entry of Nx at (s, v) is the smallest vertex id among v's neighbours on the previous level -- v's parent -- and a
+    product that lands on a vertex already reached is dropped where it is formed: it is never sorted, folded or written.
+    Ids are exact in float64.  The levels end when Nx is empty or ``max_levels`` levels were taken.
+
+    Returns (parent int64 [len(sources), n], level int32 of the same shape, info): ``parent[s, source] = source`` and
+    ``level[s, source] = 0``; an unreached vertex has parent -1 and level -1.  ``info`` = levels (the deepest level reached)
+    and per product the lists frontier_nnz, products (formed), products_kept, nnz_new and ms_mxm (device time).  Duplicate
+    sources are independent rows; a source out of range is a ValueError.  rows / cols: torch tensors (any device; the
+    plumbing runs on cuda:ctx.device) or array-likes."""
+    from .sparse_util import _result_as_input
+    ctx, device, _, n, A = _pattern_result(rows, cols, n, directed, np.float64, ctx)
+    F = P = None
+    try:
+        src = _check_sources(sources, n)
+        S = int(src.size)
+        parent = torch.full((S, n), -1, dtype=torch.int64, device=device)
+        level = torch.full((S, n), -1, dtype=torch.int32, device=device)
+        info = {"levels": 0, "frontier_nnz": [], "products": [], "products_kept": [], "nnz_new": [], "ms_mxm": []}
+        if S and n:
+            s_dev = torch.as_tensor(src, device=device)
+            lin0 = torch.arange(S, dtype=torch.int64, device=device) * n + s_dev
+            parent.view(-1)[lin0] = s_dev
+            level.view(-1)[lin0] = 0
+        if S and n and A is not None:
+            rp0 = torch.arange(S + 1, dtype=torch.int64, device=device)
+            c0, v0 = s_dev.to(torch.int32), s_dev.to(torch.float64)
+            ids = torch.arange(n, dtype=torch.float64, device=device)
+            torch.cuda.synchronize(device)   # the library works on its own stream
+            F = _csr_result(ctx, np.float64, S, n, rp0, c0, v0, device, sync=False)
+            P = _csr_result(ctx, np.float64, S, n, rp0, c0, v0, device, sync=False)
+            d = 0
+            while max_levels is None or d < max_levels:
+                d += 1
+                Nx, st = F.mxm(A, "min", "first", mask=P, complement=True)
+                try:
+                    info["frontier_nnz"].append(F.nnz)
+                    info["products"].append(st["products"])
+                    info["products_kept"].append(st["products_kept"])
+                    info["nnz_new"].append(Nx.nnz)
+                    info["ms_mxm"].append(st["ms_total"])
+                    if Nx.nnz == 0:
+                        break
+                    info["levels"] = d
+                    a = _result_as_input(Nx, device)
+                    lin = a.rows.to(torch.int64)[:a.nnz] * n + a.cols.to(torch.int64)
+                    parent.view(-1)[lin] = a.vals.to(torch.int64)
+                    level.view(-1)[lin] = d
+                    torch.cuda.synchronize(device)   # torch holds views of Nx's arrays: nothing of it is in flight when it is closed
+                    del a
+                    U, _ = P.ewise(Nx, "union", "first")
+                    P.close()
+                    P = U
+                    Fn, _ = Nx.apply_vectors(col_op="second", cols=ids)
+                    F.close()
+                    F = Fn
+                finally:
+                    Nx.close()
+        return parent.cpu().numpy(), level.cpu().numpy(), info
+    finally:
+        _close_all(device, (A, F, P))

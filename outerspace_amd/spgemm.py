@@ -285,7 +285,7 @@ class CsrResult:
         """``ewise(other, "intersect", op)``: ``op`` on the common pattern."""
         return self.ewise(other, "intersect", op)
 
-    def mxm(self, other, add="plus", mul="times"):
+    def mxm(self, other, add="plus", mul="times", *, mask=None, complement=False):
         """This CSR (M x K) times ``other`` (K x N) under the semiring ``(add, mul)`` as a new M x N CSR result on the device
         (``osp_csr_mxm``): a row-wise product of two results, nothing is ingested or transposed.  An output entry (i, j)
         exists when some k has a stored ``self[i, k]`` and a stored ``other[k, j]``; its value is the products
@@ -294,11 +294,32 @@ class CsrResult:
         operation each, as ``ewise`` defines them.  ``("plus", "times")`` equals ``spgemm_coo_device`` of the same operands
         bit for bit; ``("min", "plus")`` relaxes a frontier of distances.  ``other`` is a ``CsrResult`` of the same context and
         dtype (``self`` itself is allowed).  Returns (result, stats dict): nnz_a, nnz_b, products, nnz_out, short_rows,
-        long_rows, batches, launches, ms_total."""
+        long_rows, batches, launches, ms_total.
+
+        ``mask`` (a ``CsrResult`` of shape (M, N) on the same context; only its pattern is read, its dtype is free; ``self``
+        and ``other`` are allowed) computes the product AT the mask (``osp_csr_mxm_masked``): the entries whose coordinate the
+        mask holds, or with ``complement=True`` does not hold -- the same three arrays, bit for bit, as
+        ``self.mxm(other, add, mul)[0].apply_mask(mask, complement=complement)``, but a product the mask rejects is dropped
+        where it is formed and is neither sorted, folded nor written.  The stats dict is then nnz_a, nnz_b, nnz_mask,
+        products (formed), products_kept, nnz_out, short_rows, long_rows, batches, launches, ms_total.
+        ``complement=True`` without a mask is a ValueError.  When it pays (MEASUREMENTS.md section 0w, MI355X, 64-source BFS
+        on R-MAT scale 16 and 19): the fused call costs a bisection per formed product and saves the sort, the fold and the
+        write of every rejected one.  With a third of the products kept it takes 0.14 to 0.24 of the two calls' time, with
+        a few per cent kept 0.06 to 0.27, ``(A A)<A>`` (nearly all rows long, 4 to 8 % kept) 0.52; the break-even is
+        "nearly everything kept" (0.99 kept: 0.92 to 0.98, level within the spread), and no measured case was slower."""
         sr = _lib.Semiring()
         sr.add, sr.mul = _enum(_lib.MXM_ADD_OPS, add, "add"), _enum(_lib.MXM_MUL_OPS, mul, "mul")
+        if mask is None and complement:
+            raise ValueError("complement=True needs a mask")
         self._same_family(other)
-        return _call(self._ctx, "osp_csr_mxm", self._h, other._h, C.byref(sr), stats=_lib.MxmStats())
+        if mask is None:
+            return _call(self._ctx, "osp_csr_mxm", self._h, other._h, C.byref(sr), stats=_lib.MxmStats())
+        if not isinstance(mask, CsrResult):
+            raise TypeError("mask must be a CsrResult")
+        if mask._ctx is not self._ctx:
+            raise OspError(_lib.ERR_ARG, "the mask belongs to a different context")
+        return _call(self._ctx, "osp_csr_mxm_masked", self._h, other._h, mask._h, int(bool(complement)), C.byref(sr),
+                     stats=_lib.MxmMaskedStats())
 
     def transpose(self):
         """This CSR (M x N) transposed as a new N x M CSR result on the device (``osp_csr_transpose``): entry (j, i) exists
