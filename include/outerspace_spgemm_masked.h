@@ -31,7 +31,10 @@ extern "C" {
  * it a violation indexes out of bounds on the device.  k_begin / k_end must be 0 / 0 and row_shard_count <= 1, anything
  * else is OSP_ERR_ARG.  partial_capacity and algorithm are ignored.
  * Limits: nnzA, nnzB and nnzM must each be below 2^32 (OSP_ERR_ARG).  A null m_rowptr, or a null m_colidx with nnzM > 0,
- * is OSP_ERR_ARG.  On any error *result is left as it was.
+ * is OSP_ERR_ARG.  M, K and N must each be below 2^32 - 256 (osp_spgemm_csc_csr takes N up to 2^32 - 1), or the call is
+ * refused with OSP_ERR_ARG before anything is launched or allocated: the call makes a column view of B with N + 1 offsets (and
+ * a row view of A with M + 1), one thread each in blocks of 256, and a launch takes fewer than 2^32 threads.  Its device footprint is therefore 8 (N + 1) bytes beside
+ * the operands', whatever they hold (16 GiB at N = 2^31).  On any error *result is left as it was.
  *
  * The result is an ordinary osp_result_t: osp_result_copy_csr, _device_ptrs, _info, _write_mtx, _coo_rows,
  * osp_csr_bias_relu and osp_result_destroy all take it.  osp_result_info fills these fields of osp_result_info_t:

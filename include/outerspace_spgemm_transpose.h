@@ -51,7 +51,9 @@ typedef struct osp_transpose_stats {
  * value separately, where the default packs (row, value) records before the sort and fetches one record per entry.
  *
  * OSP_ERR_ARG: a null in or out; a non-zero reserved word; a result of osp_spgemm_partials; an in of 2^32 - 1 entries or
- * more (the sort's positions are 32 bits).  OSP_ERR_DIM: in's M above 2^32 (a row index must fit a column).  On any error
+ * more (the sort's positions are 32 bits); a non-empty in whose N is 2^32 - 256 or more (out's N + 1 row pointers are
+ * written by one thread each in blocks of 256, and a launch takes fewer than 2^32 threads; refused before anything is launched
+ * or allocated -- out's row pointers alone are 8 (N + 1) bytes).  OSP_ERR_DIM: in's M above 2^32 (a row index must fit a column).  On any error
  * *out and *stats are left as they were.  An in without entries (M == 0 and N == 0 included) is legal, launches nothing and
  * gives an empty N x M result.
  *

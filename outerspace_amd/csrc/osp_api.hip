@@ -870,6 +870,11 @@ int osp_spgemm_masked(osp_context_t ctx_, osp_dtype_t dtype, uint64_t M, uint64_
         const osp_config_t cfg = config_or_default(cfg_);
         if (cfg.k_begin != 0 || cfg.k_end != 0) throw Error(OSP_ERR_ARG, "masked product: k_begin / k_end must be 0 / 0");
         if (cfg.row_shard_count > 1) throw Error(OSP_ERR_ARG, "masked product: row shards are not supported");
+        // B's column view holds N + 1 offsets and A's row view M + 1, made by one thread per offset (ingest_ptr_kernel), and the
+        // validation takes a thread per pointer of K + 1: beyond kThreadEachMax the launch is refused by the runtime (the call used
+        // to fail there with a HIP error, after its first launches)
+        if (std::max(std::max(M, K), N) + 1 > kThreadEachMax)
+            throw Error(OSP_ERR_ARG, "masked product: M, K and N must be below 2^32 - 256 (the views take a thread per offset, N + 1 for B's)");
         return new_result(ctx, dtype, result, [&](auto tag, Result *res) {
             using T = decltype(tag);
             masked_impl<T>(ctx, res, M, K, N, a_colptr, a_rowidx, (const T *)a_vals, b_rowptr, b_colidx, (const T *)b_vals, m_rowptr,
@@ -950,6 +955,9 @@ int osp_csr_transpose(osp_result_t in_, const osp_transpose_t *tp, osp_result_t 
         if (tp) check_reserved(tp->reserved, "transpose");
         if (in->info.nnz_c >= 0xffffffffull) throw Error(OSP_ERR_ARG, "transpose: an operand with >= 2^32 - 1 non-zeros is not supported");
         if (in->info.M > (1ull << 32)) throw Error(OSP_ERR_DIM, "transpose: a row index of in must fit a column of out");
+        // out's N + 1 row pointers are written by one thread each (ingest_ptr_kernel)
+        if (in->info.nnz_c && in->info.N + 1 > kThreadEachMax)
+            throw Error(OSP_ERR_ARG, "transpose: a non-empty in must have N below 2^32 - 256 (out's N + 1 row pointers take one thread each)");
     }, [&](auto tag, Result *res, osp_transpose_stats_t *st) { transpose_impl<decltype(tag)>(in->ctx, in, res, st); });
 }
 

@@ -341,6 +341,9 @@ static inline void dbg_sync(hipStream_t s, const char *what) {
     fflush(stderr);
 }
 static inline unsigned grid_for(uint64_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
+// The most items a kernel that takes ONE THREAD EACH in blocks of 256 can be launched for: a launch of 2^32 threads and more
+// is refused ("invalid configuration argument"), and grid_for rounds up to whole blocks, so 2^24 - 1 blocks are the most.
+constexpr uint64_t kThreadEachMax = ((1ull << 24) - 1) * 256;   // 2^32 - 256
 static inline int bits_for(uint64_t n) {  // bits needed to represent values in [0, n)
     int b = 0;
     while (b < 64 && (n > (1ull << b))) b++;

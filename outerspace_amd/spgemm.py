@@ -325,7 +325,8 @@ class CsrResult:
         """This CSR (M x N) transposed as a new N x M CSR result on the device (``osp_csr_transpose``): entry (j, i) exists
         iff this result has (i, j), columns ascend in every row, values keep their bits, and transposing twice gives the same
         three arrays back.  A result of at most 64 rows takes the row-mask path (nothing is sorted), everything else a
-        stable radix sort by column.  Returns (result, stats dict): nnz, path (0 nothing launched, 1 row mask, 2 sort),
+        stable radix sort by column.  A non-empty result of 2^32 - 256 columns and more is ``OspError(ERR_ARG)``: the new N + 1 row
+        pointers take a thread each.  Returns (result, stats dict): nnz, path (0 nothing launched, 1 row mask, 2 sort),
         passes, launches, ms_total."""
         return _call(self._ctx, "osp_csr_transpose", self._h, None, stats=_lib.TransposeStats())
 
@@ -786,7 +787,8 @@ class Context:
     def spgemm_masked(self, M, K, N, a_colptr, a_rowidx, a_vals, b_rowptr, b_colidx, b_vals, m_rowptr, m_colidx, *, validate=True):
         """C<mask> = A(CSC) * B(CSR) with numpy (host) operands (``osp_spgemm_masked``): the entries of the product at the
         mask's pattern (M x N, CSR, no values) where at least one product exists, the same bits as the unmasked product
-        there.  ``result.info['partials']`` is the number of products formed."""
+        there.  ``result.info['partials']`` is the number of products formed.  The call holds N + 1 offsets of B's column
+        view on the device, and M, K or N of 2^32 - 256 and more is ``OspError(ERR_ARG)``."""
         dt, arrs = _csc_csr_arrays(K, a_colptr, a_rowidx, a_vals, b_rowptr, b_colidx, b_vals)
         mr, mc = np.ascontiguousarray(m_rowptr, np.int64), np.ascontiguousarray(m_colidx, np.uint32)
         if len(mr) != M + 1:
