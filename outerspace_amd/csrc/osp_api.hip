@@ -17,6 +17,7 @@
 #include <limits>
 #include <map>
 #include <memory>
+#include <optional>   // (osp_pipeline.h, included inside namespace osp below, cannot include it itself)
 #include <string>
 #include <vector>
 
@@ -37,6 +38,7 @@
 #include "../../include/outerspace_spgemm_extract.h"
 #include "../../include/outerspace_spgemm_build.h"
 #include "osp_internal.h"
+#include "osp_paths.h"
 #include "osp_kernels.h"
 #include "osp_split.h"
 #include "osp_sort.h"
@@ -118,6 +120,204 @@ __global__ void count_partials_kernel(const int64_t *a_colptr, const int64_t *b_
     if (threadIdx.x == 0 && total) atomicAdd(out, (unsigned long long)total);
 }
 
+// ---- compressed operands on their way in --------------------------------------------------------------
+// One compressed operand (CSC: A's columns; CSR: B's or a mask's rows): the caller's arrays, which the ingest replaces by
+// their copies on the device.
+struct CompressedIn {
+    const int64_t *ptr; const uint32_t *idx; const void *val;
+    size_t vbytes;             // bytes of a value (0: a pattern, no values)
+    uint64_t nseg, bound;      // segments, and the dimension its indices lie in
+    const char *what;          // its name in messages
+    int64_t nnz = 0;
+    const int64_t *ptr_host = nullptr;   // the caller's pointer array where it lives on the host
+};
+// Pointer arrays first: nnz comes from their last entries ...
+template <size_t n>
+static void operand_ptrs_in(Scratch &sc, hipStream_t s, osp_memspace_t space, CompressedIn (&ops)[n]) {
+    for (CompressedIn &o : ops) {
+        if (space == OSP_HOST) { o.ptr_host = o.ptr; o.nnz = o.ptr[o.nseg]; }
+        o.ptr = to_device(sc, o.ptr, o.nseg + 1, space, s);
+    }
+}
+// ... in one gathered read-back, to which `also` adds a word of the caller's; then the refusals, in the caller's words.
+template <size_t n>
+static void operand_nnz(hipStream_t s, osp_memspace_t space, CompressedIn (&ops)[n], const char *negative, const char *too_many,
+                        uint64_t *also = nullptr, const uint64_t *also_dev = nullptr) {
+    Gather g(s);
+    if (space != OSP_HOST) for (CompressedIn &o : ops) g.add(&o.nnz, o.ptr + o.nseg);
+    if (also) g.add(also, also_dev);
+    g.wait();
+    for (const CompressedIn &o : ops) if (o.nnz < 0) throw Error(OSP_ERR_ARG, negative);
+    for (const CompressedIn &o : ops) if ((uint64_t)o.nnz >= 0xffffffffull) throw Error(OSP_ERR_ARG, too_many);
+}
+static void operand_entries_in(Scratch &sc, hipStream_t s, osp_memspace_t space, CompressedIn &o) {
+    o.idx = to_device(sc, o.idx, (uint64_t)o.nnz, space, s);
+    o.val = to_device(sc, (const char *)o.val, (uint64_t)o.nnz * o.vbytes, space, s);
+}
+// Operands on the device: pointers before indices (the index check walks the segments the pointer arrays describe), each
+// pass ending in one gathered read-back of the operands' flags.  pointers = false: the index pass alone.
+template <size_t n>
+static void validate_operands(Scratch &sc, hipStream_t s, const CompressedIn (&ops)[n], bool pointers = true) {
+    uint32_t *flags = sc.get<uint32_t>(n);
+    OSP_HIP(hipMemsetAsync(flags, 0, n * sizeof(uint32_t), s));
+    for (int pass = pointers ? 0 : 1; pass < 2; pass++) {
+        for (size_t q = 0; q < n; q++) {
+            const CompressedIn &o = ops[q];
+            if (pass == 0) validate_ptr_kernel<<<grid_for(o.nseg + 1, 256), 256, 0, s>>>(o.ptr, o.nseg, o.nnz, flags + q);
+            else if (o.nnz) validate_idx_kernel<<<grid_for(o.nnz, 256), 256, 0, s>>>(o.ptr, o.idx, o.nseg, o.nnz, o.bound, flags + q);
+        }
+        uint32_t f[n] = {};
+        { Gather g(s); for (size_t q = 0; q < n; q++) g.add(&f[q], (const uint32_t *)flags + q); g.wait(); }
+        for (size_t q = 0; q < n; q++) check_flags(f[q], ops[q].what);
+    }
+}
+
+// ---- the stages of a product ---------------------------------------------------
+// Stage 2: the k shard of the operands A and B (already on the device), then the row shard.
+template <class T>
+static Shard<T> shard_of(Context *ctx, Scratch &sc, PhaseTimer &tm, const osp_config_t &cfg, uint64_t M, const CompressedIn &A, const CompressedIn &B) {
+    hipStream_t s = ctx->stream;
+    const uint64_t K = A.nseg;
+    Shard<T> sh{A.ptr, A.idx, (const T *)A.val, B.ptr, B.idx, (const T *)B.val, K, (uint64_t)B.nnz, cfg.k_begin, cfg.k_end ? cfg.k_end : K, 0, 0, 0, M};
+    if (ctx->env.verbose)
+        fprintf(stderr, "[osp] spgemm M=%llu K=%llu N=%llu nnzA=%lld nnzB=%lld k=[%llu,%llu) %s operands\n", (unsigned long long)M,
+                (unsigned long long)K, (unsigned long long)B.bound, (long long)A.nnz, (long long)B.nnz, (unsigned long long)sh.k0,
+                (unsigned long long)sh.k1, A.ptr_host ? "host" : "device");
+    if (sh.k0 > sh.k1 || sh.k1 > K) throw Error(OSP_ERR_ARG, "k range outside [0,K]");
+    int64_t e1 = A.nnz;
+    if (sh.k0 != 0 || sh.k1 != K) {
+        if (A.ptr_host) { sh.e0 = A.ptr_host[sh.k0]; e1 = A.ptr_host[sh.k1]; }
+        else { Gather g(s); g.add(&sh.e0, A.ptr + sh.k0); g.add(&e1, A.ptr + sh.k1); g.wait(); }
+    }
+    sh.nnz = (uint64_t)(e1 - sh.e0);
+    if (cfg.row_shard_count > 1) {
+        // The row shard: this rank's rows, and A without the rest -- same K columns, absolute row ids -- BEFORE the symbolic
+        // phase (a rank then sorts 1/G of A's non-zeros instead of all of them; every rank derives the same bounds from the
+        // replicated operands alone: no collective)
+        const uint64_t nnz = sh.nnz;  // all of the k shard's non-zeros: the pre-pass sees every row
+        if (cfg.row_shard_index < 0 || cfg.row_shard_index >= cfg.row_shard_count) throw Error(OSP_ERR_ARG, "row shard index out of range");
+        const uint32_t G = (uint32_t)cfg.row_shard_count;
+        tm.begin(PH_SYM);
+        {
+            Scratch cs(ctx);
+            unsigned long long *work = (unsigned long long *)cs.get<uint64_t>(M + 1);
+            uint64_t *pre = cs.get<uint64_t>(M + 1), *cost_pre = cs.get<uint64_t>(M + 1);
+            uint64_t *tmp = cs.get<uint64_t>(scan_scratch_entries(M + 1));
+            uint64_t *d_b = cs.get<uint64_t>(2ull * (G + 1));
+            OSP_HIP(hipMemsetAsync(work, 0, (M + 1) * sizeof(uint64_t), s));
+            // every 16th column is sample enough to balance G shards of a large matrix; small ones are counted exactly
+            const uint32_t stride = (sh.k1 - sh.k0) >= (1u << 16) ? 16u : 1u;
+            const uint64_t nsample = (sh.k1 - sh.k0 + stride - 1) / stride;
+            if (nnz) row_work_kernel<<<grid_for(nsample * kWave, 256), 256, 0, s>>>(sh.a_colptr, sh.a_rowidx, sh.b_rowptr, sh.k0, sh.k1, stride, work);
+            device_exclusive_scan<LoadU64, uint64_t>(LoadU64{(const uint64_t *)work}, M, pre, tmp, s);
+            device_exclusive_scan<RowCost, uint64_t>(RowCost{pre, (uint64_t)TileCap<T>::value, kSplitRowMax}, M, cost_pre, tmp, s);
+            shard_bounds_kernel<<<grid_for(G + 1, 64), 64, 0, s>>>(cost_pre, pre, M, G, d_b, d_b + G + 1);
+            std::vector<uint64_t> h_b(2ull * (G + 1));
+            copy_d2h(h_b.data(), d_b, h_b.size() * sizeof(uint64_t), s);
+            sh.r_lo = h_b[cfg.row_shard_index];
+            sh.r_hi = h_b[cfg.row_shard_index + 1];
+        }
+        int64_t *colptr2 = sc.get<int64_t>(K + 1);
+        {
+            Scratch cs(ctx);
+            uint32_t *keep_scan = cs.get<uint32_t>(nnz + 1);
+            uint32_t *tmp = cs.get<uint32_t>(scan_scratch_entries(nnz + 1));
+            const RowInRange keep{sh.a_rowidx + sh.e0, (uint32_t)sh.r_lo, sh.r_hi};
+            device_exclusive_scan<RowInRange, uint32_t>(keep, nnz, keep_scan, tmp, s);
+            const uint64_t nnz2 = d2h(keep_scan + nnz, s);
+            uint32_t *rowidx2 = sc.get<uint32_t>(nnz2);
+            T *vals2 = sc.get<T>(nnz2);
+            restrict_colptr_kernel<<<grid_for(K + 1, 256), 256, 0, s>>>(sh.a_colptr, K, sh.e0, nnz, keep_scan, colptr2);
+            if (nnz2) restrict_compact_kernel<T><<<grid_for(nnz, 256), 256, 0, s>>>(keep, keep_scan, nnz, sh.a_vals + sh.e0, rowidx2, vals2);
+            sh.a_colptr = colptr2; sh.a_rowidx = rowidx2; sh.a_vals = vals2;
+            sh.e0 = 0;  // columns before k0 are empty now
+            sh.nnz = nnz2;
+        }
+        tm.end(PH_SYM);
+    }
+    return sh;
+}
+
+// Stage 3's result: every row's offset into the staging, every chunk's (chunk = a non-zero of A times its row of B), and
+// what the chosen formulations read of the chunk table.  Everything lives in the product's scratch.
+template <class T> struct Symbolic {
+    uint64_t *row_off = nullptr, *chunk_off = nullptr;
+    uint64_t P = 0;                // partial products of the shard, or kPartialsOnDevice
+    ChunkTable<T> ct{};            // row-wise variant
+    uint32_t n_long_rows = 1;      // ... and how many rows it leaves to the multiply
+    DirectSrc dsrc{};              // direct rows
+    ShortRuns<T> srun{};           // gathered short rows
+};
+
+// Stage 3, the symbolic phase: chunk offsets in (row, k) order.  `paths`: which tables outlive it (ProductPaths{}: none,
+// what a slab of the multi-GPU product asks for); read_p: the count of partial products comes to the host here.
+template <class T>
+static Symbolic<T> symbolic_phase(Context *ctx, Scratch &sc, uint64_t M, const Shard<T> &sh, const ProductPaths &paths, bool read_p) {
+    hipStream_t s = ctx->stream;
+    const uint64_t nnz = sh.nnz;
+    Symbolic<T> sym;
+    sym.row_off = sc.get<uint64_t>(M + 1);
+    sym.chunk_off = sc.get<uint64_t>(nnz);
+    if (nnz == 0) {
+        OSP_HIP(hipMemsetAsync(sym.row_off, 0, (M + 1) * sizeof(uint64_t), s));
+        return sym;
+    }
+    Scratch ss(ctx);
+    Scratch &keep = paths.keep_table ? sc : ss;  // the chunk table outlives the symbolic phase
+    const RowSort rs(ss, nnz, std::max(1, bits_for(M)));
+    uint32_t *rows_sorted = (paths.gather_short ? keep : ss).template get<uint32_t>(nnz), *perm = keep.get<uint32_t>(nnz), *w_sorted = ss.get<uint32_t>(nnz);
+    uint32_t *bs_sorted = paths.keep_table ? keep.get<uint32_t>(nnz) : nullptr;
+    uint32_t *rowfirst = keep.get<uint32_t>(M + 1);
+    uint64_t *offs_sorted = keep.get<uint64_t>(nnz + 1);
+    uint64_t *scan_tmp = ss.get<uint64_t>(scan_scratch_entries(std::max<uint64_t>(nnz, M + 1)));
+    // (row, k) order of A's non-zeros; the last sort pass also looks up each chunk's length
+    T *av_sorted = paths.av_ride_along ? keep.get<T>(nnz) : nullptr;
+    uint32_t *w = ss.get<uint32_t>(paths.av_ride_along ? 4 * nnz : paths.keep_table ? 2 * nnz : nnz);   // (kept table: (length, B row) pairs)
+    uint32_t *bs = paths.keep_table ? w : nullptr;
+    sym_chunk_len_kernel<<<grid_for(nnz, 256), 256, 0, s>>>(sh.a_colptr, sh.b_rowptr, sh.k0, sh.k1, sh.e0, nnz, w, bs,
+                                                            paths.av_ride_along ? reinterpret_cast<const uint32_t *>(sh.a_vals) : nullptr, (uint32_t)(sizeof(T) / 4));
+    SymEpilogue sym_ep{w, bs, rows_sorted, perm, w_sorted, bs_sorted};
+    if (paths.av_ride_along) { sym_ep.av_sorted = av_sorted; sym_ep.vwords = (uint32_t)(sizeof(T) / 4); }
+    rs.sort(sh.a_rowidx + sh.e0, sym_ep);
+    device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{w_sorted}, nnz, offs_sorted, scan_tmp, s);
+    sym_row_offsets_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(rows_sorted, offs_sorted, nnz, M, sym.row_off, rowfirst);
+    const uint64_t rw_cap = (paths.rowwise || paths.gather_short) ? (uint64_t)TileCap<T>::value : 0ull;   // rows the multiply skips
+    if (!paths.expand_rows) sym_scatter_offsets_kernel<<<grid_for(nnz, 256), 256, 0, s>>>(perm, offs_sorted, rows_sorted, sym.row_off, rw_cap, nnz, sym.chunk_off);
+    // (the product proper reads P together with the size of the result, merge_pipeline: one stream round trip less)
+    sym.P = read_p ? d2h(offs_sorted + nnz, s) : kPartialsOnDevice;
+    if (paths.direct) {
+        DirectSrc &dsrc = sym.dsrc;
+        dsrc = DirectSrc{rowfirst, offs_sorted, bs_sorted, perm, sh.b_colidx, sym.chunk_off, paths.direct_max};
+        dsrc.b_rowptr = sh.b_rowptr; dsrc.K = sh.K; dsrc.nnz_b = sh.nnz_b; dsrc.keep = &sc;
+        dsrc.gather = paths.gather_long;
+        dsrc.expand_rows = paths.expand_rows;
+        if (paths.expand_rows) { dsrc.chunk_off_ready = false; dsrc.rows_sorted = rows_sorted; dsrc.row_off = sym.row_off; dsrc.rw_cap = rw_cap; dsrc.nnz = nnz; }
+        dsrc.a_vals = paths.av_ride_along ? (const void *)av_sorted : (const void *)(sh.a_vals + sh.e0); dsrc.av_in_order = paths.av_ride_along; dsrc.b_vals = sh.b_vals;
+        if (dsrc.gather) {
+            dsrc.gstat = (unsigned long long *)sc.get<uint64_t>(3);
+            zero_async(s, {{dsrc.gstat, 3 * sizeof(uint64_t)}});
+        }
+    }
+    if (paths.gather_short) {
+        // the short rows' chunks as run descriptors, chunks without entries left out (once per product)
+        const ShortRunFlag sf{offs_sorted};
+        uint32_t *cidx = ss.get<uint32_t>(nnz + 1), *cidx_tmp = ss.get<uint32_t>(scan_scratch_entries(nnz + 1));
+        device_exclusive_scan<ShortRunFlag, uint32_t>(sf, nnz, cidx, cidx_tmp, s);
+        RunDesc<T> *runs0 = sc.get<RunDesc<T>>(nnz);   // (bound: every chunk; the count stays on the device)
+        uint32_t *rowfirst0 = sc.get<uint32_t>(M + 1);
+        short_runs_kernel<T><<<grid_for(nnz, 256), 256, 0, s>>>(sf, cidx, nnz, bs_sorted, av_sorted, runs0);
+        short_rowfirst_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(rowfirst, cidx, M, rowfirst0);
+        sym.srun = ShortRuns<T>{runs0, rowfirst0, sh.b_colidx, sh.b_vals};
+    }
+    if (paths.rowwise) {
+        sym.ct = ChunkTable<T>{offs_sorted, bs_sorted, perm, rowfirst, sh.a_vals + sh.e0, sh.b_colidx, sh.b_vals, (uint32_t)rw_cap, 1u};
+        uint32_t *flag_scan = ss.get<uint32_t>(M + 1);
+        device_exclusive_scan<HeavyRowFlag, uint32_t>(HeavyRowFlag{sym.row_off, 0, (uint32_t)rw_cap}, M, flag_scan, (uint32_t *)scan_tmp, s);
+        sym.n_long_rows = d2h(flag_scan + M, s);
+    }
+    return sym;
+}
+
 template <class T>
 static void spgemm_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint64_t N, const int64_t *a_colptr_in,
                         const uint32_t *a_rowidx_in, const T *a_vals_in, const int64_t *b_rowptr_in,
@@ -130,269 +330,71 @@ static void spgemm_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
     OSP_HIP(hipEventRecord(ev.a, s));
     res->info.M = M; res->info.K = K; res->info.N = N;
 
-    // pointer arrays first: nnz comes from their last entries
-    const int64_t *a_colptr = to_device(sc, a_colptr_in, K + 1, space, s);
-    const int64_t *b_rowptr = to_device(sc, b_rowptr_in, K + 1, space, s);
-    int64_t nnz_a, nnz_b;
-    // (with them comes the number of partial products of the whole product -- a sum over k of two differences: what decides
-    // whether a product of few non-zeros still plans direct rows, see `direct` below)
+    // ---- 1. operands in ----
+    CompressedIn ops[2] = {{a_colptr_in, a_rowidx_in, a_vals_in, sizeof(T), K, M, "A (CSC)"}, {b_rowptr_in, b_colidx_in, b_vals_in, sizeof(T), K, N, "B (CSR)"}};
+    const CompressedIn &A = ops[0], &B = ops[1];
+    // (with the pointer arrays comes the number of partial products of the whole product -- a sum over k of two differences:
+    // what decides whether a product of few non-zeros still plans direct rows, osp_paths.h)
     uint64_t p_all = 0;
+    operand_ptrs_in(sc, s, space, ops);
     unsigned long long *p_all_dev = (unsigned long long *)sc.get<uint64_t>(1);
     zero_async(s, {{p_all_dev, sizeof(uint64_t)}});
-    // (few workgroups: every one ends in an atomic on ONE word, 11-13 ns apiece -- 3 579 of them were the 46 us this kernel took
-    // on the web-Google shape)
-    if (K) count_partials_kernel<<<(unsigned)std::min<uint64_t>(grid_for(K, 256), 256), 256, 0, s>>>(a_colptr, b_rowptr, K, p_all_dev);
-    {
-        Gather g(s);
-        if (space == OSP_HOST) { nnz_a = a_colptr_in[K]; nnz_b = b_rowptr_in[K]; }
-        else { g.add(&nnz_a, a_colptr + K); g.add(&nnz_b, b_rowptr + K); }
-        g.add(&p_all, (const uint64_t *)p_all_dev);
-        g.wait();
-    }
-    if (nnz_a < 0 || nnz_b < 0) throw Error(OSP_ERR_ARG, "negative nnz in pointer array");
-    if ((uint64_t)nnz_a >= 0xffffffffull || (uint64_t)nnz_b >= 0xffffffffull)
-        throw Error(OSP_ERR_ARG, "operands with >= 2^32 non-zeros are not supported");
-    const uint32_t *a_rowidx = to_device(sc, a_rowidx_in, nnz_a, space, s);
-    const T *a_vals = to_device(sc, a_vals_in, nnz_a, space, s);
-    const uint32_t *b_colidx = to_device(sc, b_colidx_in, nnz_b, space, s);
-    const T *b_vals = to_device(sc, b_vals_in, nnz_b, space, s);
-    res->info.nnz_a = nnz_a;
-    res->info.nnz_b = nnz_b;
+    // (few workgroups: every one ends in an atomic on ONE word, 11-13 ns apiece -- 3 579 of them were the 46 us this kernel
+    // took on the web-Google shape)
+    if (K) count_partials_kernel<<<(unsigned)std::min<uint64_t>(grid_for(K, 256), 256), 256, 0, s>>>(A.ptr, B.ptr, K, p_all_dev);
+    operand_nnz(s, space, ops, "negative nnz in pointer array", "operands with >= 2^32 non-zeros are not supported", &p_all, (const uint64_t *)p_all_dev);
+    for (CompressedIn &o : ops) operand_entries_in(sc, s, space, o);
+    res->info.nnz_a = A.nnz;
+    res->info.nnz_b = B.nnz;
+    if (cfg.validate) validate_operands(sc, s, ops);
 
-    if (cfg.validate) {
-        uint32_t *flags = sc.get<uint32_t>(2);
-        OSP_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(uint32_t), s));
-        validate_ptr_kernel<<<grid_for(K + 1, 256), 256, 0, s>>>(a_colptr, K, nnz_a, flags);
-        validate_ptr_kernel<<<grid_for(K + 1, 256), 256, 0, s>>>(b_rowptr, K, nnz_b, flags + 1);
-        uint32_t fa = 0, fb = 0;
-        { Gather g(s); g.add(&fa, (const uint32_t *)flags); g.add(&fb, (const uint32_t *)flags + 1); g.wait(); }
-        check_flags(fa, "A (CSC)");
-        check_flags(fb, "B (CSR)");
-        if (nnz_a) validate_idx_kernel<<<grid_for(nnz_a, 256), 256, 0, s>>>(a_colptr, a_rowidx, K, nnz_a, M, flags);
-        if (nnz_b) validate_idx_kernel<<<grid_for(nnz_b, 256), 256, 0, s>>>(b_rowptr, b_colidx, K, nnz_b, N, flags + 1);
-        { Gather g(s); g.add(&fa, (const uint32_t *)flags); g.add(&fb, (const uint32_t *)flags + 1); g.wait(); }
-        check_flags(fa, "A (CSC)");
-        check_flags(fb, "B (CSR)");
-    }
-
-    // ---- k shard ----
-    const uint64_t k0 = cfg.k_begin, k1 = cfg.k_end ? cfg.k_end : K;
-    if (ctx->env.verbose)
-        fprintf(stderr, "[osp] spgemm M=%llu K=%llu N=%llu nnzA=%lld nnzB=%lld k=[%llu,%llu) %s operands\n", (unsigned long long)M,
-                (unsigned long long)K, (unsigned long long)N, (long long)nnz_a, (long long)nnz_b, (unsigned long long)k0,
-                (unsigned long long)k1, space == OSP_HOST ? "host" : "device");
-    if (k0 > k1 || k1 > K) throw Error(OSP_ERR_ARG, "k range outside [0,K]");
-    int64_t e0 = 0, e1 = nnz_a;
-    if (k0 != 0 || k1 != K) {
-        if (space == OSP_HOST) { e0 = a_colptr_in[k0]; e1 = a_colptr_in[k1]; }
-        else { Gather g(s); g.add(&e0, a_colptr + k0); g.add(&e1, a_colptr + k1); g.wait(); }
-    }
-    // ---- row-sharded multi-GPU mode: find this rank's rows and drop the rest of A BEFORE the symbolic phase ----
-    // (a rank then sorts 1/G of A's non-zeros instead of all of them; every rank derives the same bounds from the
-    // replicated operands alone: no collective)
-    uint64_t r_lo = 0, r_hi = M;
+    // ---- 2. k shard and row shard, 3. symbolic phase ----
+    const Shard<T> sh = shard_of<T>(ctx, sc, tm, cfg, M, A, B);
     const bool row_sharded = cfg.row_shard_count > 1;
-    if (row_sharded) {
-        const uint64_t nnz = (uint64_t)(e1 - e0);  // all of the k shard's non-zeros: the pre-pass sees every row
-        if (cfg.row_shard_index < 0 || cfg.row_shard_index >= cfg.row_shard_count) throw Error(OSP_ERR_ARG, "row shard index out of range");
-        const uint32_t G = (uint32_t)cfg.row_shard_count;
-        tm.begin(PH_SYM);
-        {
-            Scratch cs(ctx);
-            unsigned long long *work = (unsigned long long *)cs.get<uint64_t>(M + 1);
-            uint64_t *pre = cs.get<uint64_t>(M + 1), *cost_pre = cs.get<uint64_t>(M + 1);
-            uint64_t *tmp = cs.get<uint64_t>(scan_scratch_entries(M + 1));
-            uint64_t *d_b = cs.get<uint64_t>(2ull * (G + 1));
-            OSP_HIP(hipMemsetAsync(work, 0, (M + 1) * sizeof(uint64_t), s));
-            // every 16th column is sample enough to balance G shards of a large matrix; small ones are counted exactly
-            const uint32_t stride = (k1 - k0) >= (1u << 16) ? 16u : 1u;
-            const uint64_t nsample = (k1 - k0 + stride - 1) / stride;
-            if (nnz) row_work_kernel<<<grid_for(nsample * kWave, 256), 256, 0, s>>>(a_colptr, a_rowidx, b_rowptr, k0, k1, stride, work);
-            device_exclusive_scan<LoadU64, uint64_t>(LoadU64{(const uint64_t *)work}, M, pre, tmp, s);
-            device_exclusive_scan<RowCost, uint64_t>(RowCost{pre, (uint64_t)TileCap<T>::value, kSplitRowMax}, M, cost_pre, tmp, s);
-            shard_bounds_kernel<<<grid_for(G + 1, 64), 64, 0, s>>>(cost_pre, pre, M, G, d_b, d_b + G + 1);
-            std::vector<uint64_t> h_b(2ull * (G + 1));
-            copy_d2h(h_b.data(), d_b, h_b.size() * sizeof(uint64_t), s);
-            r_lo = h_b[cfg.row_shard_index];
-            r_hi = h_b[cfg.row_shard_index + 1];
-        }
-        // A restricted to rows [r_lo, r_hi): same K columns, absolute row ids
-        int64_t *colptr2 = sc.get<int64_t>(K + 1);
-        uint64_t nnz2 = 0;
-        uint32_t *rowidx2 = nullptr;
-        T *vals2 = nullptr;
-        {
-            Scratch cs(ctx);
-            uint32_t *keep_scan = cs.get<uint32_t>(nnz + 1);
-            uint32_t *tmp = cs.get<uint32_t>(scan_scratch_entries(nnz + 1));
-            const RowInRange keep{a_rowidx + e0, (uint32_t)r_lo, r_hi};
-            device_exclusive_scan<RowInRange, uint32_t>(keep, nnz, keep_scan, tmp, s);
-            nnz2 = d2h(keep_scan + nnz, s);
-            rowidx2 = sc.get<uint32_t>(nnz2);
-            vals2 = sc.get<T>(nnz2);
-            restrict_colptr_kernel<<<grid_for(K + 1, 256), 256, 0, s>>>(a_colptr, K, e0, nnz, keep_scan, colptr2);
-            if (nnz2) restrict_compact_kernel<T><<<grid_for(nnz, 256), 256, 0, s>>>(keep, keep_scan, nnz, a_vals + e0, rowidx2, vals2);
-        }
-        tm.end(PH_SYM);
-        a_colptr = colptr2; a_rowidx = rowidx2; a_vals = vals2;
-        e0 = 0;  // columns before k0 are empty now
-        e1 = (int64_t)nnz2;
-    }
-    const uint64_t nnz = (uint64_t)(e1 - e0);  // non-zeros of A inside the shard
-
-    // ---- symbolic: chunk offsets in (row, k) order ----
+    if (cfg.algorithm != OSP_ALGO_OUTER && cfg.algorithm != OSP_ALGO_ROWWISE) throw Error(OSP_ERR_ARG, "unknown algorithm");
+    const ProductPaths paths = choose_paths(ctx->env, cfg.algorithm, sh.nnz, p_all, M, N, partials_only, PathLimits{kSplitRowMax, kDirectDenseMax});
     tm.begin(PH_SYM);
-    uint64_t *row_off = sc.get<uint64_t>(M + 1);
-    uint64_t *chunk_off = sc.get<uint64_t>(nnz);
-    uint64_t P = 0;
-    // Row-wise variant (cfg.algorithm): rows of up to one tile of partial products are computed inside the tile kernel
-    // from the chunk table; B's offsets must fit 32 bits for it (otherwise the outer-product path runs as usual)
-    const int algo = cfg.algorithm;
-    if (algo != OSP_ALGO_OUTER && algo != OSP_ALGO_ROWWISE) throw Error(OSP_ERR_ARG, "unknown algorithm");
-    const bool rowwise = algo == OSP_ALGO_ROWWISE && nnz && (uint64_t)nnz_b < 0xffffffffull && nnz < 0xffffffffull && !partials_only;
-    ChunkTable<T> ct{};
-    // Long rows that one workgroup could split are written straight into their column ranges by the multiply phase
-    // ("direct" rows, osp_split.h) when the operands allow 32-bit B offsets.  OSP_DIRECT=0 switches that off (every long
-    // row is then split after the multiply, as the parts-merging entry points do), OSP_DIRECT_MAX=<partial products>
-    // bounds the rows it applies to.
-    // Small products keep the split: the plan costs a handful of launches and a read-back, which a product of a few
-    // milliseconds does not earn back (web-Google shape: 2.3 ms with the split, 2.7 with direct rows).  OSP_DIRECT_MIN_NNZ
-    // moves that boundary (the tests set it to 0, so that their small inputs take the direct path).
-    const Settings &env = ctx->env;
-    const uint64_t direct_min_nnz = env.direct_min_nnz.or_((env.gather.set && env.gather.value == 0) ? (8ull << 20) : (2ull << 20));
-    // ... unless its output rows are dense on average (at least 0.375 partial products per entry of the M x N result -- three times the
-    // density from which a long row's column ranges are capped at the dense accumulators' width, plan_panel): such rows are
-    // written in a few wide ranges, long runs, and summed without a sort -- 4096^2 with 880 entries per row (3.6 M non-zeros,
-    // 3.2 G partial products) 44.4 -> 26.4 ms, Graph500 scale 14 ef 512 100 -> 79 ms.
-    const bool dense_avg = (long double)p_all * 8.0L >= 3.0L * (long double)M * (long double)N;
-    const bool direct = nnz && (nnz >= direct_min_nnz || dense_avg) && (uint64_t)nnz_b < 0xffffffffull && nnz < 0xffffffffull && !partials_only &&
-                        env.direct.on;
-    const uint64_t direct_max = std::min<uint64_t>(env.direct_max.or_(kSplitRowMax), kDirectDenseMax);   // (the planner counts a row's products in 21 bits)
-    // Gathered rows (osp_kernels.h): the merge kernel forms the partial products of planned long rows and of short rows itself,
-    // from run descriptors; on unless OSP_GATHER=0 (debugging aid, A/B timing: every row is then written by the multiply, as
-    // until round 4) or the row-wise variant runs (its tile kernel is another instantiation).  OSP_GATHER=1: long rows only.
-    const int gather_env = env.gather.or_(2);
-    const bool gather_ok = nnz && !rowwise && !partials_only && (uint64_t)nnz_b < 0xffffffffull && nnz < 0xffffffffull;
-    // (short rows: only where long rows are planned too -- a product of a few million non-zeros does not earn the tables back:
-    // web-Google shape 2.09 -> 2.50 ms with them)
-    const bool gather_short = gather_ok && gather_env >= 2 && direct;
-    ShortRuns<T> srun{};
-    DirectSrc dsrc{};
-    uint32_t n_long_rows = 1;
-    if (nnz == 0) {
-        OSP_HIP(hipMemsetAsync(row_off, 0, (M + 1) * sizeof(uint64_t), s));
-    } else {
-        Scratch ss(ctx);
-        Scratch &keep = (rowwise || direct || gather_short) ? sc : ss;  // the chunk table outlives the symbolic phase
-        const RowSort rs(ss, nnz, std::max(1, bits_for(M)));
-        uint32_t *rows_sorted = (gather_short ? keep : ss).template get<uint32_t>(nnz), *perm = keep.get<uint32_t>(nnz), *w_sorted = ss.get<uint32_t>(nnz);
-        uint32_t *bs_sorted = (rowwise || direct || gather_short) ? keep.get<uint32_t>(nnz) : nullptr;
-        uint32_t *rowfirst = keep.get<uint32_t>(M + 1);
-        uint64_t *offs_sorted = keep.get<uint64_t>(nnz + 1);
-        uint64_t *scan_tmp = ss.get<uint64_t>(scan_scratch_entries(std::max<uint64_t>(nnz, M + 1)));
-        // (row, k) order of A's non-zeros; the last sort pass also looks up each chunk's length
-        const bool table = rowwise || direct || gather_short;   // keep the chunk table: (length, B row) pairs in `w`
-        // (gathered rows: the A values ride along, so that the run descriptors' makers read them in (row, k) order)
-        const bool with_av = gather_ok && gather_env >= 1 && (direct || gather_short);
-        T *av_sorted = with_av ? keep.get<T>(nnz) : nullptr;
-        uint32_t *w = ss.get<uint32_t>(with_av ? 4 * nnz : table ? 2 * nnz : nnz);
-        uint32_t *bs = table ? w : nullptr;
-        sym_chunk_len_kernel<<<grid_for(nnz, 256), 256, 0, s>>>(a_colptr, b_rowptr, k0, k1, e0, nnz, w, bs,
-                                                                with_av ? reinterpret_cast<const uint32_t *>(a_vals) : nullptr, (uint32_t)(sizeof(T) / 4));
-        SymEpilogue sym_ep{w, bs, rows_sorted, perm, w_sorted, bs_sorted};
-        if (with_av) { sym_ep.av_sorted = av_sorted; sym_ep.vwords = (uint32_t)(sizeof(T) / 4); }
-        rs.sort(a_rowidx + e0, sym_ep);
-        device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{w_sorted}, nnz, offs_sorted, scan_tmp, s);
-        sym_row_offsets_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(rows_sorted, offs_sorted, nnz, M, row_off, rowfirst);
-        const uint64_t rw_cap = (rowwise || gather_short) ? (uint64_t)TileCap<T>::value : 0ull;   // rows the multiply skips
-        // (lazily where only rows written through cells would read them: DirectSrc::ensure_chunk_off)
-        const bool expand_rows_on = gather_short && env.expand_rows.on;
-        if (!expand_rows_on) sym_scatter_offsets_kernel<<<grid_for(nnz, 256), 256, 0, s>>>(perm, offs_sorted, rows_sorted, row_off, rw_cap, nnz, chunk_off);
-        // (the product proper reads P together with the size of the result, merge_pipeline: one stream round trip less)
-        if (partials_only || rowwise || row_sharded) P = d2h(offs_sorted + nnz, s);
-        else P = kPartialsOnDevice;
-        if (direct) {
-            dsrc = DirectSrc{rowfirst, offs_sorted, bs_sorted, perm, b_colidx, chunk_off, direct_max};
-            dsrc.b_rowptr = b_rowptr; dsrc.K = K; dsrc.nnz_b = (uint64_t)nnz_b; dsrc.keep = &sc;
-            // gathered rows (osp_kernels.h): on unless OSP_GATHER=0 (debugging aid, A/B timing: every direct row is then written
-            // by the multiply, as until round 4) or the row-wise variant runs (its tile kernel is another instantiation)
-            dsrc.gather = gather_ok && gather_env >= 1;
-            dsrc.expand_rows = expand_rows_on;
-            if (expand_rows_on) { dsrc.chunk_off_ready = false; dsrc.rows_sorted = rows_sorted; dsrc.row_off = row_off; dsrc.rw_cap = rw_cap; dsrc.nnz = nnz; }
-            dsrc.a_vals = with_av ? (const void *)av_sorted : (const void *)(a_vals + e0); dsrc.av_in_order = with_av; dsrc.b_vals = b_vals;
-            if (dsrc.gather) {
-                dsrc.gstat = (unsigned long long *)sc.get<uint64_t>(3);
-                zero_async(s, {{dsrc.gstat, 3 * sizeof(uint64_t)}});
-            }
-        }
-        if (gather_short) {
-            // the short rows' chunks as run descriptors, chunks without entries left out (once per product)
-            const ShortRunFlag sf{offs_sorted};
-            uint32_t *cidx = ss.get<uint32_t>(nnz + 1), *cidx_tmp = ss.get<uint32_t>(scan_scratch_entries(nnz + 1));
-            device_exclusive_scan<ShortRunFlag, uint32_t>(sf, nnz, cidx, cidx_tmp, s);
-            RunDesc<T> *runs0 = sc.get<RunDesc<T>>(nnz);   // (bound: every chunk; the count stays on the device)
-            uint32_t *rowfirst0 = sc.get<uint32_t>(M + 1);
-            short_runs_kernel<T><<<grid_for(nnz, 256), 256, 0, s>>>(sf, cidx, nnz, bs_sorted, av_sorted, runs0);
-            short_rowfirst_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(rowfirst, cidx, M, rowfirst0);
-            srun = ShortRuns<T>{runs0, rowfirst0, b_colidx, b_vals};
-        }
-        if (rowwise) {
-            ct = ChunkTable<T>{offs_sorted, bs_sorted, perm, rowfirst, a_vals + e0, b_colidx, b_vals, (uint32_t)rw_cap, 1u};
-            uint32_t *flag_scan = ss.get<uint32_t>(M + 1);
-            device_exclusive_scan<HeavyRowFlag, uint32_t>(HeavyRowFlag{row_off, 0, (uint32_t)rw_cap}, M, flag_scan, (uint32_t *)scan_tmp, s);
-            n_long_rows = d2h(flag_scan + M, s);
-        }
-    }
+    const Symbolic<T> sym = symbolic_phase<T>(ctx, sc, M, sh, paths, partials_only || paths.rowwise || row_sharded);
     tm.end(PH_SYM);
-    res->info.partials = P;
+    res->info.partials = sym.P;
 
+    // ---- 4. producer ----
     OuterProducer<T> prod;
-    prod.ctx = ctx; prod.res = res;
-    prod.a_colptr = a_colptr; prod.a_rowidx = a_rowidx; prod.a_vals = a_vals;
-    prod.b_rowptr = b_rowptr; prod.b_colidx = b_colidx; prod.b_vals = b_vals;
-    prod.k0 = k0; prod.k1 = k1; prod.e0 = e0; prod.chunk_off = chunk_off;
-    const uint64_t nk = k1 - k0;
-    prod.a_start = sc.get<int64_t>(nk); prod.a_cnt = sc.get<uint32_t>(nk);
-    prod.prod = sc.get<uint64_t>(nk); prod.prod_off = sc.get<uint64_t>(nk + 1);
-    prod.scan_tmp = sc.get<uint64_t>(scan_scratch_entries(nk));
-    prod.nothing_staged = rowwise && n_long_rows == 0;
-    prod.short_gathered = gather_short;
-    if ((dsrc.gather || gather_short) && nnz && !partials_only) {
-        prod.nnz = nnz;
-        prod.kscan = sc.get<uint32_t>(nnz + 1);
-        prod.kscan_tmp = sc.get<uint32_t>(scan_scratch_entries(std::max<uint64_t>(nnz, k1 - k0) + 1));
-        prod.elist = sc.get<uint32_t>(nnz);
-        prod.cscan = sc.get<uint32_t>(k1 - k0 + 1);
-        prod.klist = sc.get<uint32_t>(k1 - k0 + 1);
-    }
+    prod.bind(ctx, res, sc, sh, sym.chunk_off, paths.gather_long);
+    prod.nothing_staged = paths.rowwise && sym.n_long_rows == 0;
+    prod.short_gathered = paths.gather_short;
 
+    // ---- 5. partials-only exit or pipeline and statistics ----
     if (partials_only) {
         // osp_spgemm_partials: the multiply phase alone; offsets and records belong to the result
         if (row_sharded) throw Error(OSP_ERR_ARG, "partial products of a row shard are not supported");
         res->partials = true;
         res->rowptr = (int64_t *)ctx->alloc((M + 1) * sizeof(int64_t));
-        OSP_HIP(hipMemcpyAsync(res->rowptr, row_off, (M + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-        res->vals = ctx->alloc(std::max<uint64_t>(P, 1) * sizeof(Part<T>));
+        OSP_HIP(hipMemcpyAsync(res->rowptr, sym.row_off, (M + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+        res->vals = ctx->alloc(std::max<uint64_t>(sym.P, 1) * sizeof(Part<T>));
         res->info.panels = 1;
-        res->info.nnz_c = P;
+        res->info.nnz_c = sym.P;
         res->info.row_begin = 0;
         res->info.row_end = M;
         tm.begin(PH_MUL);
-        if (P) prod.produce(0, M, true, 0, P, (Part<T> *)res->vals, tm, nullptr, nullptr);
+        if (sym.P) prod.produce(PanelWork<T>{0, M, true, 0, sym.P, (Part<T> *)res->vals}, tm);
         tm.end(PH_MUL);
         finish_timing(res, ev, tm, s);
         return;
     }
-    // row-sharded: A holds this rank's rows only, so the staging offsets start at 0 at r_lo and P is the shard's count
-    const uint64_t off_lo = 0, P_rows = P;
-    merge_pipeline<T>(ctx, res, prod, M, N, row_off, P_rows, cfg.partial_capacity, tm, r_lo, r_hi, off_lo, sink,
-                      rowwise ? &ct : nullptr, (direct && nnz) ? &dsrc : nullptr, nullptr, gather_short ? &srun : nullptr);
-
+    MergeRequest<T> rq{M, N, sym.row_off, sym.P, cfg.partial_capacity};
+    rq.r_lo = sh.r_lo; rq.r_hi = sh.r_hi;
+    rq.sink = sink;
+    if (paths.rowwise) rq.ct = &sym.ct;
+    if (paths.direct) rq.ds = &sym.dsrc;
+    rq.short_runs = sym.srun;
+    merge_pipeline<T>(ctx, res, prod, tm, rq);
     finish_timing(res, ev, tm, s);
-    if (gather_short) res->info.gathered_short_partials = res->info.partials - res->info.heavy_partials;
-    if (dsrc.gstat && res->info.direct_rows) {
+    // what the gathered rows came to (after the product's timing: the read-back is not part of it)
+    if (paths.gather_short) res->info.gathered_short_partials = res->info.partials - res->info.heavy_partials;
+    if (sym.dsrc.gstat && res->info.direct_rows) {
         uint64_t gs[3] = {0, 0, 0};
-        copy_d2h(gs, dsrc.gstat, sizeof(gs), s);
+        copy_d2h(gs, sym.dsrc.gstat, sizeof(gs), s);
         res->info.gathered_rows = gs[0]; res->info.gathered_partials = gs[1]; res->info.gathered_runs = gs[2];
     }
     if (ctx->env.verbose) {
@@ -467,13 +469,12 @@ static void spgemm_aos_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, u
     hipStream_t s = ctx->stream;
     Scratch sc(ctx);
     // size_t offsets are taken as int64 (same bits below 2^63; larger values fail the pointer check)
-    const int64_t *ap = to_device(sc, (const int64_t *)a_pos, K + 1, space, s);
-    const int64_t *bp = to_device(sc, (const int64_t *)b_pos, K + 1, space, s);
-    int64_t nnz_a, nnz_b;
-    if (space == OSP_HOST) { nnz_a = (int64_t)a_pos[K]; nnz_b = (int64_t)b_pos[K]; }
-    else { nnz_a = d2h(ap + K, s); nnz_b = d2h(bp + K, s); }
-    if (nnz_a < 0 || nnz_b < 0 || (uint64_t)nnz_a >= 0xffffffffull || (uint64_t)nnz_b >= 0xffffffffull)
-        throw Error(OSP_ERR_ARG, "operands with >= 2^32 non-zeros are not supported");
+    CompressedIn pos[2] = {{(const int64_t *)a_pos, nullptr, nullptr, 0, K, M, "A (CSC)"}, {(const int64_t *)b_pos, nullptr, nullptr, 0, K, N, "B (CSR)"}};
+    const char *const too_many = "operands with >= 2^32 non-zeros are not supported";
+    operand_ptrs_in(sc, s, space, pos);
+    operand_nnz(s, space, pos, too_many, too_many);
+    const int64_t *ap = pos[0].ptr, *bp = pos[1].ptr;
+    const int64_t nnz_a = pos[0].nnz, nnz_b = pos[1].nnz;
     if ((nnz_a && !a_data) || (nnz_b && !b_data)) throw Error(OSP_ERR_ARG, "null data array");
     const Part<T> *ad = to_device(sc, (const Part<T> *)a_data, (uint64_t)nnz_a, space, s);
     const Part<T> *bd = to_device(sc, (const Part<T> *)b_data, (uint64_t)nnz_b, space, s);
@@ -486,11 +487,19 @@ static void spgemm_aos_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, u
 
 // The symbolic phase of a parts merge: the candidate chunks -- chunk (r, p) = row r of part p -- scanned into every row's
 // offset into the staging (prod.row_off); info.partials = P, the entries of all parts.  `prod` reads the parts' rows
-// through d_rp, the device array of their row pointers.
+// a host array of device pointers, on the device
+template <class P>
+static const P *pointer_table(Scratch &sc, hipStream_t s, const std::vector<P> &h) {
+    P *d = (P *)sc.get<void *>(h.size());
+    copy_h2d(d, h.data(), h.size() * sizeof(void *), s);
+    return d;
+}
+// through a device array of their row pointers (rp: the pointers themselves, on the host).
 template <class Producer>
-static void parts_symbolic(Context *ctx, Scratch &sc, PhaseTimer &tm, Result *res, const int64_t *const *d_rp, int nparts, uint64_t M,
-                           Producer &prod) {
+static void parts_symbolic(Context *ctx, Scratch &sc, PhaseTimer &tm, Result *res, const std::vector<const int64_t *> &rp, uint64_t M, Producer &prod) {
     hipStream_t s = ctx->stream;
+    const int nparts = (int)rp.size();
+    const int64_t *const *d_rp = pointer_table(sc, s, rp);
     tm.begin(PH_SYM);
     const uint64_t ncand = M * (uint64_t)nparts;
     uint64_t *row_off = sc.get<uint64_t>(M + 1);
@@ -504,6 +513,13 @@ static void parts_symbolic(Context *ctx, Scratch &sc, PhaseTimer &tm, Result *re
     prod.ctx = ctx; prod.d_rowptrs = d_rp; prod.nparts = nparts; prod.row_off = row_off;
 }
 
+// One part of a parts merge on its way in: its row pointers (d: on the device) and its count of entries, refused when negative.
+static uint64_t part_ptr_in(Scratch &sc, hipStream_t s, osp_memspace_t space, const int64_t *rowptr, uint64_t M, const char *negative, const int64_t *&d) {
+    d = to_device(sc, rowptr, M + 1, space, s);
+    const int64_t n = (space == OSP_HOST) ? rowptr[M] : d2h(d + M, s);
+    if (n < 0) throw Error(OSP_ERR_ARG, negative);
+    return (uint64_t)n;
+}
 template <class T>
 static void merge_parts_impl(Context *ctx, Result *res, uint64_t M, uint64_t N, int nparts,
                              const int64_t *const *rowptrs, const uint32_t *const *colidxs, const void *const *valss,
@@ -519,9 +535,7 @@ static void merge_parts_impl(Context *ctx, Result *res, uint64_t M, uint64_t N, 
     std::vector<const T *> va(nparts);
     uint64_t nnz_in = 0;
     for (int p = 0; p < nparts; p++) {
-        rp[p] = to_device(sc, rowptrs[p], M + 1, space, s);
-        int64_t nnz = (space == OSP_HOST) ? rowptrs[p][M] : d2h(rp[p] + M, s);
-        if (nnz < 0) throw Error(OSP_ERR_ARG, "negative nnz in part");
+        const uint64_t nnz = part_ptr_in(sc, s, space, rowptrs[p], M, "negative nnz in part", rp[p]);
         ci[p] = to_device(sc, colidxs[p], nnz, space, s);
         va[p] = to_device(sc, (const T *)valss[p], nnz, space, s);
         nnz_in += nnz;
@@ -530,16 +544,10 @@ static void merge_parts_impl(Context *ctx, Result *res, uint64_t M, uint64_t N, 
     if (ctx->env.verbose)
         fprintf(stderr, "[osp] merge_csr_parts M=%llu N=%llu parts=%d entries=%llu %s operands\n", (unsigned long long)M,
                 (unsigned long long)N, nparts, (unsigned long long)nnz_in, space == OSP_HOST ? "host" : "device");
-    const int64_t **d_rp = (const int64_t **)sc.get<void *>(nparts);
-    const uint32_t **d_ci = (const uint32_t **)sc.get<void *>(nparts);
-    const T **d_va = (const T **)sc.get<void *>(nparts);
-    copy_h2d(d_rp, rp.data(), nparts * sizeof(void *), s);
-    copy_h2d(d_ci, ci.data(), nparts * sizeof(void *), s);
-    copy_h2d(d_va, va.data(), nparts * sizeof(void *), s);
     PartsProducer<T> prod;
-    prod.d_colidxs = d_ci; prod.d_valss = d_va;
-    parts_symbolic(ctx, sc, tm, res, d_rp, nparts, M, prod);
-    merge_pipeline<T>(ctx, res, prod, M, N, prod.row_off, res->info.partials, cfg.partial_capacity, tm);
+    prod.d_colidxs = pointer_table(sc, s, ci); prod.d_valss = pointer_table(sc, s, va);
+    parts_symbolic(ctx, sc, tm, res, rp, M, prod);
+    merge_pipeline<T>(ctx, res, prod, tm, MergeRequest<T>{M, N, prod.row_off, res->info.partials, cfg.partial_capacity});
     finish_timing(res, ev, tm, s);
 }
 
@@ -556,35 +564,29 @@ static void merge_record_parts_impl(Context *ctx, Result *res, uint64_t M, uint6
     res->info.M = M; res->info.N = N;
     std::vector<const int64_t *> rp(nparts);
     std::vector<const Part<T> *> rc(nparts);
-    uint64_t nnz_in = 0;
+    std::vector<uint64_t> count(nparts);
     for (int p = 0; p < nparts; p++) {
-        rp[p] = to_device(sc, rowptrs[p], M + 1, space, s);
-        const int64_t n = (space == OSP_HOST) ? rowptrs[p][M] : d2h(rp[p] + M, s);
-        if (n < 0) throw Error(OSP_ERR_ARG, "negative record count in part");
-        rc[p] = to_device(sc, (const Part<T> *)records[p], (uint64_t)n, space, s);
-        nnz_in += (uint64_t)n;
+        count[p] = part_ptr_in(sc, s, space, rowptrs[p], M, "negative record count in part", rp[p]);
+        rc[p] = to_device(sc, (const Part<T> *)records[p], count[p], space, s);
+        res->info.nnz_a += count[p];
     }
-    res->info.nnz_a = nnz_in;
     if (cfg.validate) {
         // offsets monotone from 0 to the record count, columns below N: what the split and dense paths index with
         uint32_t *flags = sc.get<uint32_t>(1);
         OSP_HIP(hipMemsetAsync(flags, 0, sizeof(uint32_t), s));
         for (int p = 0; p < nparts; p++) {
-            const uint64_t n = (uint64_t)((space == OSP_HOST) ? rowptrs[p][M] : d2h(rp[p] + M, s));
+            const uint64_t n = count[p];
             validate_ptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(rp[p], M, n, flags);
             if (n) validate_record_cols_kernel<T><<<grid_for(n, 256), 256, 0, s>>>(rc[p], n, N, flags);
         }
         check_flags(d2h(flags, s), "record parts");
     }
-    const int64_t **d_rp = (const int64_t **)sc.get<void *>(nparts);
-    const Part<T> **d_rc = (const Part<T> **)sc.get<void *>(nparts);
-    copy_h2d(d_rp, rp.data(), nparts * sizeof(void *), s);
-    copy_h2d(d_rc, rc.data(), nparts * sizeof(void *), s);
     RecordPartsProducer<T> prod;
-    prod.d_recs = d_rc; prod.before = before;
-    parts_symbolic(ctx, sc, tm, res, d_rp, nparts, M, prod);
-    merge_pipeline<T>(ctx, res, prod, M, N, prod.row_off, res->info.partials, cfg.partial_capacity, tm, 0, ~0ull, 0, nullptr, nullptr,
-                      nullptr, cuts);
+    prod.d_recs = pointer_table(sc, s, rc); prod.before = before;
+    parts_symbolic(ctx, sc, tm, res, rp, M, prod);
+    MergeRequest<T> rq{M, N, prod.row_off, res->info.partials, cfg.partial_capacity};
+    rq.cuts = cuts;
+    merge_pipeline<T>(ctx, res, prod, tm, rq);
     finish_timing(res, ev, tm, s);
 }
 
@@ -1425,14 +1427,9 @@ int osp_spgemm_multi(osp_multi_context_t mc_, osp_multi_operands_t ops_, const o
                 OSP_HIP(hipSetDevice(c->device));
                 const MultiOperands::Slab &sl = ops->slab[g];
                 Scratch sc(c);
-                uint32_t *flags = sc.get<uint32_t>(2);
-                OSP_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(uint32_t), c->stream));
-                if (sl.nnz_a) validate_idx_kernel<<<grid_for(sl.nnz_a, 256), 256, 0, c->stream>>>(sl.a_colptr, sl.a_rowidx, sl.K, sl.nnz_a, ops->M, flags);
-                if (sl.nnz_b) validate_idx_kernel<<<grid_for(sl.nnz_b, 256), 256, 0, c->stream>>>(sl.b_rowptr, sl.b_colidx, sl.K, sl.nnz_b, ops->N, flags + 1);
-                uint32_t fa = 0, fb = 0;
-                { Gather gt(c->stream); gt.add(&fa, (const uint32_t *)flags); gt.add(&fb, (const uint32_t *)flags + 1); gt.wait(); }
-                check_flags(fa, "A (CSC)");
-                check_flags(fb, "B (CSR)");
+                const CompressedIn slab[2] = {{sl.a_colptr, sl.a_rowidx, nullptr, 0, sl.K, ops->M, "A (CSC)", (int64_t)sl.nnz_a},
+                                              {sl.b_rowptr, sl.b_colidx, nullptr, 0, sl.K, ops->N, "B (CSR)", (int64_t)sl.nnz_b}};
+                validate_operands(sc, c->stream, slab, false);   // (the pointer arrays were checked on the host when the operands were made)
             }
         }
         with_type(ops->dtype, [&](auto tag) { multi_product<decltype(tag)>(mc, ops, res.get(), cfg); });

@@ -113,31 +113,6 @@ __global__ void rebase_offsets_kernel(int64_t *rp, uint64_t n, int64_t first) {
     if (i < n) rp[i] -= first;
 }
 
-// symbolic phase of one slab (the rank's columns of A / rows of B as arrays of their own): records per output row and
-// the offset of every chunk.  The same launches spgemm_impl makes, without the variants a slab does not use.
-template <class T>
-static uint64_t slab_symbolic(Context *ctx, uint64_t M, uint64_t Ks, const int64_t *a_colptr, const uint32_t *a_rowidx, const int64_t *b_rowptr,
-                              uint64_t nnz, uint64_t *row_off, uint64_t *chunk_off) {
-    hipStream_t s = ctx->stream;
-    if (nnz == 0) {
-        OSP_HIP(hipMemsetAsync(row_off, 0, (M + 1) * sizeof(uint64_t), s));
-        return 0;
-    }
-    Scratch ss(ctx);
-    const RowSort rs(ss, nnz, std::max(1, bits_for(M)));
-    uint32_t *rows_sorted = ss.get<uint32_t>(nnz), *perm = ss.get<uint32_t>(nnz), *w_sorted = ss.get<uint32_t>(nnz);
-    uint32_t *rowfirst = ss.get<uint32_t>(M + 1);
-    uint64_t *offs_sorted = ss.get<uint64_t>(nnz + 1);
-    uint64_t *scan_tmp = ss.get<uint64_t>(scan_scratch_entries(std::max<uint64_t>(nnz, M + 1)));
-    uint32_t *w = ss.get<uint32_t>(nnz);
-    sym_chunk_len_kernel<<<grid_for(nnz, 256), 256, 0, s>>>(a_colptr, b_rowptr, 0, Ks, 0, nnz, w, nullptr);
-    rs.sort(a_rowidx, SymEpilogue{w, nullptr, rows_sorted, perm, w_sorted, nullptr});
-    device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{w_sorted}, nnz, offs_sorted, scan_tmp, s);
-    sym_row_offsets_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(rows_sorted, offs_sorted, nnz, M, row_off, rowfirst);
-    sym_scatter_offsets_kernel<<<grid_for(nnz, 256), 256, 0, s>>>(perm, offs_sorted, rows_sorted, row_off, 0, nnz, chunk_off);
-    return d2h(offs_sorted + nnz, s);
-}
-
 // everything the rank threads of one product share
 template <class T> struct MultiShared {
     int G = 0, R = 1;
@@ -182,7 +157,7 @@ static void multi_rank_main(MultiContext *mc, const MultiOperands *ops, MultiSha
     Scratch sc(ctx);
     PhaseTimer tm(s);
     const MultiOperands::Slab &sl = ops->slab[g];
-    uint64_t *row_off = nullptr, *chunk_off = nullptr;
+    uint64_t *row_off = nullptr;
     OuterProducer<T> prod;
     Result dummy;   // the producer counts its launches into a result
     const auto t_begin = std::chrono::steady_clock::now();
@@ -191,17 +166,15 @@ static void multi_rank_main(MultiContext *mc, const MultiOperands *ops, MultiSha
     };
     // ---- A. symbolic phase of the slab ----
     guarded([&] {
-        row_off = sc.get<uint64_t>(M + 1);
-        chunk_off = sc.get<uint64_t>(sl.nnz_a);
-        sh->P[g] = slab_symbolic<T>(ctx, M, sl.K, sl.a_colptr, sl.a_rowidx, sl.b_rowptr, sl.nnz_a, row_off, chunk_off);
+        // (the rank's columns of A / rows of B as arrays of their own: a shard of all its columns and all rows; the symbolic
+        // phase of spgemm_impl without the variants a slab does not use: records per output row, the offset of every chunk)
+        const Shard<T> slab{sl.a_colptr, sl.a_rowidx, (const T *)sl.a_vals, sl.b_rowptr, sl.b_colidx, (const T *)sl.b_vals,
+                            sl.K, sl.nnz_b, 0, sl.K, 0, sl.nnz_a, 0, M};
+        const Symbolic<T> sym = symbolic_phase<T>(ctx, sc, M, slab, ProductPaths{}, true);
+        row_off = sym.row_off;
+        sh->P[g] = sym.P;
         sh->row_off[g] = row_off;
-        prod.ctx = ctx; prod.res = &dummy;
-        prod.a_colptr = sl.a_colptr; prod.a_rowidx = sl.a_rowidx; prod.a_vals = (const T *)sl.a_vals;
-        prod.b_rowptr = sl.b_rowptr; prod.b_colidx = sl.b_colidx; prod.b_vals = (const T *)sl.b_vals;
-        prod.k0 = 0; prod.k1 = sl.K; prod.e0 = 0; prod.chunk_off = chunk_off;
-        prod.a_start = sc.get<int64_t>(sl.K); prod.a_cnt = sc.get<uint32_t>(sl.K);
-        prod.prod = sc.get<uint64_t>(sl.K); prod.prod_off = sc.get<uint64_t>(sl.K + 1);
-        prod.scan_tmp = sc.get<uint64_t>(scan_scratch_entries(sl.K));
+        prod.bind(ctx, &dummy, sc, slab, sym.chunk_off);
         OSP_HIP(hipStreamSynchronize(s));
     });
     const float ms_symbolic = ms_since(t_begin);
@@ -298,14 +271,14 @@ static void multi_rank_main(MultiContext *mc, const MultiOperands *ops, MultiSha
                 hipEvent_t arrive = sh->ev[((size_t)h * G + g) * R + r];
                 if (h == g) {
                     // own rows: multiplied straight into the receive buffer
-                    if (count) prod.produce(r0, r1, false, base, count, sh->recv[g][g] + dst_off, tm, nullptr, nullptr);
+                    if (count) prod.produce(PanelWork<T>{r0, r1, false, base, count, sh->recv[g][g] + dst_off}, tm);
                     OSP_HIP(hipEventRecord(arrive, s));
                 } else {
                     hipStream_t cs = mc->copy[g][h];
                     if (count) {
                         Slot &sl2 = slots[h][r & 1];
                         if (sl2.used) OSP_HIP(hipStreamWaitEvent(s, sl2.copied, 0));   // the copy out of this slot (sub-panel r - 2) has finished
-                        prod.produce(r0, r1, false, base, count, sl2.buf, tm, nullptr, nullptr);
+                        prod.produce(PanelWork<T>{r0, r1, false, base, count, sl2.buf}, tm);
                         OSP_HIP(hipEventRecord(sl2.produced, s));
                         OSP_HIP(hipStreamWaitEvent(cs, sl2.produced, 0));
                         CopyRec cr;

@@ -10,21 +10,33 @@
         else { constexpr bool RA = false; __VA_ARGS__; }                     \
     } while (0)
 
+// What a producer is asked for: the partial products of rows [r0,r1) -- `count` of them, the first at staging offset `base`
+// -- into stage[0 .. row_off[r1]-row_off[r0]).
+template <class T> struct PanelWork {
+    uint64_t r0, r1;
+    bool whole;                       // the rows are all rows of the product
+    uint64_t base, count;
+    Part<T> *stage;
+    // cells / qstage: the plan and the second buffer of the panel's direct rows, osp_kernels.h store_direct; null when the
+    // panel has none
+    const uint32_t *cells = nullptr; Part<T> *qstage = nullptr;
+    const HubArgs *hub = nullptr;     // cells and run table of the panel's hub rows, osp_kernels.h "HUB rows"; null when the panel has none
+    bool compact = false;             // the panel has gathered rows -- chunks nobody writes; osp_kernels.h, multiply_kernel IND
+    bool has_long = true;             // it has rows longer than a tile
+    bool desc_only = false;           // only rows written through cells are left to write
+    bool walk_all = false;            // walk all of A even so (a panel of mostly hub rows)
+};
 // Where the partial products of a panel come from.
 template <class T> struct Producer {
     virtual ~Producer() {}
-    // enqueue kernels that fill stage[0 .. row_off[r1]-row_off[r0]) for rows [r0,r1)
-    // (cells / qstage: the plan and the second buffer of the panel's direct rows, osp_kernels.h store_direct; null
-    // when the panel has none)
-    // (hub: cells and run table of the panel's hub rows, osp_kernels.h "HUB rows"; null when the panel has none)
-    // (compact: the panel has gathered rows -- chunks nobody writes; osp_kernels.h, multiply_kernel IND;
-    //  has_long: it has rows longer than a tile)
-    virtual void produce(uint64_t r0, uint64_t r1, bool whole, uint64_t base, uint64_t count,
-                         Part<T> *stage, PhaseTimer &tm, const uint32_t *cells = nullptr, Part<T> *qstage = nullptr,
-                         const HubArgs *hub = nullptr, bool compact = false, bool has_long = true, bool desc_only = false, bool walk_all = false) = 0;
+    virtual void produce(const PanelWork<T> &w, PhaseTimer &tm) = 0;   // enqueues the kernels that fill w.stage
 };
 
 // ---- rows of partial products -> merged rows -------------------------------------------------------
+// gathered short rows (osp_kernels.h, GatherArgs): their run table, the first run of every row, B (runs0 null: they are staged)
+template <class T> struct ShortRuns {
+    const RunDesc<T> *runs0 = nullptr; const uint32_t *rowfirst0 = nullptr; const uint32_t *b_colidx = nullptr; const T *b_vals = nullptr;
+};
 template <class T> struct MergeIO {
     Part<T> *stage;                      // partial products of rows [r0,r1), addressed row_off[r] - base
     const uint64_t *row_off; uint64_t r0, r1, base;
@@ -32,11 +44,7 @@ template <class T> struct MergeIO {
     const uint64_t *out_in; uint64_t *out_out;    // entries written before / after this call (device)
     ChunkTable<T> ct{};                           // row-wise variant: rows that fit a tile are computed in the tile kernel
     uint32_t *abort_word = nullptr;               // set by a look-back that gave up (merge_tiles_kernel): the product is an error
-    // gathered short rows (osp_kernels.h, GatherArgs): their run table, the first run of every row, B (null: they are staged)
-    const RunDesc<T> *runs0 = nullptr; const uint32_t *rowfirst0 = nullptr; const uint32_t *b_colidx = nullptr; const T *b_vals = nullptr;
-};
-template <class T> struct ShortRuns {
-    const RunDesc<T> *runs0 = nullptr; const uint32_t *rowfirst0 = nullptr; const uint32_t *b_colidx = nullptr; const T *b_vals = nullptr;
+    ShortRuns<T> sr{};
 };
 
 struct TilePlan {
@@ -640,7 +648,7 @@ static void merge_panel(Context *ctx, Result *res, PhaseTimer &tm, const MergeIO
         ntot = p0.ntiles + (p1.ntiles - nlong);   // (the scan's total: every long row's tiles but one -- no read-back)
         desc = sc.get<TileDesc>(ntot);
         tile_desc_kernel<(int)kCap><<<grid_for(p0.ntiles, 256), 256, 0, s>>>(p0.tile_rows, p0.ntiles, r1, io.row_off, base, 0u, j0, extra,
-                                                                           nlong, tb, pl.vcol0, pl.vcol1, desc, nullptr, nullptr, io.rowfirst0);
+                                                                           nlong, tb, pl.vcol0, pl.vcol1, desc, nullptr, nullptr, io.sr.rowfirst0);
         tile_desc_kernel<(int)kCap><<<grid_for(p1.ntiles, 256), 256, 0, s>>>(p1.tile_rows, p1.ntiles, nvirt, vrow_off, 0, 1u, j0, extra,
                                                                            nlong, tb, pl.vcol0, pl.vcol1, desc, pl.ga.runs ? pl.vrun_off : nullptr,
                                                                            pl.vrun_end);
@@ -648,7 +656,7 @@ static void merge_panel(Context *ctx, Result *res, PhaseTimer &tm, const MergeIO
     } else {
         desc = sc.get<TileDesc>(ntot);
         tile_desc_kernel<(int)kCap><<<grid_for(p0.ntiles, 256), 256, 0, s>>>(p0.tile_rows, p0.ntiles, r1, io.row_off, base, 0u, nullptr,
-                                                                           nullptr, 0u, nullptr, nullptr, nullptr, desc, nullptr, nullptr, io.rowfirst0);
+                                                                           nullptr, 0u, nullptr, nullptr, nullptr, desc, nullptr, nullptr, io.sr.rowfirst0);
     }
     uint64_t *tile_status = sc.get<uint64_t>(ntot);
     // ticket counters: one word (the kernel can also take several plus an arrival counter -- osp_kernels.h, take_ticket; measured in
@@ -664,10 +672,10 @@ static void merge_panel(Context *ctx, Result *res, PhaseTimer &tm, const MergeIO
         OSP_WITH_RA(ctx, merge_tiles_kernel<T, kMergeThreads, 64, TileCap<T>::value, kMergeMaxWgs, RA>
                     <<<std::min<uint32_t>(ntot, rw_grid), kMergeThreads, 0, s>>>(desc, ntot, lv, colbits, tile_status, ticket, io.out_in, io.c_col,
                                                                                  io.c_val, io.out_out, io.ct, nshards, io.abort_word));
-    } else if (pl.ga.runs || io.runs0) {   // the panel has gathered rows: the instantiation that forms their records
+    } else if (pl.ga.runs || io.sr.runs0) {   // the panel has gathered rows: the instantiation that forms their records
         GatherArgs<T> ga = pl.ga;
-        ga.runs0 = io.runs0;
-        if (io.runs0) { ga.b_colidx = io.b_colidx; ga.b_vals = io.b_vals; }
+        ga.runs0 = io.sr.runs0;
+        if (io.sr.runs0) { ga.b_colidx = io.sr.b_colidx; ga.b_vals = io.sr.b_vals; }
         const uint32_t merge_grid = ctx->cus * (uint32_t)merge_wgs_per_cu<T, kMergeThreads, TileCap<T>::value>();
         OSP_WITH_RA(ctx, merge_tiles_kernel<T, kMergeThreads, 0, TileCap<T>::value, kMergeMaxWgs, RA, true>
                     <<<std::min<uint32_t>(ntot, merge_grid), kMergeThreads, 0, s>>>(desc, ntot, lv, colbits, tile_status, ticket, io.out_in, io.c_col,
@@ -748,17 +756,29 @@ struct PanelSink {
 };
 
 // ---- stages shared by both entry points: partial products of each row -> final CSR ----------------
-constexpr uint64_t kPartialsOnDevice = ~0ull;   // merge_pipeline's P: not read back yet, it is d_row_off[M_all]
+constexpr uint64_t kPartialsOnDevice = ~0ull;   // MergeRequest::P: not read back yet, it is row_off[M_all]
+template <class T> struct MergeRequest {
+    uint64_t M_all, N;
+    const uint64_t *row_off;            // (device) every row's offset into the staging, M_all + 1 of them
+    uint64_t P;                         // partial products of the output rows, or kPartialsOnDevice
+    uint64_t capacity;                  // cfg.partial_capacity (0: sized by the free memory)
+    // ---- optional ----
+    // output rows [r_lo, r_hi) only (row-sharded multi-GPU mode: A holds this rank's rows only, so the staging offsets start
+    // at 0 at r_lo and P is the shard's count)
+    uint64_t r_lo = 0, r_hi = ~0ull;
+    const PanelSink *sink = nullptr;    // streaming mode
+    const ChunkTable<T> *ct = nullptr;  // row-wise variant
+    const DirectSrc *ds = nullptr;      // direct rows
+    // ascending row ids inside (r_lo, r_hi): a panel never reaches across one of them -- the multi-GPU merge makes its
+    // panels end where the pieces it receives end (osp_multi.h)
+    const std::vector<uint64_t> *cuts = nullptr;
+    ShortRuns<T> short_runs{};          // gathered short rows
+};
 template <class T>
-static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_t M_all, uint64_t N,
-                           const uint64_t *d_row_off,
-                           uint64_t P, uint64_t cap_cfg, PhaseTimer &tm, uint64_t r_lo = 0, uint64_t r_hi = ~0ull,
-                           uint64_t off_lo = 0, const PanelSink *sink = nullptr, const ChunkTable<T> *ct = nullptr,
-                           const DirectSrc *ds = nullptr, const std::vector<uint64_t> *cuts = nullptr, const ShortRuns<T> *sr = nullptr) {
-    // cuts (optional, ascending row ids inside (r_lo, r_hi)): a panel never reaches across one of them -- the multi-GPU
-    // merge makes its panels end where the pieces it receives end (osp_multi.h)
-    // output rows [r_lo, r_hi) only (row-sharded multi-GPU mode); P = their partial products, off_lo = row_off[r_lo]
-    if (r_hi == ~0ull) r_hi = M_all;
+static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, PhaseTimer &tm, const MergeRequest<T> &rq) {
+    const uint64_t N = rq.N, r_lo = rq.r_lo, r_hi = rq.r_hi == ~0ull ? rq.M_all : rq.r_hi;
+    uint64_t P = rq.P;
+    const PanelSink *sink = rq.sink;
     const uint64_t M = r_hi - r_lo;
     res->info.M = M;
     res->info.row_begin = r_lo;
@@ -776,12 +796,12 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
     {
         Scratch us(ctx);
         uint64_t *ub_tmp = us.get<uint64_t>(scan_scratch_entries(M + 1));
-        if (P != 0) device_exclusive_scan<RowUpperBound, uint64_t>(RowUpperBound{d_row_off + r_lo, N}, M, ub, ub_tmp, s);
+        if (P != 0) device_exclusive_scan<RowUpperBound, uint64_t>(RowUpperBound{rq.row_off + r_lo, N}, M, ub, ub_tmp, s);
         if (P == 0) {
             cap_c = 0;
         } else if (P == kPartialsOnDevice) {   // the caller left the count of partial products on the device: one wait for both
             Gather g(s);
-            g.add(&P, d_row_off + M_all);
+            g.add(&P, rq.row_off + rq.M_all);
             g.add(&cap_c, (const uint64_t *)ub + M);
             g.wait();
             res->info.partials = P;
@@ -819,14 +839,14 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
     size_t free_b = 0, total_b = 0;
     OSP_HIP(hipMemGetInfo(&free_b, &total_b));
     free_b += ctx->pooled_bytes + (ctx->sibling ? ctx->sibling->pooled_bytes : 0);   // (what alloc() can free before it fails)
-    uint64_t cap = cap_cfg;
+    uint64_t cap = rq.capacity;
     // streaming: the panel's output buffer (at most one record per partial product) comes out of the same budget
     // what a staged partial product needs: its record in the staging buffer, for 9 of 10 another one in the second buffer,
     // and a few per cent for tile tables and the cells of the direct rows -- 2.0 record sizes; 2.6 budgets 30 % on top of
     // that (3.3 until round 3: R-MAT-22 mild ran as 4 panels, now 3: one panel's planning, launches and read-backs less)
     // (round 5, gathered rows: nothing is written for nine records of ten, but both buffers are still addressed by the rows'
     // positions -- allocated in full -- and the run table is sized by a bound: measured 2.25 record sizes per product; 2.5)
-    const double per_record = sink ? 3.7 : (ds && ds->gather) ? 2.5 : 2.6;
+    const double per_record = sink ? 3.7 : (rq.ds && rq.ds->gather) ? 2.5 : 2.6;
     if (cap == 0) cap = std::max<uint64_t>((uint64_t)(free_b * 0.85 / (per_record * E)), 1ull << 20);
     cap = std::min<uint64_t>(cap, 0xfffffff0ull);  // staging positions are u32
     if (ctx->env.verbose)
@@ -834,19 +854,19 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
                 (unsigned long long)M, (unsigned long long)N, (unsigned long long)P, (unsigned long long)cap_c, cap_c * E / 1e9,
                 free_b / 1e9, (unsigned long long)cap, cap * E / 1e9);
     std::vector<uint64_t> bounds{r_lo};  // absolute row ids
-    std::vector<uint64_t> boff{off_lo};  // row_off at the bounds (multi-panel only)
-    if (P <= cap && !(cuts && !cuts->empty())) {
+    std::vector<uint64_t> boff{0};  // row_off at the bounds (multi-panel only)
+    if (P <= cap && !(rq.cuts && !rq.cuts->empty())) {
         bounds.push_back(r_hi);
-        boff.push_back(off_lo + P);
+        boff.push_back(P);
     } else {
         // The panels' bounds are found on the device by one wave (round 5; until then all M + 1 row offsets came to the host:
         // 33 MB through a fresh vector, 6.5 ms of the headline product with the device idle): at most kMaxPanels of them, the
         // bounds and the offsets there in one small read-back.
         constexpr uint32_t kMaxPanels = 4096;
-        const uint32_t ncuts = cuts ? (uint32_t)cuts->size() : 0u;
+        const uint32_t ncuts = rq.cuts ? (uint32_t)rq.cuts->size() : 0u;
         uint64_t *d_b = sc.get<uint64_t>(2ull * (kMaxPanels + 1) + 2), *d_cuts = sc.get<uint64_t>(std::max<uint32_t>(ncuts, 1));
-        if (ncuts) copy_h2d(d_cuts, cuts->data(), ncuts * sizeof(uint64_t), s);
-        panel_bounds_kernel<<<1, kWave, 0, s>>>(d_row_off, r_lo, M, cap, d_cuts, ncuts, kMaxPanels, d_b);
+        if (ncuts) copy_h2d(d_cuts, rq.cuts->data(), ncuts * sizeof(uint64_t), s);
+        panel_bounds_kernel<<<1, kWave, 0, s>>>(rq.row_off, r_lo, M, cap, d_cuts, ncuts, kMaxPanels, d_b);
         std::vector<uint64_t> hb(2ull * (kMaxPanels + 1) + 2);
         copy_d2h(hb.data(), d_b, hb.size() * sizeof(uint64_t), s);
         const uint64_t np = hb[0], bad = hb[1];
@@ -856,11 +876,11 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
         for (uint64_t p = 1; p <= np; p++) { bounds.push_back(hb[2 + p]); boff.push_back(hb[2 + (kMaxPanels + 1) + p]); }
         boff[0] = hb[2 + (kMaxPanels + 1)];
     }
-    const bool all_rows = r_lo == 0 && r_hi == M_all;
+    const bool all_rows = r_lo == 0 && r_hi == rq.M_all;
     const uint32_t npanels = (uint32_t)bounds.size() - 1;
     res->info.panels = npanels;
     // staging offset of panel p's first row, and its number of partial products
-    auto panel_base = [&](uint32_t p) { return (npanels == 1) ? off_lo : boff[p]; };
+    auto panel_base = [&](uint32_t p) { return (npanels == 1) ? 0 : boff[p]; };
     auto panel_count = [&](uint32_t p) { return (npanels == 1) ? P : boff[p + 1] - boff[p]; };
     uint64_t max_panel = 0, max_rows_panel = 0;
     for (uint32_t p = 0; p < npanels; p++) {
@@ -896,18 +916,17 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
         const uint64_t r0 = bounds[p], r1 = bounds[p + 1];
         const uint64_t base = panel_base(p), count = panel_count(p);
         PlanPtr pl(new PanelPlan<T>(ctx));
+        std::optional<AuxScope> scope;
         if (beside) {
-            AuxScope scope(ctx);
+            scope.emplace(ctx);
             OSP_HIP(hipStreamWaitEvent(ctx->stream, ctx->aux_fork, 0));
-            tm.begin(PH_MERGE, ctx->stream);
-            plan_panel<T>(ctx, res, tm, *pl, d_row_off, r0, r1, base, count, colbits, ds);
-            tm.end(PH_MERGE);
+        }
+        tm.begin(PH_MERGE, ctx->stream);
+        plan_panel<T>(ctx, res, tm, *pl, rq.row_off, r0, r1, base, count, colbits, rq.ds);
+        tm.end(PH_MERGE);
+        if (beside) {
             OSP_HIP(hipEventRecord(ctx->aux_join, ctx->stream));
             res->info.plans_overlapped++;
-        } else {
-            tm.begin(PH_MERGE);
-            plan_panel<T>(ctx, res, tm, *pl, d_row_off, r0, r1, base, count, colbits, ds);
-            tm.end(PH_MERGE);
         }
         return pl;
     };
@@ -920,11 +939,13 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
         if (beside) { OSP_HIP(hipEventRecord(ctx->aux_fork, s)); ctx->fork_window = true; ctx->releases_in_fork_window = 0; }
         struct WindowEnd { Context *c; ~WindowEnd() { c->fork_window = false; } } window_end{ctx};
         tm.begin(PH_MUL);
-        bool column_major = count != 0 && !(sr && plan.p0.nlong == 0), desc_only = false;   // (short rows gathered, no long row: nothing is staged)
+        PanelWork<T> w{r0, r1, npanels == 1 && all_rows, base, count, stage, plan.cells, plan.qstage, plan.hub.cells ? &plan.hub : nullptr};
+        w.has_long = plan.p0.nlong != 0;
+        bool column_major = count != 0 && !(rq.short_runs.runs0 && plan.p0.nlong == 0);   // (short rows gathered, no long row: nothing is staged)
         if (count && plan.xjobbase && plan.xjobs_bound) {
             tm.begin(PH_EXPAND_K);
-            const RowSrc<T> src{ds->rowfirst, ds->off, ds->bs, ds->av_in_order ? nullptr : ds->perm, (const T *)ds->a_vals, ds->b_colidx, (const T *)ds->b_vals};
-            expand_rows_kernel<T><<<(unsigned)plan.xjobs_bound, kExpandThreads, 0, s>>>(plan.p0.long_rows, plan.p0.nlong, plan.xjobbase, d_row_off, base, src, stage);
+            const RowSrc<T> src{rq.ds->rowfirst, rq.ds->off, rq.ds->bs, rq.ds->av_in_order ? nullptr : rq.ds->perm, (const T *)rq.ds->a_vals, rq.ds->b_colidx, (const T *)rq.ds->b_vals};
+            expand_rows_kernel<T><<<(unsigned)plan.xjobs_bound, kExpandThreads, 0, s>>>(plan.p0.long_rows, plan.p0.nlong, plan.xjobbase, rq.row_off, base, src, stage);
             tm.end(PH_EXPAND_K);
             res->info.expand_launches++;
             res->info.expand_partials += plan.xpartials;
@@ -933,22 +954,22 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
         // stretched by the plan it shares the CUs with: 16 ms of the headline's three panels against 2 before -- and ms_merge
         // no longer does; no kernel phase of its own, as the split of records has none)
         if (count && plan.split_from_b && plan.split_beside) {
-            split_stretch_from_b<T>(ctx, s, plan, d_row_off, base, colbits);
+            split_stretch_from_b<T>(ctx, s, plan, rq.row_off, base, colbits);
             dbg_sync(s, "split: stretch rows, from B");
         }
         if (count && plan.expand_ok) {
             // what is left for the column-major multiply: rows written through cells -- hub rows, direct rows with an over-long range
-            desc_only = true;
+            w.desc_only = true;
             // (with every planned row gathered -- the default -- nothing can have been counted: no round trip)
             const uint32_t nw = (plan.nwritten && plan.may_write) ? d2h(plan.nwritten, s) : 0u;
             column_major = plan.hub.cells != nullptr || nw != 0 || (plan.mode_rows[kModeDirect] != 0 && plan.ga.runs == nullptr);   // (a panel whose run table would not fit 32 bits writes its direct rows)
         }
         // (the compacted multiply pays where few chunks are left to write; a panel whose hub rows hold a third of its products
         // walks all of A as before: Graph500 scale 22, 77 % in hub rows, 34.0 against 28-33 ms per launch)
-        const bool mostly_hub = plan.hub.cells != nullptr && plan.mode_partials[kModeStretch] * 3 >= count;
-        if (column_major && ds) ds->ensure_chunk_off(s);
-        if (column_major) prod.produce(r0, r1, npanels == 1 && all_rows, base, count, stage, tm, plan.cells, plan.qstage, plan.hub.cells ? &plan.hub : nullptr,
-                                       plan.ga.runs != nullptr && !mostly_hub, plan.p0.nlong != 0, desc_only, mostly_hub);
+        w.walk_all = plan.hub.cells != nullptr && plan.mode_partials[kModeStretch] * 3 >= count;
+        w.compact = plan.ga.runs != nullptr && !w.walk_all;
+        if (column_major && rq.ds) rq.ds->ensure_chunk_off(s);
+        if (column_major) prod.produce(w, tm);
         tm.end(PH_MUL);
         if (beside) {
             ctx->fork_window = false;
@@ -959,32 +980,39 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
             OSP_HIP(hipStreamWaitEvent(s, ctx->aux_join, 0));
         }
     };
+    // ---- streaming: one output buffer sized for the largest panel's bound, reused by every panel ----
+    int64_t *prow = nullptr;
+    uint64_t *cells = nullptr;  // [0] = 0 (entries before the panel), [1] = entries of the panel
+    uint64_t nnz_total = 0;
     if (sink) {
-        // ---- streaming: one output buffer sized for the largest panel's bound, reused by every panel ----
         std::vector<uint64_t> h_ub(npanels + 1);
         for (uint32_t p = 0; p <= npanels; p++) h_ub[p] = d2h(ub + (bounds[p] - r_lo), s);
         uint64_t max_out = 1;
         for (uint32_t p = 0; p < npanels; p++) max_out = std::max(max_out, h_ub[p + 1] - h_ub[p]);
         c_col = sc.get<uint32_t>(max_out);
         c_val = sc.get<T>(max_out);
-        int64_t *prow = sc.get<int64_t>(max_rows_panel + 1);
-        uint64_t *cells = sc.get<uint64_t>(2);  // [0] = 0 (entries before the panel), [1] = entries of the panel
-        uint64_t nnz_total = 0;
-        PlanPtr cur, nxt;
-        for (uint32_t p = 0; p < npanels; p++) {
-            const uint64_t r0 = bounds[p], r1 = bounds[p + 1];
-            const uint64_t base = panel_base(p);
-            if (!cur) cur = plan_one(p, false);
-            PanelPlan<T> &plan = *cur;
-            multiply_and_plan_next(p, plan, nxt);
-            tm.begin(PH_MERGE);
-            OSP_HIP(hipMemsetAsync(cells, 0, 2 * sizeof(uint64_t), s));
-            MergeIO<T> io{stage, d_row_off, r0, r1, base, prow - r0, c_col, c_val, cells, cells + 1};
-            if (ct) io.ct = *ct;
-            if (sr) { io.runs0 = sr->runs0; io.rowfirst0 = sr->rowfirst0; io.b_colidx = sr->b_colidx; io.b_vals = sr->b_vals; }
-            io.abort_word = abort_word;
-            merge_panel<T>(ctx, res, tm, io, colbits, plan);
-            tm.end(PH_MERGE);
+        prow = sc.get<int64_t>(max_rows_panel + 1);
+        cells = sc.get<uint64_t>(2);
+    }
+    // ---- the panel loop; resident: every panel appends to the result's arrays, one read-back at the end, then the tails ----
+    PlanPtr cur, nxt;
+    for (uint32_t p = 0; p < npanels; p++) {
+        const uint64_t r0 = bounds[p], r1 = bounds[p + 1];
+        // ---- plan (unless made beside the previous panel's multiply), multiply (or scatter of CSR parts) ----
+        if (!cur) cur = plan_one(p, false);
+        PanelPlan<T> &plan = *cur;
+        multiply_and_plan_next(p, plan, nxt);
+        // ---- merge ----
+        tm.begin(PH_MERGE);
+        if (sink) OSP_HIP(hipMemsetAsync(cells, 0, 2 * sizeof(uint64_t), s));
+        MergeIO<T> io{stage, rq.row_off, r0, r1, panel_base(p), sink ? prow - r0 : res->rowptr - r_lo, c_col, c_val,
+                      sink ? cells : out_nnz + p, sink ? cells + 1 : out_nnz + p + 1};
+        if (rq.ct) io.ct = *rq.ct;
+        io.sr = rq.short_runs;
+        io.abort_word = abort_word;
+        merge_panel<T>(ctx, res, tm, io, colbits, plan);
+        tm.end(PH_MERGE);
+        if (sink) {   // its size and the abort word come back, then the caller gets the panel
             uint64_t nnz_p = 0;
             uint32_t aflag = 0;
             { Gather g(s); g.add(&nnz_p, (const uint64_t *)cells + 1); g.add(&aflag, (const uint32_t *)abort_word); g.wait(); }  // synchronises: the panel is complete
@@ -994,35 +1022,16 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
             ctx->ensure_free(2ull << 30);  // the consumer needs room of its own
             if (sink->fn(&pd, sink->user)) throw Error(OSP_ERR_ARG, "panel callback returned non-zero");
             OSP_HIP(hipStreamSynchronize(s));  // whatever the callback queued on this stream reads the buffers
-            cur = std::move(nxt);
         }
-        res->info.nnz_c = nnz_total;
-        return;
-    }
-
-    PlanPtr cur, nxt;
-    for (uint32_t p = 0; p < npanels; p++) {
-        const uint64_t r0 = bounds[p], r1 = bounds[p + 1];
-        const uint64_t base = panel_base(p);
-        // ---- plan (unless made beside the previous panel's multiply), multiply (or scatter of CSR parts) ----
-        if (!cur) cur = plan_one(p, false);
-        PanelPlan<T> &plan = *cur;
-        multiply_and_plan_next(p, plan, nxt);
-        // ---- merge ----
-        tm.begin(PH_MERGE);
-        MergeIO<T> io{stage, d_row_off, r0, r1, base, res->rowptr - r_lo, c_col, c_val, out_nnz + p, out_nnz + p + 1};
-        if (ct) io.ct = *ct;
-        if (sr) { io.runs0 = sr->runs0; io.rowfirst0 = sr->rowfirst0; io.b_colidx = sr->b_colidx; io.b_vals = sr->b_vals; }
-        io.abort_word = abort_word;
-        merge_panel<T>(ctx, res, tm, io, colbits, plan);
-        tm.end(PH_MERGE);
         cur = std::move(nxt);
     }
-    uint64_t nnz_total = 0;
-    uint32_t aflag = 0;
-    { Gather g(s); g.add(&nnz_total, (const uint64_t *)out_nnz + npanels); g.add(&aflag, (const uint32_t *)abort_word); g.wait(); }
-    check_abort(aflag);
+    if (!sink) {
+        uint32_t aflag = 0;
+        { Gather g(s); g.add(&nnz_total, (const uint64_t *)out_nnz + npanels); g.add(&aflag, (const uint32_t *)abort_word); g.wait(); }
+        check_abort(aflag);
+    }
     res->info.nnz_c = nnz_total;
+    if (sink) return;
     // The arrays were sized by the bound sum_i min(U_i, N); a product that compresses leaves their tails unused.  Copying the
     // result into arrays of its exact size gives that memory back -- at the price of reading and writing all of C once more
     // (the cage15 shape: 5 of 48 ms for 11.6 GB of tails).  So the copy is made only where the tails are worth it: more than a
@@ -1051,61 +1060,74 @@ static void merge_pipeline(Context *ctx, Result *res, Producer<T> &prod, uint64_
 }
 
 // ---- outer-product producer ---------------------------------------------------------------------
-template <class T> struct OuterProducer : Producer<T> {
-    Context *ctx;
-    Result *res;
+// The operands of one product on the device, A restricted to its shard: what the symbolic phase and the producer read.
+template <class T> struct Shard {
     const int64_t *a_colptr; const uint32_t *a_rowidx; const T *a_vals;
     const int64_t *b_rowptr; const uint32_t *b_colidx; const T *b_vals;
-    uint64_t k0, k1; int64_t e0;
+    uint64_t K, nnz_b;
+    uint64_t k0, k1;        // the k shard: columns [k0, k1) of A
+    int64_t e0;             // A's first non-zero inside it ...
+    uint64_t nnz;           // ... and how many
+    uint64_t r_lo, r_hi;    // the row shard: output rows [r_lo, r_hi)
+};
+template <class T> struct OuterProducer : Producer<T> {
+    Context *ctx;
+    Result *res;            // counts the launches
+    Shard<T> sh;
     const uint64_t *chunk_off;   // (the planner of direct rows rewrites the entries of its chunks, panel by panel)
     int64_t *a_start; uint32_t *a_cnt; uint64_t *prod; uint64_t *prod_off; uint64_t *scan_tmp;
     bool nothing_staged = false;  // row-wise variant and no row is longer than a tile: the tile kernel does it all
     // panels with gathered rows: the list of A's entries whose chunks are written (null: not prepared -- such a panel walks all of A)
     uint32_t *kscan = nullptr, *kscan_tmp = nullptr, *elist = nullptr, *cscan = nullptr, *klist = nullptr;
-    uint64_t nnz = 0;
     bool short_gathered = false;  // the short rows are gathered (their chunks: kChunkSkip): a panel without long rows multiplies nothing
-    void produce(uint64_t r0, uint64_t r1, bool whole, uint64_t base, uint64_t count, Part<T> *stage,
-                 PhaseTimer &tm, const uint32_t *cells, Part<T> *qstage, const HubArgs *hub = nullptr, bool compact = false, bool has_long = true,
-                 bool desc_only = false, bool walk_all = false) override {
+    // The shard's operands and chunk offsets, and the per-column arrays of a panel (in `sc`); lists: the product gathers rows,
+    // so its panels list the entries of A whose chunks are still written.
+    void bind(Context *ctx_, Result *res_, Scratch &sc, const Shard<T> &sh_, const uint64_t *chunk_off_, bool lists = false) {
+        ctx = ctx_; res = res_; sh = sh_; chunk_off = chunk_off_;
+        const uint64_t nk = sh.k1 - sh.k0;
+        a_start = sc.get<int64_t>(nk); a_cnt = sc.get<uint32_t>(nk);
+        prod = sc.get<uint64_t>(nk); prod_off = sc.get<uint64_t>(nk + 1);
+        scan_tmp = sc.get<uint64_t>(scan_scratch_entries(nk));
+        if (!lists) return;
+        kscan = sc.get<uint32_t>(sh.nnz + 1);
+        kscan_tmp = sc.get<uint32_t>(scan_scratch_entries(std::max<uint64_t>(sh.nnz, nk) + 1));
+        elist = sc.get<uint32_t>(sh.nnz);
+        cscan = sc.get<uint32_t>(nk + 1);
+        klist = sc.get<uint32_t>(nk + 1);
+    }
+    // The instantiation that knows hub rows' descriptors (MODE 2), direct rows' (1) or neither (0); IND: it walks the list of
+    // A's entries whose chunks are written instead of all of A.
+    template <int MODE, bool IND> void launch(unsigned nblocks, const PanelWork<T> &w) {
+        multiply_kernel<T, MODE, IND><<<nblocks, kMulThreads, 0, ctx->stream>>>(
+            sh.a_vals, sh.b_colidx, sh.b_vals, sh.b_rowptr, chunk_off, sh.e0, a_start, a_cnt, prod_off, sh.k0, sh.k1 - sh.k0, w.count, w.base, w.stage,
+            MODE ? w.cells : nullptr, MODE ? w.qstage : nullptr, MODE == 2 ? *w.hub : HubArgs{}, IND ? elist : nullptr, IND ? klist : nullptr);
+    }
+    void produce(const PanelWork<T> &w, PhaseTimer &tm) override {
         if (nothing_staged) return;
-        if (short_gathered && !has_long) return;
+        if (short_gathered && !w.has_long) return;
         hipStream_t s = ctx->stream;
-        const uint64_t nk = k1 - k0;
-        const bool ind = (compact || short_gathered) && elist && nnz && !walk_all;
+        const uint64_t nk = sh.k1 - sh.k0, nnz = sh.nnz;
+        const bool ind = (w.compact || short_gathered) && elist && nnz && !w.walk_all;
         if (ind) {
-            const PanelKeepFlag keep{a_rowidx, chunk_off, e0, (uint32_t)r0, r1, desc_only ? 1u : 0u};
+            const PanelKeepFlag keep{sh.a_rowidx, chunk_off, sh.e0, (uint32_t)w.r0, w.r1, w.desc_only ? 1u : 0u};
             device_exclusive_scan<PanelKeepFlag, uint32_t>(keep, nnz, kscan, kscan_tmp, s);
             panel_keep_list_kernel<<<grid_for(nnz, 256), 256, 0, s>>>(keep, kscan, nnz, elist);
-            const PanelKeepColFlag kcf{a_colptr, e0, k0, kscan};
+            const PanelKeepColFlag kcf{sh.a_colptr, sh.e0, sh.k0, kscan};
             device_exclusive_scan<PanelKeepColFlag, uint32_t>(kcf, nk, cscan, kscan_tmp, s);
-            panel_keep_columns_kernel<<<grid_for(nk, 256), 256, 0, s>>>(a_colptr, b_rowptr, k0, nk, e0, kscan, cscan, a_start, a_cnt, prod, klist);
+            panel_keep_columns_kernel<<<grid_for(nk, 256), 256, 0, s>>>(sh.a_colptr, sh.b_rowptr, sh.k0, nk, sh.e0, kscan, cscan, a_start, a_cnt, prod, klist);
         } else {
-            panel_columns_kernel<<<grid_for(nk, 256), 256, 0, s>>>(a_colptr, a_rowidx, b_rowptr, k0, nk, (uint32_t)r0, r1,
-                                                                   whole ? 1 : 0, a_start, a_cnt, prod);
+            panel_columns_kernel<<<grid_for(nk, 256), 256, 0, s>>>(sh.a_colptr, sh.a_rowidx, sh.b_rowptr, sh.k0, nk, (uint32_t)w.r0, w.r1,
+                                                                   w.whole ? 1 : 0, a_start, a_cnt, prod);
         }
         device_exclusive_scan<LoadU64, uint64_t>(LoadU64{prod}, nk, prod_off, scan_tmp, s);
-        uint64_t nblocks = (count + kMulPerBlock - 1) / kMulPerBlock;
+        uint64_t nblocks = (w.count + kMulPerBlock - 1) / kMulPerBlock;
         if (ind) nblocks = std::min<uint64_t>(nblocks, (uint64_t)ctx->cus * 8);   // (strides over the slices: osp_kernels.h)
         dbg_sync(s, "panel columns + scan");
         tm.begin(PH_MUL_K);
-        if (ind && hub && hub->cells)
-            multiply_kernel<T, 2, true><<<(unsigned)nblocks, kMulThreads, 0, s>>>(a_vals, b_colidx, b_vals, b_rowptr, chunk_off, e0,
-                                                                                a_start, a_cnt, prod_off, k0, nk, count, base, stage, cells, qstage, *hub, elist, klist);
-        else if (ind && cells)
-            multiply_kernel<T, 1, true><<<(unsigned)nblocks, kMulThreads, 0, s>>>(a_vals, b_colidx, b_vals, b_rowptr, chunk_off, e0,
-                                                                                a_start, a_cnt, prod_off, k0, nk, count, base, stage, cells, qstage, HubArgs{}, elist, klist);
-        else if (ind)
-            multiply_kernel<T, 0, true><<<(unsigned)nblocks, kMulThreads, 0, s>>>(a_vals, b_colidx, b_vals, b_rowptr, chunk_off, e0,
-                                                                                a_start, a_cnt, prod_off, k0, nk, count, base, stage, nullptr, nullptr, HubArgs{}, elist, klist);
-        else if (hub && hub->cells)
-            multiply_kernel<T, 2><<<(unsigned)nblocks, kMulThreads, 0, s>>>(a_vals, b_colidx, b_vals, b_rowptr, chunk_off, e0,
-                                                                          a_start, a_cnt, prod_off, k0, nk, count, base, stage, cells, qstage, *hub);
-        else if (cells)
-            multiply_kernel<T, 1><<<(unsigned)nblocks, kMulThreads, 0, s>>>(a_vals, b_colidx, b_vals, b_rowptr, chunk_off, e0,
-                                                                          a_start, a_cnt, prod_off, k0, nk, count, base, stage, cells, qstage);
-        else
-            multiply_kernel<T, 0><<<(unsigned)nblocks, kMulThreads, 0, s>>>(a_vals, b_colidx, b_vals, b_rowptr, chunk_off, e0,
-                                                                          a_start, a_cnt, prod_off, k0, nk, count, base, stage, nullptr, nullptr);
+        const unsigned nb = (unsigned)nblocks;
+        if (w.hub && w.hub->cells) ind ? launch<2, true>(nb, w) : launch<2, false>(nb, w);
+        else if (w.cells) ind ? launch<1, true>(nb, w) : launch<1, false>(nb, w);
+        else ind ? launch<0, true>(nb, w) : launch<0, false>(nb, w);
         tm.end(PH_MUL_K);
         dbg_sync(s, "multiply");
         res->info.multiply_launches++;
@@ -1117,10 +1139,10 @@ template <class T> struct PartsProducer : Producer<T> {
     const int64_t *const *d_rowptrs; const uint32_t *const *d_colidxs; const T *const *d_valss;
     int nparts;
     const uint64_t *row_off;
-    void produce(uint64_t r0, uint64_t r1, bool, uint64_t base, uint64_t, Part<T> *stage, PhaseTimer &, const uint32_t *, Part<T> *, const HubArgs *, bool, bool, bool, bool) override {
-        const uint64_t nr = r1 - r0;
+    void produce(const PanelWork<T> &w, PhaseTimer &) override {
+        const uint64_t nr = w.r1 - w.r0;
         parts_scatter_kernel<T><<<grid_for(nr * kWave, 256), 256, 0, ctx->stream>>>(d_rowptrs, d_colidxs, d_valss, nparts,
-                                                                                    r0, r1, row_off, base, stage);
+                                                                                    w.r0, w.r1, row_off, w.base, w.stage);
     }
 };
 
@@ -1130,10 +1152,10 @@ template <class T> struct RecordPartsProducer : Producer<T> {
     int nparts;
     const uint64_t *row_off;
     const std::function<void(uint64_t, uint64_t)> *before = nullptr;   // called with the panel's rows before its records are read
-    void produce(uint64_t r0, uint64_t r1, bool, uint64_t base, uint64_t, Part<T> *stage, PhaseTimer &, const uint32_t *, Part<T> *, const HubArgs *, bool, bool, bool, bool) override {
-        if (before) (*before)(r0, r1);
-        const uint64_t nr = r1 - r0;
-        parts_scatter_rec_kernel<T><<<grid_for(nr * kWave, 256), 256, 0, ctx->stream>>>(d_rowptrs, d_recs, nparts, r0, r1, row_off, base, stage);
+    void produce(const PanelWork<T> &w, PhaseTimer &) override {
+        if (before) (*before)(w.r0, w.r1);
+        const uint64_t nr = w.r1 - w.r0;
+        parts_scatter_rec_kernel<T><<<grid_for(nr * kWave, 256), 256, 0, ctx->stream>>>(d_rowptrs, d_recs, nparts, w.r0, w.r1, row_off, w.base, w.stage);
     }
 };
 

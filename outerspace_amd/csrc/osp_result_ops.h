@@ -294,48 +294,19 @@ static void masked_impl(Context *ctx, Result *res, uint64_t M, uint64_t K, uint6
     EventPair ev_in, ev_k;
     fresh_info(res, M, K, N);   // (rank_atomic included)
 
-    const int64_t *a_colptr = to_device(sc, a_colptr_in, K + 1, space, s);
-    const int64_t *b_rowptr = to_device(sc, b_rowptr_in, K + 1, space, s);
-    const int64_t *m_rowptr = to_device(sc, m_rowptr_in, M + 1, space, s);
-    int64_t nnz_a, nnz_b, nnz_m;
-    if (space == OSP_HOST) {
-        nnz_a = a_colptr_in[K]; nnz_b = b_rowptr_in[K]; nnz_m = m_rowptr_in[M];
-    } else {
-        Gather g(s);
-        g.add(&nnz_a, a_colptr + K); g.add(&nnz_b, b_rowptr + K); g.add(&nnz_m, m_rowptr + M);
-        g.wait();
-    }
-    if (nnz_a < 0 || nnz_b < 0 || nnz_m < 0) throw Error(OSP_ERR_ARG, "negative nnz in pointer array");
-    if ((uint64_t)nnz_a >= 0xffffffffull || (uint64_t)nnz_b >= 0xffffffffull || (uint64_t)nnz_m >= 0xffffffffull)
-        throw Error(OSP_ERR_ARG, "operands or masks with >= 2^32 non-zeros are not supported");
-    if (nnz_m && !m_colidx_in) throw Error(OSP_ERR_ARG, "null mask column array with a non-empty mask");
-    const uint32_t *a_rowidx = to_device(sc, a_rowidx_in, nnz_a, space, s);
-    const T *a_vals = to_device(sc, a_vals_in, nnz_a, space, s);
-    const uint32_t *b_colidx = to_device(sc, b_colidx_in, nnz_b, space, s);
-    const T *b_vals = to_device(sc, b_vals_in, nnz_b, space, s);
-    const uint32_t *m_colidx = to_device(sc, m_colidx_in, nnz_m, space, s);
+    CompressedIn ops[3] = {{a_colptr_in, a_rowidx_in, a_vals_in, sizeof(T), K, M, "A (CSC)"}, {b_rowptr_in, b_colidx_in, b_vals_in, sizeof(T), K, N, "B (CSR)"},
+                           {m_rowptr_in, m_colidx_in, nullptr, 0, M, N, "mask (CSR)"}};
+    operand_ptrs_in(sc, s, space, ops);
+    operand_nnz(s, space, ops, "negative nnz in pointer array", "operands or masks with >= 2^32 non-zeros are not supported");
+    if (ops[2].nnz && !m_colidx_in) throw Error(OSP_ERR_ARG, "null mask column array with a non-empty mask");
+    for (CompressedIn &o : ops) operand_entries_in(sc, s, space, o);
+    const int64_t *a_colptr = ops[0].ptr, *b_rowptr = ops[1].ptr, *m_rowptr = ops[2].ptr;
+    const uint32_t *a_rowidx = ops[0].idx, *b_colidx = ops[1].idx, *m_colidx = ops[2].idx;
+    const T *a_vals = (const T *)ops[0].val, *b_vals = (const T *)ops[1].val;
+    const int64_t nnz_a = ops[0].nnz, nnz_b = ops[1].nnz, nnz_m = ops[2].nnz;
     res->info.nnz_a = nnz_a;
     res->info.nnz_b = nnz_b;
-
-    if (cfg.validate) {
-        uint32_t *flags = sc.get<uint32_t>(3);
-        OSP_HIP(hipMemsetAsync(flags, 0, 3 * sizeof(uint32_t), s));
-        validate_ptr_kernel<<<grid_for(K + 1, 256), 256, 0, s>>>(a_colptr, K, nnz_a, flags);
-        validate_ptr_kernel<<<grid_for(K + 1, 256), 256, 0, s>>>(b_rowptr, K, nnz_b, flags + 1);
-        validate_ptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(m_rowptr, M, nnz_m, flags + 2);
-        uint32_t f[3] = {0, 0, 0};
-        { Gather g(s); for (int q = 0; q < 3; q++) g.add(&f[q], (const uint32_t *)flags + q); g.wait(); }
-        check_flags(f[0], "A (CSC)");
-        check_flags(f[1], "B (CSR)");
-        check_flags(f[2], "mask (CSR)");
-        if (nnz_a) validate_idx_kernel<<<grid_for(nnz_a, 256), 256, 0, s>>>(a_colptr, a_rowidx, K, nnz_a, M, flags);
-        if (nnz_b) validate_idx_kernel<<<grid_for(nnz_b, 256), 256, 0, s>>>(b_rowptr, b_colidx, K, nnz_b, N, flags + 1);
-        if (nnz_m) validate_idx_kernel<<<grid_for(nnz_m, 256), 256, 0, s>>>(m_rowptr, m_colidx, M, nnz_m, N, flags + 2);
-        { Gather g(s); for (int q = 0; q < 3; q++) g.add(&f[q], (const uint32_t *)flags + q); g.wait(); }
-        check_flags(f[0], "A (CSC)");
-        check_flags(f[1], "B (CSR)");
-        check_flags(f[2], "mask (CSR)");
-    }
+    if (cfg.validate) validate_operands(sc, s, ops);
 
     // ---- views: A by rows, B by columns ----
     OSP_HIP(hipEventRecord(ev_in.a, s));
@@ -532,16 +503,9 @@ static void apply_mask_impl(Context *ctx, const Result *in, Result *res, const i
     const uint32_t *m_colidx = space == OSP_HOST ? to_device(sc, m_colidx_in, (uint64_t)nnz_m, space, s) : m_colidx_in;
 
     if (validate) {
-        uint32_t *flags = sc.get<uint32_t>(1);
-        zero_async(s, {{flags, sizeof(uint32_t)}});
-        validate_ptr_kernel<<<grid_for(M + 1, 256), 256, 0, s>>>(m_rowptr, M, (uint64_t)nnz_m, flags);
-        launches += 2;
-        check_flags(d2h((const uint32_t *)flags, s), "mask (CSR)");
-        if (nnz_m) {
-            validate_idx_kernel<<<grid_for((uint64_t)nnz_m, 256), 256, 0, s>>>(m_rowptr, m_colidx, M, (uint64_t)nnz_m, N, flags);
-            launches++;
-            check_flags(d2h((const uint32_t *)flags, s), "mask (CSR)");
-        }
+        const CompressedIn mask[1] = {{m_rowptr, m_colidx, nullptr, 0, M, N, "mask (CSR)", nnz_m}};
+        validate_operands(sc, s, mask);
+        launches += nnz_m ? 3 : 2;   // (the flag's zeroing, the pointer check, the index check of a mask with entries)
     }
 
     res->info = in->info;
