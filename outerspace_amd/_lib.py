@@ -227,6 +227,23 @@ class BuildStats(_Stats):
     _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("long_runs", C.c_uint64), ("ms_total", C.c_float),
                 ("launches", C.c_uint32), ("readbacks", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
+ASSIGN_NO_ACCUM = -1  # OSP_ASSIGN_NO_ACCUM
+# the accum operators osp_csr_assign takes: the union's (None passes ASSIGN_NO_ACCUM: the region is replaced)
+ASSIGN_ACCUM_OPS = {name: EWISE_OPS[name] for name in ("plus", "times", "min", "max", "first", "second")}
+
+
+class Assign(_Stats):
+    """osp_assign_t"""
+    _fields_ = [("rows", C.c_void_p), ("n_rows", C.c_uint64), ("cols", C.c_void_p), ("n_cols", C.c_uint64), ("space", C.c_int32),
+                ("accum", C.c_int32), ("reserved", C.c_uint32 * 6)]
+
+
+class AssignStats(_Stats):
+    """osp_assign_stats_t"""
+    _fields_ = [("nnz_c", C.c_uint64), ("nnz_a", C.c_uint64), ("nnz_region", C.c_uint64), ("nnz_both", C.c_uint64),
+                ("nnz_out", C.c_uint64), ("ms_total", C.c_float), ("launches", C.c_uint32), ("readbacks", C.c_uint32),
+                ("reserved", C.c_uint32 * 5)]
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -312,6 +329,9 @@ EXTRACT_EXPORTS = ["osp_csr_extract"]
 
 # every symbol include/outerspace_spgemm_build.h declares
 BUILD_EXPORTS = ["osp_csr_build"]
+
+# every symbol include/outerspace_spgemm_assign.h declares
+ASSIGN_EXPORTS = ("osp_csr_assign",)
 
 _lib = None
 
@@ -406,6 +426,7 @@ def lib():
     L.osp_csr_sddmm.argtypes = [vp, C.POINTER(Semiring), i32, vp, vp, u64, i32, C.POINTER(vp), C.POINTER(SddmmStats)]
     L.osp_csr_extract.argtypes = [vp, C.POINTER(Extract), C.POINTER(vp), C.POINTER(ExtractStats)]
     L.osp_csr_build.argtypes = [vp, C.POINTER(Build), C.POINTER(vp), C.POINTER(BuildStats)]
+    L.osp_csr_assign.argtypes = [vp, vp, C.POINTER(Assign), C.POINTER(vp), C.POINTER(AssignStats)]
     _lib = L
     return L
 

@@ -37,6 +37,7 @@
 #include "../../include/outerspace_spgemm_sddmm.h"
 #include "../../include/outerspace_spgemm_extract.h"
 #include "../../include/outerspace_spgemm_build.h"
+#include "../../include/outerspace_spgemm_assign.h"
 #include "osp_internal.h"
 #include "osp_paths.h"
 #include "osp_kernels.h"
@@ -58,6 +59,7 @@
 #include "osp_sddmm.h"
 #include "osp_extract.h"
 #include "osp_build.h"
+#include "osp_assign.h"
 
 namespace osp {
 
@@ -1062,6 +1064,23 @@ int osp_csr_extract(osp_result_t in_, const osp_extract_t *ex, osp_result_t *out
         check_dims(ex->rows ? ex->n_rows : 0, 0, ex->cols ? ex->n_cols : 0);
         if (in->info.nnz_c >= 0xffffffffull) throw Error(OSP_ERR_ARG, "extract: results with >= 2^32 - 1 non-zeros are not supported");
     }, [&](auto tag, Result *res, osp_extract_stats_t *st) { extract_impl<decltype(tag)>(in->ctx, in, res, *ex, st); });
+}
+
+int osp_csr_assign(osp_result_t c_, osp_result_t a_, const osp_assign_t *as, osp_result_t *out, osp_assign_stats_t *stats) {
+    Result *c = (Result *)c_, *a = (Result *)a_;
+    return csr_op({c, a}, as != nullptr, out, stats, [&] {
+        check_space(as->space);
+        if (as->accum != OSP_ASSIGN_NO_ACCUM && (as->accum < OSP_EWISE_PLUS || as->accum > OSP_EWISE_SECOND))
+            throw Error(OSP_ERR_ARG, "assign: accum is OSP_ASSIGN_NO_ACCUM or one of PLUS, TIMES, MIN, MAX, FIRST, SECOND");
+        check_reserved(as->reserved, "assign");
+        if (a->ctx != c->ctx) throw Error(OSP_ERR_ARG, "assign: the operands belong to different contexts");
+        if (a->dtype != c->dtype) throw Error(OSP_ERR_ARG, "assign: the operands' dtypes differ");
+        check_dims(as->rows ? as->n_rows : 0, 0, as->cols ? as->n_cols : 0);
+        if (c->info.nnz_c >= 0xffffffffull || a->info.nnz_c >= 0xffffffffull)
+            throw Error(OSP_ERR_ARG, "assign: operands with >= 2^32 - 1 non-zeros are not supported");
+        if (a->info.M != (as->rows ? as->n_rows : c->info.M) || a->info.N != (as->cols ? as->n_cols : c->info.N))
+            throw Error(OSP_ERR_DIM, "assign: a's shape is not (the number of rows, the number of columns) of the region");
+    }, [&](auto tag, Result *res, osp_assign_stats_t *st) { assign_impl<decltype(tag)>(c->ctx, c, a, res, *as, st); });
 }
 
 int osp_csr_build(osp_context_t ctx_, const osp_build_t *b, osp_result_t *out, osp_build_stats_t *stats) {

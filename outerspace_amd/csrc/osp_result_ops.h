@@ -1,5 +1,5 @@
 // osp_result_ops.h -- the host side of the operations on results: what they share (the frame of a call, the two-pass and
-// bit-compaction helpers) and every *_impl from bias_relu to build, the conv stage and the masked product between them.  Part of
+// bit-compaction helpers) and every *_impl from bias_relu to assign, the conv stage and the masked product between them.  Part of
 // the ONE translation unit osp_api.hip (included there, inside namespace osp, after osp_pipeline.h and the ingest); the kernels
 // are in the headers the sections name.  DESIGN.md sections 8-20.
 #pragma once
@@ -1687,4 +1687,131 @@ static void build_impl(Context *ctx, Result *res, const osp_build_t &b, osp_buil
         fprintf(stderr, "[osp] build dup=%d vals=%d %llu x %llu nnz %llu -> %llu long_runs=%llu launches=%u readbacks=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
                 dup, b.vals != nullptr, (unsigned long long)M, (unsigned long long)N, (unsigned long long)nnz, (unsigned long long)nnz_out,
                 (unsigned long long)long_runs, launches, readbacks, st->ms_total, (unsigned long long)ctx->malloc_calls);
+}
+
+// ---- out = c with the region (rows, cols) assigned from a (osp_assign.h) ----
+template <class T, int OP = -1>
+static void launch_assign_write_a(int op, unsigned grid, hipStream_t s, const Result *a, const Result *c, const AssignMaps &mp, const uint64_t *bits,
+                                  const uint64_t *pos, Result *res) {
+    typedef ValueBits<T> V;
+    if constexpr (OP <= EW_SECOND) {
+        if (op == OP)
+            assign_write_a_kernel<T, OP><<<grid, kCompactThreads, 0, s>>>(a->rowptr, a->colidx, (const V *)a->vals, a->info.M, a->info.nnz_c, mp, c->rowptr,
+                                                                         c->colidx, (const V *)c->vals, bits, pos, res->rowptr, res->colidx,
+                                                                         (V *)res->vals);
+        else launch_assign_write_a<T, OP + 1>(op, grid, s, a, c, mp, bits, pos, res);
+    }
+}
+
+template <class T>
+static void assign_impl(Context *ctx, const Result *c, const Result *a, Result *res, const osp_assign_t &as, osp_assign_stats_t *st) {
+    typedef ValueBits<T> V;
+    OpFrame fr(ctx);
+    hipStream_t s = fr.s;
+    Scratch &sc = fr.sc;
+    const uint64_t M = c->info.M, N = c->info.N, nnz_c = c->info.nnz_c, nnz_a = a->info.nnz_c;
+    const bool has_rows = as.rows != nullptr, has_cols = as.cols != nullptr, accum = as.accum != OSP_ASSIGN_NO_ACCUM;
+    const uint64_t m = has_rows ? as.n_rows : M, n = has_cols ? as.n_cols : N;
+    const osp_memspace_t space = (osp_memspace_t)as.space;
+    res->info = c->info;
+    uint64_t nnz_region = 0, nnz_both = 0, nnz_out = 0;
+    uint32_t launches = 0, readbacks = 0;
+    if (M == 0 || nnz_c + nnz_a == 0) {
+        empty_result<T>(res, M, s);
+    } else if (m == 0 || n == 0 || (accum && nnz_a == 0)) {
+        copy_csr<T>(c, res, s);
+        nnz_out = nnz_c;
+    } else if (!has_rows && !has_cols && !accum) {
+        copy_csr<T>(a, res, s);   // (the region is all of c)
+        nnz_out = nnz_a;
+    } else {
+        // out's M row lengths are written by one thread each (assign_len_kernel)
+        if (M > kThreadEachMax) throw Error(OSP_ERR_ARG, "assign: c must have at most 2^32 - 256 rows (out's row lengths take one thread each)");
+        // (pool buffers are recycled, and OSP_POISON fills them: the error word, the counter and both maps are zeroed on every call)
+        const uint64_t nwc = (N + 63) / 64, nwx = (nnz_c + 63) / 64;
+        uint32_t *err = sc.get<uint32_t>(1);
+        unsigned long long *other = sc.get<unsigned long long>(1);
+        uint32_t *rmap = has_rows ? sc.get<uint32_t>(M) : nullptr;
+        uint64_t *colbits = has_cols ? sc.get<uint64_t>(nwc) : nullptr;
+        uint32_t *cpos = has_cols ? sc.get<uint32_t>(nwc + 1) : nullptr;   // (ranks of columns: below n <= 2^32 - 1)
+        zero_async(s, {{err, sizeof(uint32_t)}, {other, sizeof(unsigned long long)}, {rmap, has_rows ? M * sizeof(uint32_t) : 0},
+                       {colbits, has_cols ? nwc * sizeof(uint64_t) : 0}});
+        launches++;
+        AssignMaps mp{};
+        if (has_rows) {
+            mp.rows = to_device(sc, as.rows, m, space, s);
+            mp.rmap = rmap;
+            assign_rowmap_kernel<<<grid_for(m, 256), 256, 0, s>>>(mp.rows, m, M, rmap, err);
+            launches++;
+        }
+        if (has_cols) {
+            mp.cols = to_device(sc, as.cols, n, space, s);
+            mp.colbits = colbits;
+            mp.cpos = cpos;
+            uint32_t *tmp = sc.get<uint32_t>(scan_scratch_entries(nwc));
+            extract_colmap_kernel<<<grid_for(n, 256), 256, 0, s>>>(mp.cols, n, N, (unsigned long long *)colbits, nullptr, err);
+            launches += 1 + device_exclusive_scan<LoadPopc64, uint32_t>(LoadPopc64{colbits}, nwc, cpos, tmp, s);
+        }
+        // The flag pass reads the maps, which hold only what a good index wrote, and writes scratch alone: the error word
+        // travels with its count in the call's one read-back, and nothing of out is written before the lists are known good.
+        uint32_t bad = 0;
+        uint64_t n_other = 0;
+        const auto more = [&](Gather &ga) {
+            ga.add(&bad, (const uint32_t *)err);
+            ga.add(&n_other, (const uint64_t *)other);
+        };
+        BitScan x{nullptr, nullptr, 0, 0};
+        if (nnz_c) {
+            x = flag_and_scan(sc, nnz_c, s, [&](unsigned grid, uint64_t *bits) {
+                const auto flag = accum ? assign_flag_kernel<true> : assign_flag_kernel<false>;
+                flag<<<grid, kCompactThreads, 0, s>>>(c->rowptr, c->colidx, M, nnz_c, mp, a->rowptr, a->colidx, bits, other);
+            }, more);
+        } else {   // an embedding: no bit, and a scan of one zero word in the arrays' place
+            x.bits = sc.get<uint64_t>(nwx + 1);
+            x.pos = sc.get<uint64_t>(nwx + 2);
+            zero_async(s, {{x.bits, (nwx + 1) * sizeof(uint64_t)}, {x.pos, (nwx + 2) * sizeof(uint64_t)}});
+            x.launches = 1;
+            Gather ga(s);
+            more(ga);
+            ga.wait();
+        }
+        readbacks++;
+        launches += x.launches;
+        if (bad & kAssignBadRow) throw Error(OSP_ERR_ARG, "assign: a row index is not below the rows of c");
+        if (bad & kAssignRepeatedRow) throw Error(OSP_ERR_ARG, "assign: a row index is repeated");
+        if (bad & kAssignBadCol) throw Error(OSP_ERR_ARG, "assign: the columns are not strictly ascending and below the columns of c");
+        nnz_region = accum ? n_other : x.count;
+        nnz_both = accum ? x.count : n_other;
+        nnz_out = nnz_c + nnz_a - x.count;
+        alloc_rowptr(res, M);
+        alloc_entries<T>(res, nnz_out);
+        uint32_t *len = sc.get<uint32_t>(M);
+        uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(M));
+        assign_len_kernel<<<grid_for(M, 256), 256, 0, s>>>(c->rowptr, M, mp, a->rowptr, x.bits, x.pos, len);
+        launches += 1 + device_exclusive_scan<LoadU32As64, uint64_t>(LoadU32As64{len}, M, (uint64_t *)res->rowptr, tmp, s);
+        if (x.count < nnz_c) {   // (else c has no entry left of its own)
+            assign_write_c_kernel<V><<<grid_for(nnz_c, (unsigned)kCompactChunk), kCompactThreads, 0, s>>>(
+                c->rowptr, c->colidx, (const V *)c->vals, M, nnz_c, mp, a->rowptr, a->colidx, x.bits, x.pos, res->rowptr, res->colidx, (V *)res->vals);
+            launches++;
+        }
+        if (nnz_a) {
+            launch_assign_write_a<T>(as.accum, grid_for(nnz_a, (unsigned)kCompactChunk), s, a, c, mp, x.bits, x.pos, res);
+            launches++;
+        }
+    }
+    fr.finish(res, nnz_out);
+    *st = osp_assign_stats_t{};
+    st->nnz_c = nnz_c;
+    st->nnz_a = nnz_a;
+    st->nnz_region = nnz_region;
+    st->nnz_both = nnz_both;
+    st->nnz_out = nnz_out;
+    st->ms_total = res->info.ms_total;
+    st->launches = launches;
+    st->readbacks = readbacks;
+    if (ctx->env.verbose)
+        fprintf(stderr, "[osp] assign rows=%d cols=%d accum=%d %llu x %llu into %llu x %llu nnz %llu , %llu -> %llu (region %llu, both %llu) launches=%u readbacks=%u %.3f ms; pool misses so far: %llu hipMalloc calls\n",
+                has_rows, has_cols, as.accum, (unsigned long long)m, (unsigned long long)n, (unsigned long long)M, (unsigned long long)N,
+                (unsigned long long)nnz_c, (unsigned long long)nnz_a, (unsigned long long)nnz_out, (unsigned long long)nnz_region,
+                (unsigned long long)nnz_both, launches, readbacks, st->ms_total, (unsigned long long)ctx->malloc_calls);
 }

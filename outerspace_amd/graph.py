@@ -17,7 +17,9 @@ feature propagation on the product of a result with a dense matrix ``osp_csr_mxd
 dense-dense product ``osp_csr_sddmm`` (``edge_scores``, ``landmark_bounds``, ``factorize``), and a minimum spanning forest
 and a greedy weighted matching on mxv with the winner's column ``osp_csr_mxv_arg`` (``minimum_spanning_forest``,
 ``greedy_matching``), and BFS parent trees on the semiring product of two results AT a mask ``osp_csr_mxm_masked``
-(``bfs_parents``, at the end): the first traversal here that never forms the part of a product it would throw away.
+(``bfs_parents``): the first traversal here that never forms the part of a product it would throw away, and matrices put
+together from results with the assignment into a region ``osp_csr_assign`` (``bipartite_adjacency``, ``disjoint_union``,
+``replace_subgraph``, at the end).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -1971,3 +1973,75 @@ def bfs_parents(rows, cols, n=None, sources=(0,), *, directed=False, max_levels=
         return parent.cpu().numpy(), level.cpu().numpy(), info
     finally:
         _close_all(device, (A, F, P))
+
+
+# ---- a result assigned into a region of another (osp_csr_assign): block matrices, a subgraph put back -------------------------------
+def bipartite_adjacency(rows, cols, shape, weights=None, *, dup="plus", dtype=np.float64, ctx=None):
+    """The (m + n) x (m + n) adjacency matrix [[0, B], [B^T, 0]] of the bipartite graph with biadjacency edge list
+    (rows[e], cols[e]) in ``shape`` = (m, n), as a CSR result (``networkx.bipartite.from_biadjacency_matrix``: row vertex i
+    is vertex i, column vertex k is vertex m + k): B in one ``Context.build`` (repeated edges combined by ``dup``,
+    ``weights=None`` means 1), its transpose, and ``spgemm.block_matrix`` of the two.  The caller closes the result."""
+    ctx, device, dtype = _setup(dtype, ctx)
+    m, n = (int(d) for d in shape)
+    if m < 0 or n < 0:
+        raise ValueError("shape must be (m, n) with m, n >= 0")
+    _, _, r, c, w = _edges(rows, cols, None, device, weights, _torch_dtype(dtype))   # (no id below 0; the two sides have ranges of their own)
+    if r.numel() and (int(r.max().item()) >= m or int(c.max().item()) >= n):
+        raise ValueError(f"rows must lie in [0, {m}) and cols in [0, {n})")
+    B = _build_device(ctx, device, m, n, r, c, w, dup, dtype)
+    Bt = None
+    try:
+        Bt, _ = B.transpose()
+        return _S.block_matrix([[None, B], [Bt, None]])[0]
+    finally:
+        _close_all(device, [B, Bt])
+
+
+def disjoint_union(graphs, *, directed=False, dtype=np.float64, ctx=None):
+    """The disjoint union of a short list of graphs (rows, cols, n) (``networkx.disjoint_union_all``): the block-diagonal
+    adjacency matrix, graph g's vertex v renumbered ``offsets[g] + v``.  Every block is ``adjacency_matrix`` of its graph
+    (unit weights; ``directed=False``: symmetric, self loops dropped; ``directed=True``: self loops kept), the union is
+    ``spgemm.block_matrix`` of the diagonal grid: one pass over the growing result per graph.  Returns (result, offsets
+    int64 of len(graphs) + 1); the caller closes the result."""
+    ctx, device, dtype = _setup(dtype, ctx)
+    graphs = [tuple(g) for g in graphs]
+    blocks = []
+    try:
+        for r, c, n in graphs:
+            blocks.append(adjacency_matrix(r, c, n, directed=directed, loops=directed, dtype=dtype, ctx=ctx))
+        offsets = np.concatenate([[0], np.cumsum([b.shape[0] for b in blocks])]).astype(np.int64)
+        if not blocks:
+            return ctx.build(0, 0, [], [], dtype=dtype, space="host")[0], offsets
+        grid = [[b if i == k else None for k in range(len(blocks))] for i, b in enumerate(blocks)]
+        return _S.block_matrix(grid)[0], offsets
+    finally:
+        _close_all(device, blocks)
+
+
+def replace_subgraph(rows, cols, n, vertices, sub_rows, sub_cols, *, directed=False, dtype=np.float64, ctx=None):
+    """The graph with edges (rows[e], cols[e]) on vertices [0, n) with the subgraph that ``vertices`` induce REPLACED by the
+    graph with edges (sub_rows[e], sub_cols[e]), which is numbered by position in ``vertices`` (its vertex i is
+    ``vertices[i]``): the inverse of ``induced_subgraph``.  Both patterns are built as ``adjacency_matrix`` builds them
+    (``directed=False``: symmetric, self loops dropped; ``directed=True``: self loops kept) and the one is put into the
+    other on the GPU by ``A.assign(S, vertices, vertices)``: the edges inside ``vertices`` are removed, the given ones
+    added, every other edge stays.  ``vertices`` must be distinct and in [0, n) (else a ValueError) and may come in any
+    order.
+
+    Returns (u, v, info): the new graph's edges, int64, ascending by (u, v) -- once each with u < v for an undirected
+    graph, every edge u -> v for a directed one; info = the assign's stats and n."""
+    ctx, device, dtype = _setup(dtype, ctx)
+    A = S = out = None
+    try:
+        A = adjacency_matrix(rows, cols, n, directed=directed, loops=directed, dtype=dtype, ctx=ctx)
+        n = A.shape[0]
+        vs = _check_vertices(vertices, n)
+        S = adjacency_matrix(sub_rows, sub_cols, int(vs.size), directed=directed, loops=directed, dtype=dtype, ctx=ctx)
+        out, st = A.assign(S, vs, vs, None, "host")
+        info = dict(st, n=n)
+        if not directed:
+            u, v, _ = _upper_entries(out)
+            return u, v, info
+        rowptr, colidx, _ = out.to_host()
+        return np.repeat(np.arange(n, dtype=np.int64), np.diff(rowptr)), colidx.astype(np.int64), info
+    finally:
+        _close_all(device, [A, S, out])

@@ -596,6 +596,66 @@ class CsrResult:
             raise OspError(_lib.ERR_DIM, f"permute needs a square result (got {self.shape[0]} x {self.shape[1]})")
         return self.extract(perm, perm, space)
 
+    def assign(self, a, rows=None, cols=None, accum=None, space="device"):
+        """This result with the region ``rows x cols`` assigned from ``a``, as a new CSR result of this result's shape on the
+        device (``osp_csr_assign``), the inverse of ``extract``: ``a[i, k]`` stands at ``(rows[i], cols[k])``; a list given as
+        None is every row / column.  ``accum=None`` replaces the region (an entry of ``self`` inside it that ``a`` does not
+        hold is deleted); ``accum`` ``"plus" "times" "min" "max" "first" "second"`` combines: ``op(self, a)`` where both hold
+        a coordinate, the one value's bits where one does.  Outside the region the entries are ``self``'s, bit for bit.
+        ``a`` is a ``CsrResult`` of ``len(rows) x len(cols)``, this result's context and dtype (``self`` itself is allowed).
+        ``rows``: any order, distinct.  ``cols``: None or strictly ascending lists go to the library directly; any other
+        list is handled by composition -- with ``o = argsort(cols)``, ``a.extract(cols=o)`` is assigned with ``cols[o]`` --
+        and a repeated column then fails in the library as not strictly ascending.  Lists are as ``extract`` takes them.
+        Returns (result, stats dict): nnz_c, nnz_a, nnz_region, nnz_both, nnz_out, ms_total, launches, readbacks, composed
+        (the composed path: ms_total, launches and readbacks are the sums over its calls)."""
+        sp = _space(space)
+        acc = _lib.ASSIGN_NO_ACCUM if accum is None else _enum(_lib.ASSIGN_ACCUM_OPS, accum, "accum")
+        rp, nr, keep_r, _ = _index_arg(rows, space, "rows")
+        cp, nc, keep_c, ascending = _index_arg(cols, space, "cols")
+        self._same_family(a, context=False)   # (the context is not checked here: the library refuses a foreign operand)
+        sorted_a, st_x = None, None
+        if ascending is False:
+            if a.shape[1] != nc:
+                raise OspError(_lib.ERR_DIM, f"a must have {nc} columns (got {a.shape[1]})")
+            if space == "host":
+                w = np.asarray(keep_c, np.int64)
+                order = np.argsort(w, kind="stable")
+                by_rank = w[order]
+            else:
+                import torch
+                w = keep_c.long() & 0xffffffff
+                order = torch.argsort(w, stable=True)
+                order, by_rank = order.to(torch.int32).contiguous(), w[order].to(torch.int32).contiguous()   # (the low 32 bits)
+                torch.cuda.synchronize(keep_c.device)   # the library works on its own stream
+            cp, nc, keep_c, _ = _index_arg(by_rank, space, "cols")   # (a repeated column is the library's to refuse)
+            sorted_a, st_x = a.extract(cols=order, space=space)
+            a = sorted_a
+        spec = _lib.Assign()
+        spec.rows, spec.n_rows, spec.cols, spec.n_cols, spec.space, spec.accum = rp, nr, cp, nc, sp, acc
+        try:
+            out, stats = _call(self._ctx, "osp_csr_assign", self._h, a._h, C.byref(spec), stats=_lib.AssignStats(), keep=(keep_r, keep_c))
+        finally:
+            if sorted_a is not None:
+                sorted_a.close()
+        if st_x is not None:
+            for key in ("ms_total", "launches", "readbacks"):
+                stats[key] += st_x[key]
+        return out, dict(stats, composed=st_x is not None)
+
+    def embed(self, shape, rows=None, cols=None, space="device"):
+        """This result placed in an otherwise empty result of ``shape``: ``out[rows[i], cols[k]] = self[i, k]``, the inverse
+        of ``extract`` -- an empty result from ``Context.build`` with empty lists, then ``assign`` into it.  Returns
+        ``assign``'s (result, stats dict)."""
+        _space(space)
+        _index_arg(rows, space, "rows")
+        _index_arg(cols, space, "cols")
+        M, N = (int(d) for d in shape)
+        empty, _ = self._ctx.build(M, N, [], [], dtype=self.dtype, space="host")
+        try:
+            return empty.assign(self, rows, cols, None, space)
+        finally:
+            empty.close()
+
     def coo_rows_into(self, rows_device_ptr):
         """Row index of every entry into caller-owned DEVICE memory (nnz u32 values): with ``device_ptrs()[1:]`` the COO
         form ``Context.spgemm_coo_device`` takes (``osp_result_coo_rows``)."""
@@ -1107,3 +1167,66 @@ def spgemm_masked(A, B, mask, transpose_b=True, ctx=None, dtype=None):
     out = res.to_scipy()
     res.close()
     return out
+
+
+def block_grid(blocks):
+    """The checks of ``block_matrix``, which touch no handle: ``blocks`` as a rectangular grid of ``CsrResult`` or None, every
+    block row and block column with at least one block (``scipy.sparse.bmat`` refuses an all-None one too) and consistent
+    heights and widths, one context and dtype.  Returns (grid, row offsets, column offsets, the first block)."""
+    grid = [list(row) for row in blocks]
+    if not grid or not grid[0] or any(len(row) != len(grid[0]) for row in grid):
+        raise ValueError("blocks must be a non-empty rectangular grid")
+    heights, widths, first = [None] * len(grid), [None] * len(grid[0]), None
+    for i, row in enumerate(grid):
+        for k, b in enumerate(row):
+            if b is None:
+                continue
+            if not isinstance(b, CsrResult):
+                raise TypeError("a block must be a CsrResult or None")
+            first = b if first is None else first
+            if b._ctx is not first._ctx:
+                raise OspError(_lib.ERR_ARG, "the blocks belong to different contexts")
+            if b.dtype != first.dtype:
+                raise OspError(_lib.ERR_ARG, "the blocks' dtypes differ")
+            for sizes, at, got, what in ((heights, i, b.shape[0], "row"), (widths, k, b.shape[1], "column")):
+                if sizes[at] is None:
+                    sizes[at] = got
+                elif sizes[at] != got:
+                    raise ValueError(f"blocks[{i}][{k}] has {got} {what}s, its block {what} {sizes[at]}")
+    for sizes, what in ((heights, "row"), (widths, "column")):
+        if None in sizes:
+            raise ValueError(f"block {what} {sizes.index(None)} is all None: its size is unknown")
+    return grid, np.concatenate([[0], np.cumsum(heights)]).astype(np.int64), np.concatenate([[0], np.cumsum(widths)]).astype(np.int64), first
+
+
+def block_matrix(blocks):
+    """The matrix assembled from a grid of blocks, ``scipy.sparse.bmat``'s semantics for a grid (a list of rows) of
+    ``CsrResult`` or None: block (i, k) stands at the row offset of block row i and the column offset of block column k, None
+    is an empty block, sizes come from the blocks and must agree along every block row and column.  It starts from an
+    empty result (``Context.build`` with empty lists) and makes ONE ``assign`` per non-None block, with contiguous row and
+    column lists from the offsets (None where a block spans every row or column); intermediate results are closed.  The
+    cost is one pass over the growing result per block, so this is meant for small grids: [[0, B], [B^T, 0]], a few
+    diagonal blocks.  The blocks stay valid.  Returns (result, stats dict): blocks (assigned), nnz_out, ms_total, launches,
+    readbacks (sums over the calls)."""
+    grid, r0, c0, first = block_grid(blocks)
+    M, N = int(r0[-1]), int(c0[-1])
+    out, _ = first._ctx.build(M, N, [], [], dtype=first.dtype, space="host")
+    stats = {"blocks": 0, "nnz_out": 0, "ms_total": 0.0, "launches": 0, "readbacks": 0}
+    try:
+        for i, row in enumerate(grid):
+            for k, b in enumerate(row):
+                if b is None or b.shape[0] == 0 or b.shape[1] == 0:
+                    continue
+                rows = None if b.shape[0] == M else np.arange(r0[i], r0[i + 1])
+                cols = None if b.shape[1] == N else np.arange(c0[k], c0[k + 1])
+                nxt, st = out.assign(b, rows, cols, None, "host")
+                out.close()
+                out = nxt
+                stats["blocks"] += 1
+                for key in ("ms_total", "launches", "readbacks"):
+                    stats[key] += st[key]
+    except BaseException:
+        out.close()
+        raise
+    stats["nnz_out"] = out.nnz
+    return out, stats
