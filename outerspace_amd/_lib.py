@@ -244,6 +244,21 @@ class AssignStats(_Stats):
                 ("nnz_out", C.c_uint64), ("ms_total", C.c_float), ("launches", C.c_uint32), ("readbacks", C.c_uint32),
                 ("reserved", C.c_uint32 * 5)]
 
+# the operators osp_csr_kron takes: the mul operators of a semiring
+KRON_OPS = MXM_MUL_OPS
+KRON_LAUNCHES = 2  # OSP_KRON_LAUNCHES
+
+
+class Kron(_Stats):
+    """osp_kron_t"""
+    _fields_ = [("op", C.c_int32), ("reserved", C.c_uint32 * 7)]
+
+
+class KronStats(_Stats):
+    """osp_kron_stats_t"""
+    _fields_ = [("nnz_a", C.c_uint64), ("nnz_b", C.c_uint64), ("nnz_out", C.c_uint64), ("ms_total", C.c_float),
+                ("launches", C.c_uint32), ("readbacks", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -332,6 +347,9 @@ BUILD_EXPORTS = ["osp_csr_build"]
 
 # every symbol include/outerspace_spgemm_assign.h declares
 ASSIGN_EXPORTS = ("osp_csr_assign",)
+
+# every symbol include/outerspace_spgemm_kron.h declares
+KRON_EXPORTS = ("osp_csr_kron",)
 
 _lib = None
 
@@ -427,6 +445,7 @@ def lib():
     L.osp_csr_extract.argtypes = [vp, C.POINTER(Extract), C.POINTER(vp), C.POINTER(ExtractStats)]
     L.osp_csr_build.argtypes = [vp, C.POINTER(Build), C.POINTER(vp), C.POINTER(BuildStats)]
     L.osp_csr_assign.argtypes = [vp, vp, C.POINTER(Assign), C.POINTER(vp), C.POINTER(AssignStats)]
+    L.osp_csr_kron.argtypes = [vp, vp, C.POINTER(Kron), C.POINTER(vp), C.POINTER(KronStats)]
     _lib = L
     return L
 

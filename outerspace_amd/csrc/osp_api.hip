@@ -38,6 +38,7 @@
 #include "../../include/outerspace_spgemm_extract.h"
 #include "../../include/outerspace_spgemm_build.h"
 #include "../../include/outerspace_spgemm_assign.h"
+#include "../../include/outerspace_spgemm_kron.h"
 #include "osp_internal.h"
 #include "osp_paths.h"
 #include "osp_kernels.h"
@@ -60,6 +61,7 @@
 #include "osp_extract.h"
 #include "osp_build.h"
 #include "osp_assign.h"
+#include "osp_kron.h"
 
 namespace osp {
 
@@ -1081,6 +1083,23 @@ int osp_csr_assign(osp_result_t c_, osp_result_t a_, const osp_assign_t *as, osp
         if (a->info.M != (as->rows ? as->n_rows : c->info.M) || a->info.N != (as->cols ? as->n_cols : c->info.N))
             throw Error(OSP_ERR_DIM, "assign: a's shape is not (the number of rows, the number of columns) of the region");
     }, [&](auto tag, Result *res, osp_assign_stats_t *st) { assign_impl<decltype(tag)>(c->ctx, c, a, res, *as, st); });
+}
+
+int osp_csr_kron(osp_result_t a_, osp_result_t b_, const osp_kron_t *kr, osp_result_t *out, osp_kron_stats_t *stats) {
+    Result *a = (Result *)a_, *b = (Result *)b_;
+    static_assert(OSP_KRON_LAUNCHES == kKronLaunches, "the header states the kernels of the general path");
+    return csr_op({a, b}, kr != nullptr, out, stats, [&] {
+        if (kr->op < OSP_EWISE_PLUS || kr->op > OSP_EWISE_SECOND) throw Error(OSP_ERR_ARG, "kron: op is not one of TIMES, PLUS, MIN, MAX, FIRST, SECOND");
+        check_reserved(kr->reserved, "kron");
+        if (a->ctx != b->ctx) throw Error(OSP_ERR_ARG, "kron: the operands belong to different contexts");
+        if (a->dtype != b->dtype) throw Error(OSP_ERR_ARG, "kron: the operands' dtypes differ");
+        if (a->info.nnz_c >= 0xffffffffull || b->info.nnz_c >= 0xffffffffull)
+            throw Error(OSP_ERR_ARG, "kron: operands with >= 2^32 - 1 non-zeros are not supported");
+        // (every dimension of a result is at most 2^32 - 1: the products fit 64 bits)
+        check_dims(a->info.M * b->info.M, 0, a->info.N * b->info.N);
+        if (a->info.nnz_c * b->info.nnz_c >= 0xffffffffull)
+            throw Error(OSP_ERR_CAPACITY, "kron: the product would hold 2^32 - 1 entries or more");
+    }, [&](auto tag, Result *res, osp_kron_stats_t *st) { kron_impl<decltype(tag)>(a->ctx, a, b, res, *kr, st); });
 }
 
 int osp_csr_build(osp_context_t ctx_, const osp_build_t *b, osp_result_t *out, osp_build_stats_t *stats) {

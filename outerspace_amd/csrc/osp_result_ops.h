@@ -1,5 +1,5 @@
 // osp_result_ops.h -- the host side of the operations on results: what they share (the frame of a call, the two-pass and
-// bit-compaction helpers) and every *_impl from bias_relu to assign, the conv stage and the masked product between them.  Part of
+// bit-compaction helpers) and every *_impl from bias_relu to kron, the conv stage and the masked product between them.  Part of
 // the ONE translation unit osp_api.hip (included there, inside namespace osp, after osp_pipeline.h and the ingest); the kernels
 // are in the headers the sections name.  DESIGN.md sections 8-20.
 #pragma once
@@ -1814,4 +1814,54 @@ static void assign_impl(Context *ctx, const Result *c, const Result *a, Result *
                 has_rows, has_cols, as.accum, (unsigned long long)m, (unsigned long long)n, (unsigned long long)M, (unsigned long long)N,
                 (unsigned long long)nnz_c, (unsigned long long)nnz_a, (unsigned long long)nnz_out, (unsigned long long)nnz_region,
                 (unsigned long long)nnz_both, launches, readbacks, st->ms_total, (unsigned long long)ctx->malloc_calls);
+}
+
+// ---- out = a (x) b, the Kronecker product (osp_kron.h) ----
+template <class T, int OP = 0>
+static void launch_kron_entries(int op, unsigned grid, hipStream_t s, const Result *a, const Result *b, uint64_t nnz_out, Result *res) {
+    typedef ValueBits<T> V;
+    if constexpr (OP <= EW_SECOND) {
+        if (op == OP)
+            kron_entries_kernel<T, OP><<<grid, kKronThreads, 0, s>>>(a->rowptr, a->colidx, (const V *)a->vals, (uint32_t)a->info.M, b->rowptr, b->colidx,
+                                                                     (const V *)b->vals, (uint32_t)b->info.M, (uint32_t)b->info.N, b->info.nnz_c, nnz_out,
+                                                                     res->colidx, (V *)res->vals);
+        else launch_kron_entries<T, OP + 1>(op, grid, s, a, b, nnz_out, res);
+    }
+}
+
+// (the entry point has checked the shape of out and that nnz_a nnz_b is below 2^32 - 1)
+template <class T>
+static void kron_impl(Context *ctx, const Result *a, const Result *b, Result *res, const osp_kron_t &kr, osp_kron_stats_t *st) {
+    OpFrame fr(ctx);
+    hipStream_t s = fr.s;
+    const uint64_t M = a->info.M * b->info.M, N = a->info.N * b->info.N, nnz_a = a->info.nnz_c, nnz_b = b->info.nnz_c;
+    fresh_info(res, M, 0, N);
+    res->info.nnz_a = nnz_a; res->info.nnz_b = nnz_b;
+    uint64_t nnz_out = 0;
+    uint32_t launches = 0;
+    if (M == 0 || nnz_a == 0 || nnz_b == 0) {
+        empty_result<T>(res, M, s);
+    } else {
+        // the host knows the size of out: nothing is read back, and out's three arrays are the call's only allocations
+        nnz_out = nnz_a * nnz_b;
+        alloc_rowptr(res, M);
+        alloc_entries<T>(res, nnz_out);
+        kron_rowptr_kernel<<<std::min(grid_for(M + 1, 256), kKronRowBlocks), 256, 0, s>>>(a->rowptr, b->rowptr, M, (uint32_t)b->info.M, nnz_b, res->rowptr);
+        launch_kron_entries<T>(kr.op, grid_for(nnz_out, (unsigned)kKronChunk), s, a, b, nnz_out, res);
+        launches = kKronLaunches;
+    }
+    fr.finish(res, nnz_out);
+    res->info.partials = nnz_out;
+    *st = osp_kron_stats_t{};
+    st->nnz_a = nnz_a;
+    st->nnz_b = nnz_b;
+    st->nnz_out = nnz_out;
+    st->ms_total = res->info.ms_total;
+    st->launches = launches;
+    st->readbacks = 0;
+    if (ctx->env.verbose)
+        fprintf(stderr, "[osp] kron op=%d (%llu x %llu, nnz %llu) (x) (%llu x %llu, nnz %llu) -> %llu x %llu, nnz %llu launches=%u readbacks=0 %.3f ms; pool misses so far: %llu hipMalloc calls\n",
+                kr.op, (unsigned long long)a->info.M, (unsigned long long)a->info.N, (unsigned long long)nnz_a, (unsigned long long)b->info.M,
+                (unsigned long long)b->info.N, (unsigned long long)nnz_b, (unsigned long long)M, (unsigned long long)N, (unsigned long long)nnz_out,
+                launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
 }

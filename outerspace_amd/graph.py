@@ -19,7 +19,8 @@ and a greedy weighted matching on mxv with the winner's column ``osp_csr_mxv_arg
 ``greedy_matching``), and BFS parent trees on the semiring product of two results AT a mask ``osp_csr_mxm_masked``
 (``bfs_parents``): the first traversal here that never forms the part of a product it would throw away, and matrices put
 together from results with the assignment into a region ``osp_csr_assign`` (``bipartite_adjacency``, ``disjoint_union``,
-``replace_subgraph``, at the end).
+``replace_subgraph``), and product graphs and Kronecker powers on the Kronecker product of two results ``osp_csr_kron``
+(``tensor_product``, ``cartesian_product``, ``strong_product``, ``kronecker_power``, at the end).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -2045,3 +2046,105 @@ def replace_subgraph(rows, cols, n, vertices, sub_rows, sub_cols, *, directed=Fa
         return np.repeat(np.arange(n, dtype=np.int64), np.diff(rowptr)), colidx.astype(np.int64), info
     finally:
         _close_all(device, [A, S, out])
+
+
+# ---- the Kronecker product of two results (osp_csr_kron): product graphs, Kronecker powers ---------------------------------------------
+# A graph argument is (rows, cols, n), as in disjoint_union; vertex (u, v) of a product of g (n1 vertices) and h (n2) is
+# u * n2 + v.  The adjacency matrices are adjacency_matrix's (unit weights; directed=False: symmetric, self loops dropped;
+# directed=True: self loops kept).
+def _identity(ctx, device, n, dtype):
+    """The n x n identity as a CSR result, in one ``Context.build``."""
+    d = torch.arange(n, dtype=torch.int64, device=device)
+    return _build_device(ctx, device, n, n, d, d, None, "error", dtype)
+
+
+def _product_parts(g, h, directed, dtype, ctx):
+    (r1, c1, n1), (r2, c2, n2) = tuple(g), tuple(h)
+    A = adjacency_matrix(r1, c1, n1, directed=directed, loops=directed, dtype=dtype, ctx=ctx)
+    try:
+        return A, adjacency_matrix(r2, c2, n2, directed=directed, loops=directed, dtype=dtype, ctx=ctx)
+    except BaseException:
+        A.close()
+        raise
+
+
+def tensor_product(g, h, *, directed=False, dtype=np.float64, ctx=None):
+    """The tensor (Kronecker, categorical) product of two graphs (``networkx.tensor_product``): (u, v) ~ (u', v') when
+    u ~ u' in g AND v ~ v' in h -- ``A_g (x) A_h`` in one ``CsrResult.kron``.  Returns (result, info): the product's
+    adjacency matrix, which the caller closes, and the kron's stats with n (its vertices)."""
+    ctx, device, dtype = _setup(dtype, ctx)
+    A = B = None
+    try:
+        A, B = _product_parts(g, h, directed, dtype, ctx)
+        out, st = A.kron(B)
+        return out, dict(st, n=out.shape[0])
+    finally:
+        _close_all(device, [A, B])
+
+
+def cartesian_product(g, h, *, directed=False, dtype=np.float64, ctx=None):
+    """The Cartesian product of two graphs (``networkx.cartesian_product``): (u, v) ~ (u', v') when u = u' and v ~ v' in h,
+    or u ~ u' in g and v = v' -- ``A_g (x) I  union  I (x) A_h``, two ``CsrResult.kron`` with an identity from one
+    ``Context.build`` each, joined by ``union("plus")``.  Returns (result, info): the adjacency matrix, which the caller
+    closes; info = n, nnz, launches and ms_total of the three calls."""
+    ctx, device, dtype = _setup(dtype, ctx)
+    A = B = I1 = I2 = L = R = None
+    try:
+        A, B = _product_parts(g, h, directed, dtype, ctx)
+        I1, I2 = _identity(ctx, device, A.shape[0], dtype), _identity(ctx, device, B.shape[0], dtype)
+        L, s1 = A.kron(I2)
+        R, s2 = I1.kron(B)
+        out, s3 = L.union(R, "plus")
+        steps = (s1, s2, s3)
+        return out, {"n": out.shape[0], "nnz": out.nnz, "launches": sum(s["launches"] for s in steps),
+                     "ms_total": sum(s["ms_total"] for s in steps)}
+    finally:
+        _close_all(device, [A, B, I1, I2, L, R])
+
+
+def strong_product(g, h, *, directed=False, dtype=np.float64, ctx=None):
+    """The strong product of two graphs (``networkx.strong_product``): the union of ``tensor_product`` and
+    ``cartesian_product``, joined by ``union("plus")``.  Returns (result, info) as ``cartesian_product`` does."""
+    ctx, device, dtype = _setup(dtype, ctx)
+    T = Cp = None
+    try:
+        T, s1 = tensor_product(g, h, directed=directed, dtype=dtype, ctx=ctx)
+        Cp, s2 = cartesian_product(g, h, directed=directed, dtype=dtype, ctx=ctx)
+        out, s3 = T.union(Cp, "plus")
+        steps = (s1, s2, s3)
+        return out, {"n": out.shape[0], "nnz": out.nnz, "launches": sum(s["launches"] for s in steps),
+                     "ms_total": sum(s["ms_total"] for s in steps)}
+    finally:
+        _close_all(device, [T, Cp])
+
+
+def kronecker_power(rows, cols, n, k, *, directed=False, loops=True, dtype=np.float64, ctx=None):
+    """The k-th Kronecker power ``A (x) A (x) ... (x) A`` (k factors, folded from the left) of the adjacency matrix of the
+    graph with edges (rows[e], cols[e]) on vertices [0, n): the deterministic Kronecker graph of a seed, the model behind
+    R-MAT, whose vertices (n^k), entries (nnz^k), degrees (outer products of the seed's) and -- for a loop-free symmetric
+    seed -- triangles (6^(k-1) t^k) are known in closed form.  ``loops=True`` keeps the seed's self loops (a Kronecker
+    graph's usual seed has them).  Returns (result, info): the matrix, which the caller closes; info = n (= n^k), nnz
+    (= nnz^k), nnz_seed, ms_steps (the k - 1 products' times) and ms_total."""
+    ctx, device, dtype = _setup(dtype, ctx)
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    A = out = None
+    try:
+        A = adjacency_matrix(rows, cols, n, directed=directed, loops=loops, dtype=dtype, ctx=ctx)
+        out, ms, nnz_seed = A, [], A.nnz
+        for _ in range(k - 1):
+            nxt, st = out.kron(A)
+            if out is not A:
+                _close_all(device, [out])
+            out = nxt
+            ms.append(st["ms_total"])
+        if out is A:
+            A = None   # (k = 1: the seed itself is the result)
+        return out, {"n": out.shape[0], "nnz": out.nnz, "nnz_seed": nnz_seed, "ms_steps": ms, "ms_total": sum(ms)}
+    except BaseException:
+        if out is not None and out is not A:
+            out.close()
+        raise
+    finally:
+        _close_all(device, [A])

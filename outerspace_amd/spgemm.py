@@ -321,6 +321,21 @@ class CsrResult:
         return _call(self._ctx, "osp_csr_mxm_masked", self._h, other._h, mask._h, int(bool(complement)), C.byref(sr),
                      stats=_lib.MxmMaskedStats())
 
+    def kron(self, other, op="times"):
+        """The Kronecker product ``self (x) other`` as a new CSR result on the device (``osp_csr_kron``): with this result
+        ``mA x nA`` and ``other`` ``mB x nB`` it is ``(mA mB) x (nA nB)`` and holds ``op(self[ia, ja], other[ib, jb])`` at
+        ``(ia mB + ib, ja nB + jb)`` for every pair of stored entries, this result's value first.  ``op`` is ``"times" "plus"
+        "min" "max" "first" "second"``: one IEEE operation in the results' dtype or a copy of one operand's bits, as ``ewise``
+        defines them.  The product is structural (an explicit zero makes entries).  Its whole structure is closed form:
+        nothing is sorted, scanned or read back, and the only allocations are the result's arrays.  ``other`` is a
+        ``CsrResult`` of the same context and dtype (``self`` itself is allowed).  A product of 2^32 - 1 entries or more is
+        ``OspError(ERR_CAPACITY)``, a shape beyond a result's limits ``OspError(ERR_ARG)``.  Returns (result, stats dict):
+        nnz_a, nnz_b, nnz_out, ms_total, launches, readbacks."""
+        kr = _lib.Kron()
+        kr.op = _enum(_lib.KRON_OPS, op, "op")
+        self._same_family(other)
+        return _call(self._ctx, "osp_csr_kron", self._h, other._h, C.byref(kr), stats=_lib.KronStats())
+
     def transpose(self):
         """This CSR (M x N) transposed as a new N x M CSR result on the device (``osp_csr_transpose``): entry (j, i) exists
         iff this result has (i, j), columns ascend in every row, values keep their bits, and transposing twice gives the same
