@@ -396,8 +396,15 @@ int osp_spgemm_conv2d(osp_context_t ctx, osp_dtype_t dtype, uint64_t N, uint64_t
 /*
  * MaxPool2d(kernel (kh, kw), stride (stride_h, stride_w)) of a CSR activation `in` of N*H*W rows (pixel x channel): out
  * is (N*PH*PW) x C with PH = (H - kh) / stride_h + 1 (no padding, no dilation, floor mode), every entry the max over its
- * window with an absent entry counting as 0 -- F.max_pool2d on the densified input -- and the zeros dropped.  Same
+ * window with an absent entry counting as +0 -- F.max_pool2d on the densified input -- and the zeros dropped.  Same
  * contract as osp_csr_bias_relu: `in` stays valid, row pointers are exact, columns ascend.
+ * The rule, entry by entry (values are copied, never recomputed, so every output value has the bits of an input value):
+ *   - a window that holds a NaN gives a NaN wherever in the window it lies, as torch does; the entry is kept (NaN != 0) and
+ *     carries the bits of the window's FIRST NaN in tap order (ky outer, kx inner);
+ *   - otherwise the window's maximum, an absent tap counting as +0; a window whose maximum is a zero of either sign is
+ *     dropped (stored zeros included);
+ *   - so an all-present, all-negative window keeps its negative maximum, and one absent tap makes such a window's
+ *     maximum +0: dropped.
  */
 int osp_csr_maxpool2d(osp_result_t in, uint64_t N, uint64_t H, uint64_t W, uint32_t kh, uint32_t kw, uint32_t stride_h,
                       uint32_t stride_w, osp_result_t *out);

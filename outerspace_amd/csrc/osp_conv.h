@@ -95,7 +95,10 @@ __global__ void im2col_colptr_kernel(const uint64_t *__restrict__ ubase, const u
 
 // ---- max-pool of a CSR activation ----
 // Output row (n, py, px), every channel j: the max over the kh x kw window rows (n, py*sh + ky, px*sw + kx) of the input,
-// an absent entry counting as 0 -- F.max_pool2d on the densified input.  Zeros are dropped (what csr_matrix(dense) drops).
+// an absent entry counting as +0 -- F.max_pool2d on the densified input.  Zeros are dropped (what csr_matrix(dense) drops).
+// A window that holds a NaN gives a NaN wherever it lies, as torch does: the fold keeps the window's FIRST NaN in tap order
+// (ky outer, kx inner) -- values are copied, never recomputed, so the output carries that NaN's bits -- and the entry stays
+// (NaN != 0).  A window whose maximum is either zero is dropped; an all-present, all-negative window keeps its maximum.
 // One wave per output row, a lane per channel, 64 channels per step; pass 0 counts, pass 1 writes (bias_relu_rows_kernel).
 template <class T, bool WRITE>
 __global__ __launch_bounds__(256) void csr_maxpool_rows_kernel(const int64_t *__restrict__ rowptr, const uint32_t *__restrict__ col,
@@ -119,7 +122,8 @@ __global__ __launch_bounds__(256) void csr_maxpool_rows_kernel(const int64_t *__
                 for (uint32_t kx = 0; kx < kw; kx++) {
                     const uint64_t ir = row0 + (uint64_t)ky * W + kx;
                     const T w = csr_at(col, val, rowptr[ir], rowptr[ir + 1], (uint32_t)j);
-                    v = (ky == 0 && kx == 0) || w > v ? w : v;
+                    // the first tap starts the fold; after it a larger value or a NaN replaces v unless v is a NaN already
+                    v = (ky == 0 && kx == 0) || (v == v && !(w <= v)) ? w : v;
                 }
         }
         const bool keep = j < C && v != T(0);

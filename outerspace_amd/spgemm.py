@@ -202,7 +202,13 @@ class CsrResult:
         """MaxPool2d of this CSR read as a "pixel x channel" activation of N images of H x W pixels (row n*H*W + y*W + x):
         a new (N*PH*PW) x C CSR result on the device (``osp_csr_maxpool2d``).  An absent entry counts as 0 and zeros are
         dropped, so it equals ``F.max_pool2d`` on the densified input.  No padding, no dilation, floor mode; stride
-        defaults to the kernel size, as in torch."""
+        defaults to the kernel size, as in torch.
+
+        The rule: a window that holds a NaN gives a NaN wherever in the window it lies (as torch does); the entry is kept
+        (``NaN != 0``) and, values being copied and never recomputed, carries the bits of the window's first NaN in tap
+        order (``ky`` outer, ``kx`` inner).  Otherwise the entry is the window's maximum with an absent tap counting as
+        +0: a window whose maximum is a zero of either sign is dropped, and an all-present, all-negative window keeps its
+        negative maximum."""
         kh, kw = _pair(kernel_size)
         sh, sw = _pair(kernel_size if stride is None else stride)
         return _call(self._ctx, "osp_csr_maxpool2d", self._h, int(N), int(H), int(W), kh, kw, sh, sw)

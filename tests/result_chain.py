@@ -110,7 +110,8 @@ class ChainMismatch(AssertionError):
 # Bit patterns no result can be: NaNs with a payload of the driver's own (no input holds it, a copied NaN keeps its input's
 # payload and a computed one has the hardware's), and a position no row has.
 SENTINEL = {np.dtype(np.float32): np.uint32(0x7fc5eed5), np.dtype(np.float64): np.uint64(0x7ff85eed5eed5eed),
-            np.dtype(np.int64): np.int64(np.iinfo(np.int64).min + 1)}
+            np.dtype(np.int64): np.int64(np.iinfo(np.int64).min + 1),
+            np.dtype(np.uint32): np.uint32(0xfeed5eed)}        # (an index list: tests/test_gpu_conv.py; no row of its cases)
 MARGIN = 64                          # the fewest elements on either side of a caller's output
 
 

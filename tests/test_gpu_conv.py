@@ -287,3 +287,310 @@ def test_conv_error_paths():
     res.close()
     # the context still works after the failures
     assert ctx.im2col_device(np.float32, N, C, H, W, act.nnz, ptrs, S.conv2d_geometry(3)) > 0
+
+
+# ==== the conv stage against tests/conv_model.py, in bits ================================================================================
+# Operands carry tests/test_gpu_apply_mask.py's special values at every seventh entry; every output value is a copy, so values
+# are compared with ieee_model.assert_same_bits AND as whole bit patterns (a copied NaN keeps its payload).  The inputs are
+# tests/conv_cases.py's, which tests/test_conv_model_cpu.py runs against the model with planted defects.
+import os
+import subprocess
+import sys
+
+from outerspace_amd import _lib
+from outerspace_amd import spgemm as S
+from tests import conv_cases as cc
+from tests import conv_model as model
+from tests.ieee_model import assert_same_bits
+from tests.result_chain import Frame
+from tests.test_gpu_parity import assert_same
+
+DTYPES = [np.float32, np.float64]
+CHILD_TIMEOUT_S = 120   # a hang guard: a child starts Python, loads the library, creates a context and makes 16 small calls
+
+
+def _bits(v):
+    v = np.ascontiguousarray(v)
+    return v.view(np.uint32 if v.dtype == np.float32 else np.uint64)
+
+
+def _same_copies(got, want):
+    assert_same_bits(got, want)
+    assert np.array_equal(_bits(got), _bits(want))   # copies: a NaN keeps its sign and payload too
+
+
+@pytest.fixture(scope="module")
+def mctx(_ctx_shared):
+    yield _ctx_shared
+    _ctx_shared.trim()
+    torch.cuda.empty_cache()
+
+
+# ---- im2col: chunk and wave edges ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", DTYPES)
+def test_im2col_chunk_and_wave_edges(mctx, dt):
+    """Channels of exactly 0, 1, 63, 64, 65, 2047, 2048, 2049, 4096, 4097 and 0 entries, the COO shuffled."""
+    assert model.CHUNK == 2048 and model.WAVE == 64   # a change of kConvChunk fails here, not silently
+    assert cc.EDGE_COUNTS == [0, 1, 63, 64, 65, 2047, 2048, 2049, 4096, 4097, 0] and cc.EDGE_SHAPE == (2, 11, 33, 63)
+    N, C, H, W = cc.EDGE_SHAPE
+    x = cc.edge_input(dt)
+    assert np.bincount(x[1], minlength=C).tolist() == cc.EDGE_COUNTS and np.any(np.diff(x[1].astype(np.int64)) < 0)
+    for g in cc.EDGE_GEOMS:
+        want = model.im2col(N, C, H, W, x, g)
+        colptr, rows, vals, nnz = cc.im2col(mctx, dt, cc.EDGE_SHAPE, x, g)
+        assert nnz == len(want[1]) == colptr[-1]       # the count-only call reports the same nnz
+        assert np.array_equal(colptr, want[0])
+        assert np.array_equal(rows, want[1])
+        _same_copies(vals, want[2])
+
+
+# ---- im2col: caller-owned outputs ------------------------------------------------------------------------------------------------------------
+def _framed(fr):
+    """(the frame's buffer on the device as bits, the device address of the output inside it)."""
+    host = fr.new()
+    bits = torch.from_numpy(host.view(np.int32 if host.dtype.itemsize == 4 else np.int64)).to(DEV)
+    return bits, bits.data_ptr() + fr.pad * host.dtype.itemsize
+
+
+def _unframed(name, fr, bits):
+    """The output as a host array, the margins checked (result_chain.MarginDamaged) and no element left as the sentinel."""
+    b = bits.cpu().numpy().view(fr.sentinel.dtype)
+    fr.check(name, b)
+    inside = b[fr.pad:fr.pad + fr.n]
+    assert not np.any(inside == fr.sentinel), f"{name}: {int(np.sum(inside == fr.sentinel))} elements were never written"
+    return fr.interior(b).copy()
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_im2col_writes_exactly_its_outputs(mctx, dt):
+    N, C, H, W = cc.EDGE_SHAPE
+    x = cc.edge_input(dt)
+    ts = cc.upload_coo(x)
+    for g in cc.EDGE_GEOMS:
+        want = model.im2col(N, C, H, W, x, g)
+        frames = {"a_colptr": Frame((len(want[0]),), np.int64), "a_rowidx": Frame((len(want[1]),), np.uint32), "a_vals": Frame((len(want[2]),), dt)}
+        dev = {name: _framed(fr) for name, fr in frames.items()}
+        torch.cuda.synchronize(DEV)
+        nnz = mctx.im2col_device(dt, N, C, H, W, len(x[0]), cc.ptrs(ts), cc.lib_geom(g), out_ptrs=tuple(dev[k][1] for k in ("a_colptr", "a_rowidx", "a_vals")))
+        got = {name: _unframed(name, fr, dev[name][0]) for name, fr in frames.items()}
+        assert nnz == len(want[1])
+        assert np.array_equal(got["a_colptr"], want[0]) and np.array_equal(got["a_rowidx"], want[1])
+        _same_copies(got["a_vals"], want[2])
+
+
+# ---- im2col: index space ---------------------------------------------------------------------------------------------------------------------
+def _coo(pix, ch, dt, seed):
+    return np.array(pix, np.uint32), np.array(ch, np.uint32), cc.values(len(pix), dt, seed)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_im2col_at_the_limits_of_the_index_space(mctx, dt):
+    g = model.geom(1)
+    # pixels at 0, on both sides of bit 31 and the last one, in two channels
+    H, W = 65535, 65536
+    last = H * W - 1
+    x = _coo([last, 1 << 31, 0, (1 << 31) - 1, (1 << 31) + 1, last], [0, 0, 0, 1, 1, 1], dt, 3)
+    want = model.im2col(1, 2, H, W, x, g)
+    assert want[0].tolist() == [0, 3, 6] and want[1].tolist() == [0, 1 << 31, last, (1 << 31) - 1, (1 << 31) + 1, last]
+    colptr, rows, vals, nnz = cc.im2col(mctx, dt, (1, 2, H, W), x, g)
+    assert nnz == 6 and np.array_equal(colptr, want[0]) and np.array_equal(rows, want[1])
+    _same_copies(vals, want[2])
+    # the widest row that is accepted: its last pixel maps to row 2^32 - 3
+    W = (1 << 32) - 2
+    x = _coo([W - 1, 0, 1 << 31], [0, 0, 0], dt, 4)
+    want = model.im2col(1, 1, 1, W, x, g)
+    colptr, rows, vals, nnz = cc.im2col(mctx, dt, (1, 1, 1, W), x, g)
+    assert nnz == 3 and colptr.tolist() == [0, 3] and rows.tolist() == [0, 1 << 31, (1 << 32) - 3] == want[1].tolist()
+    _same_copies(vals, want[2])
+
+
+def test_im2col_refusals_at_the_limits(mctx):
+    dt = np.float32
+    ok = _coo([0, 5, 2], [0, 0, 1], dt, 5)
+    ts = cc.upload_coo(ok)
+
+    def works():
+        colptr, rows, vals, nnz = cc.im2col(mctx, dt, (1, 2, 2, 3), ok, model.geom(1))
+        assert nnz == 3 and colptr.tolist() == [0, 2, 3] and rows.tolist() == [0, 5, 2]
+        _same_copies(vals, ok[2][[0, 1, 2]][np.lexsort((ok[0], ok[1]))])
+
+    works()
+    refused = [((1, 2, 1, (1 << 32) - 1), model.geom(1), _lib.ERR_RANGE),                 # W = 2^32 - 1
+               ((1, 2, 1, (1 << 32) - 3), model.geom(1, 1, (0, 1)), _lib.ERR_RANGE)]      # N*OH*OW = 2^32 - 1 exactly
+    g = refused[1][1]
+    assert model.output_size((1 << 32) - 3, g.kw, g.sw, g.pw, g.dw) == (1 << 32) - 1 and model.output_size(1, g.kh, g.sh, g.ph, g.dh) == 1
+    for (N, C, H, W), g, status in refused:
+        with pytest.raises(S.OspError) as ei:
+            mctx.im2col_device(dt, N, C, H, W, 3, cc.ptrs(ts), cc.lib_geom(g))
+        assert ei.value.status == status
+        works()                                                                           # the context still works
+    dup = _coo([0, 5, 2, 5], [0, 0, 1, 0], dt, 6)
+    td = cc.upload_coo(dup)
+    with pytest.raises(S.OspError) as ei:
+        mctx.im2col_device(dt, 1, 2, 2, 3, 4, cc.ptrs(td), cc.lib_geom(model.geom(1)))
+    assert ei.value.status == _lib.ERR_DUPLICATE
+    with pytest.raises(ValueError):
+        model.im2col(1, 2, 2, 3, dup, model.geom(1))
+    works()
+
+
+# ---- conv2d: parity with the COO product -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("geometry", list(cc.CONV_GEOMS))
+def test_conv2d_equals_the_coo_product_of_the_models_unfold(ctx, dt, geometry):
+    """osp_spgemm_conv2d against osp_spgemm_coo on the model's unfold matrix and W, in the four formulations."""
+    g = cc.CONV_GEOMS[geometry]
+    N, C, H, W = cc.CONV_SHAPE
+    K = C * g.kh * g.kw
+    M = N * model.output_size(H, g.kh, g.sh, g.ph, g.dh) * model.output_size(W, g.kw, g.sw, g.pw, g.dw)
+    for OC in cc.CONV_OC:
+        x, w = cc.conv_input(dt, g, OC)
+        assert np.isnan(x[2]).any() and np.isnan(w[2]).any() and np.any(np.diff(w[1].astype(np.int64)) < 0)
+        colptr, rows, vals = model.im2col(N, C, H, W, x, g)
+        a = (rows, np.repeat(np.arange(K, dtype=np.uint32), np.diff(colptr)), vals)
+        ref = ctx.spgemm_coo(M, K, OC, a, (w[1], w[0], w[2]))                           # B = W^T
+        got = cc.conv2d(ctx, dt, cc.CONV_SHAPE, x, OC, w, g)
+        try:
+            assert got.shape == ref.shape == (M, OC) and got.nnz == ref.nnz > 0
+            assert_same(got, {"partials": ref.info["partials"], "rowptr": ref.rowptr, "colidx": ref.colidx, "vals": ref.vals})
+        finally:
+            got.close()
+            ref.close()
+
+
+# ---- max-pool ------------------------------------------------------------------------------------------------------------------------------------
+def _pool(mctx, csr, C, N, H, W, kernel, stride, a=None):
+    """Pools the uploaded ``a`` (or uploads csr) and compares with the model: structure exact, values as bits, info."""
+    want = model.maxpool(csr, C, N, H, W, kernel, stride)
+    own = a is None
+    a = cc.build(mctx, csr, C) if own else a
+    try:
+        out = a.maxpool2d(N, H, W, kernel, stride)
+        try:
+            assert out.dtype == csr[2].dtype.type and out.shape == (len(want[0]) - 1, C)
+            assert np.array_equal(out.rowptr, want[0]) and np.array_equal(out.colidx, want[1])
+            _same_copies(out.vals, want[2])
+            info = out.info
+            assert (info["M"], info["N"], info["row_begin"], info["row_end"], info["nnz_c"]) == (len(want[0]) - 1, C, 0, len(want[0]) - 1, len(want[1]))
+            assert out.nnz == len(want[1])
+        finally:
+            out.close()
+    finally:
+        if own:
+            a.close()
+    return want
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("C", cc.POOL_CHANNELS)
+def test_maxpool_over_channel_counts_and_geometries(mctx, dt, C):
+    assert cc.POOL_CHANNELS == (1, 63, 64, 65, 128, 129)
+    N, H, W = cc.POOL_SHAPE
+    csr = cc.pool_input(dt, C)
+    assert np.isnan(csr[2]).any() and np.any(_bits(csr[2]) == 0) and np.any((csr[2] == 0) & np.signbit(csr[2]))
+    a = cc.build(mctx, csr, C)
+    try:
+        assert np.array_equal(a.rowptr, csr[0]) and np.array_equal(a.colidx, csr[1]) and np.array_equal(_bits(a.vals), _bits(csr[2]))
+        for kernel, stride in cc.POOL_GEOMS:
+            want = _pool(mctx, csr, C, N, H, W, kernel, stride, a)
+            if (kernel, stride) == (2, None):   # all-negative full windows keep a negative maximum; one absent tap: dropped
+                lens = np.diff(want[0]).reshape(N, H // 2, W // 2)
+                assert lens[0, 0, 0] == lens[0, 1, 1] == C and lens[0, 2, 0] == lens[0, 3, 1] == 0
+                assert (want[2][:C] < 0).all()
+    finally:
+        a.close()
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("kh,kw", cc.NAN_WINDOWS)
+def test_maxpool_nan_at_every_tap_position(mctx, dt, kh, kw):
+    """A NaN at each tap of the window in turn gives that NaN's bits; of two NaNs the first in tap order."""
+    csr, N = cc.nan_position_input(dt, kh, kw)
+    want = _pool(mctx, csr, 3, N, kh, kw, (kh, kw), None)
+    nan_a, nan_b = (int(b) for b in _bits(cc.special(dt)[:2]))
+    bits = _bits(want[2]).reshape(N, 3)
+    T = kh * kw
+    assert [int(b) for b in bits[:T, 0]] == [nan_a] * T and [int(b) for b in bits[T:, 1]] == [nan_b] * T
+    assert [int(b) for b in bits[T:, 0]] == [nan_a] * (T - 1) + [nan_b]
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_maxpool_of_empty_inputs_and_of_many_channels(mctx, dt):
+    empty = (np.zeros(2 * 4 * 6 + 1, np.int64), np.zeros(0, np.uint32), np.zeros(0, dt))
+    _pool(mctx, empty, 5, 2, 4, 6, 2, None)
+    # a result of zero columns, from extract with an empty column list
+    a = cc.build(mctx, cc.pool_input(dt, 5), 5)
+    try:
+        none, _ = a.extract(None, np.zeros(0, np.uint32), space="host")
+        try:
+            N, H, W = cc.POOL_SHAPE
+            assert none.shape == (N * H * W, 0)
+            _pool(mctx, (np.zeros(N * H * W + 1, np.int64), np.zeros(0, np.uint32), np.zeros(0, dt)), 0, N, H, W, 2, None, none)
+        finally:
+            none.close()
+    finally:
+        a.close()
+    # C = 2^20 + 1 on a 2x2 image pooled to one row: the channels at both ends and around a wave step
+    C = (1 << 20) + 1
+    chans = np.array([0, 63, 64, (1 << 20) - 1, 1 << 20], np.uint32)
+    rows = [chans, chans[[0, 2, 4]], chans[[1, 3]], chans[[0, 4]]]
+    rowptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    csr = (rowptr, np.concatenate(rows), cc.values(int(rowptr[-1]), dt, 8))
+    want = _pool(mctx, csr, C, 1, 2, 2, 2, None)
+    assert len(want[0]) == 2 and 0 < len(want[1]) <= 5
+
+
+# ---- coo_rows ------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", DTYPES)
+def test_coo_rows_into_a_frame(mctx, dt):
+    for lengths in (cc.ROWS_LENGTHS, [0] * 7):
+        csr, ncol = cc.rows_input(dt, lengths)
+        a = cc.build(mctx, csr, ncol)
+        try:
+            want = model.coo_rows(csr[0])
+            assert np.array_equal(cc.coo_rows(a), want)
+            fr = Frame((len(want),), np.uint32)
+            bits, addr = _framed(fr)
+            torch.cuda.synchronize(DEV)
+            a.coo_rows_into(addr)
+            assert np.array_equal(_unframed("rows", fr, bits), want)
+        finally:
+            a.close()
+    assert sorted(set(cc.ROWS_LENGTHS)) == [0, 1, 3, 65, 129]
+
+
+# ---- the pool ---------------------------------------------------------------------------------------------------------------------------------------
+_state = {"digest": None, "stop": None}
+
+
+def test_the_slice_in_this_process(mctx):
+    _state["digest"] = cc.slice_digest(mctx)
+    assert _state["digest"][1] == len(DTYPES) * (2 * len(cc.EDGE_GEOMS) + 1 + len(cc.NAN_WINDOWS) + 1)
+
+
+def _child(mode):
+    if _state["stop"]:
+        pytest.skip(f"{_state['stop']}: nothing further is started on the GPU")
+    assert _state["digest"] is not None, "the in-process run did not finish: no digest to compare with"
+    env = dict(os.environ)
+    env[mode] = "1"
+    try:
+        r = subprocess.run([sys.executable, "-m", "tests.conv_cases"], cwd=cc.ROOT, env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT_S)
+    except subprocess.TimeoutExpired:
+        _state["stop"] = f"the child under {mode} hung"
+        raise
+    if r.returncode != 0:
+        _state["stop"] = f"the child under {mode} ended with status {r.returncode}"
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    line = [x for x in r.stdout.splitlines() if x.startswith("CONV_SLICE ")]
+    assert line == [f"CONV_SLICE {_state['digest'][0]} calls={_state['digest'][1]}"], r.stdout[-2000:]
+    return r
+
+
+def test_the_slice_in_a_child_under_poison():
+    _child("OSP_POISON")
+
+
+def test_the_slice_in_a_child_under_guard():
+    r = _child("OSP_GUARD")
+    assert "[osp] OSP_GUARD:" not in r.stderr, r.stderr[-4000:]
