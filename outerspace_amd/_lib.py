@@ -259,6 +259,23 @@ class KronStats(_Stats):
     _fields_ = [("nnz_a", C.c_uint64), ("nnz_b", C.c_uint64), ("nnz_out", C.c_uint64), ("ms_total", C.c_float),
                 ("launches", C.c_uint32), ("readbacks", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
+SELECT_K_ORDERS = {"largest": 0, "smallest": 1, "random": 2}  # osp_select_k_order_t
+
+
+class SelectK(_Stats):
+    """osp_select_k_t"""
+    _fields_ = [("order", C.c_int32), ("k", C.c_uint32), ("seed", C.c_uint64), ("reserved", C.c_uint32 * 8)]
+
+
+class SelectKStats(_Stats):
+    """osp_select_k_stats_t"""
+    _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("rows_capped", C.c_uint64), ("rows_long", C.c_uint64),
+                ("ms_total", C.c_float), ("launches", C.c_uint32), ("readbacks", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
+# capped rows of a k-select longer than this are selected by a workgroup, shorter ones by one wave (kSelectKLongMin, osp_select_k.h)
+SELECT_K_LONG_MIN = 2048
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -350,6 +367,9 @@ ASSIGN_EXPORTS = ("osp_csr_assign",)
 
 # every symbol include/outerspace_spgemm_kron.h declares
 KRON_EXPORTS = ("osp_csr_kron",)
+
+# every symbol include/outerspace_spgemm_select_k.h declares
+SELECT_K_EXPORTS = ("osp_csr_select_k",)
 
 _lib = None
 
@@ -446,6 +466,7 @@ def lib():
     L.osp_csr_build.argtypes = [vp, C.POINTER(Build), C.POINTER(vp), C.POINTER(BuildStats)]
     L.osp_csr_assign.argtypes = [vp, vp, C.POINTER(Assign), C.POINTER(vp), C.POINTER(AssignStats)]
     L.osp_csr_kron.argtypes = [vp, vp, C.POINTER(Kron), C.POINTER(vp), C.POINTER(KronStats)]
+    L.osp_csr_select_k.argtypes = [vp, C.POINTER(SelectK), C.POINTER(vp), C.POINTER(SelectKStats)]
     _lib = L
     return L
 

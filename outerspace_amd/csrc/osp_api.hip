@@ -39,6 +39,7 @@
 #include "../../include/outerspace_spgemm_build.h"
 #include "../../include/outerspace_spgemm_assign.h"
 #include "../../include/outerspace_spgemm_kron.h"
+#include "../../include/outerspace_spgemm_select_k.h"
 #include "osp_internal.h"
 #include "osp_paths.h"
 #include "osp_kernels.h"
@@ -62,6 +63,7 @@
 #include "osp_build.h"
 #include "osp_assign.h"
 #include "osp_kron.h"
+#include "osp_select_k.h"
 
 namespace osp {
 
@@ -1100,6 +1102,15 @@ int osp_csr_kron(osp_result_t a_, osp_result_t b_, const osp_kron_t *kr, osp_res
         if (a->info.nnz_c * b->info.nnz_c >= 0xffffffffull)
             throw Error(OSP_ERR_CAPACITY, "kron: the product would hold 2^32 - 1 entries or more");
     }, [&](auto tag, Result *res, osp_kron_stats_t *st) { kron_impl<decltype(tag)>(a->ctx, a, b, res, *kr, st); });
+}
+
+int osp_csr_select_k(osp_result_t in_, const osp_select_k_t *sk, osp_result_t *out, osp_select_k_stats_t *stats) {
+    Result *in = (Result *)in_;
+    return csr_op({in}, sk != nullptr, out, stats, [&] {
+        if (sk->order < OSP_SELECT_K_LARGEST || sk->order > OSP_SELECT_K_RANDOM) throw Error(OSP_ERR_ARG, "select_k: order is not one of osp_select_k_order_t");
+        if (sk->k == 0) throw Error(OSP_ERR_ARG, "select_k: k must be at least 1");
+        check_reserved(sk->reserved, "select_k");
+    }, [&](auto tag, Result *res, osp_select_k_stats_t *st) { select_k_impl<decltype(tag)>(in->ctx, in, res, *sk, st); });
 }
 
 int osp_csr_build(osp_context_t ctx_, const osp_build_t *b, osp_result_t *out, osp_build_stats_t *stats) {

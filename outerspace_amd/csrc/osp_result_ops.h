@@ -1865,3 +1865,88 @@ static void kron_impl(Context *ctx, const Result *a, const Result *b, Result *re
                 (unsigned long long)b->info.N, (unsigned long long)nnz_b, (unsigned long long)M, (unsigned long long)N, (unsigned long long)nnz_out,
                 launches, st->ms_total, (unsigned long long)ctx->malloc_calls);
 }
+
+// ---- the row-wise k-select of a CSR result (osp_select_k.h) ----
+template <class F, int ORDER = 0>
+static void with_select_k_order(int order, F &&body) {
+    if constexpr (ORDER < SELK_ORDERS) {
+        if (order == ORDER) body(std::integral_constant<int, ORDER>{});
+        else with_select_k_order<F, ORDER + 1>(order, std::forward<F>(body));
+    }
+}
+
+template <class T>
+static void select_k_impl(Context *ctx, const Result *in, Result *res, const osp_select_k_t &sk, osp_select_k_stats_t *st) {
+    OpFrame fr(ctx);
+    hipStream_t s = fr.s;
+    Scratch &sc = fr.sc;
+    const uint64_t M = in->info.M, N = in->info.N, nnz_in = in->info.nnz_c;
+    const uint32_t k = sk.k;
+    res->info = in->info;
+    uint64_t nnz = nnz_in, n_wave = 0, n_long = 0;
+    uint32_t launches = 0, readbacks = 0;
+    if (nnz_in == 0) {
+        empty_result<T>(res, M, s);
+    } else if (k >= std::min(N, nnz_in)) {
+        copy_csr<T>(in, res, s);   // no row can hold more than k entries: `in` itself, and nothing to ask the device
+    } else {
+        with_select_k_order(sk.order, [&](auto order_tag) {
+            constexpr int ORDER = decltype(order_tag)::value;
+            typedef typename SelectKKey<T, ORDER>::type K;
+            const uint64_t seed = select_k_mix(sk.seed + 0x9E3779B97F4A7C15ull);
+            const T *val = (const T *)in->vals;
+            // ---- classes: at most nnz / (k + 1) rows are longer than k ----
+            unsigned long long *counters = (unsigned long long *)sc.get<uint64_t>(SELK_COUNTERS);
+            uint32_t *wave_rows = sc.get<uint32_t>(nnz_in / ((uint64_t)k + 1) + 1);
+            uint32_t *long_rows = sc.get<uint32_t>(nnz_in / ((uint64_t)std::max(k, kSelectKLongMin) + 1) + 1);
+            K *thr = (K *)sc.get<uint64_t>(M);
+            uint32_t *tie = sc.get<uint32_t>(M);
+            OSP_HIP(hipMemsetAsync(counters, 0, SELK_COUNTERS * sizeof(uint64_t), s));
+            select_k_classify_kernel<K><<<grid_for(M, 256), 256, 0, s>>>(in->rowptr, M, k, kSelectKLongMin, wave_rows, long_rows, counters, thr, tie);
+            launches++;
+            {
+                Gather g(s);
+                g.add(&n_wave, (const uint64_t *)counters + SELK_NWAVE);
+                g.add(&n_long, (const uint64_t *)counters + SELK_NLONG);
+                g.wait();
+                readbacks++;
+            }
+            if (n_wave + n_long == 0) {
+                copy_csr<T>(in, res, s);
+                return;
+            }
+            // ---- the pair of every capped row ----
+            constexpr uint64_t kSlice = 1ull << 30;   // rows per launch (grid limit)
+            for (uint64_t r0 = 0; r0 < n_wave; r0 += kSlice) {
+                select_k_threshold_kernel<T, ORDER, kWave><<<(unsigned)std::min(kSlice, n_wave - r0), kWave, 0, s>>>(in->rowptr, in->colidx, val, wave_rows + r0,
+                                                                                                                 k, seed, thr, tie);
+                launches++;
+            }
+            if (n_long) {
+                select_k_threshold_kernel<T, ORDER, kSelectKLongThreads><<<(unsigned)n_long, kSelectKLongThreads, 0, s>>>(in->rowptr, in->colidx, val, long_rows,
+                                                                                                                      k, seed, thr, tie);
+                launches++;
+            }
+            // ---- flag, scan, write ----
+            const Compacted c = compact_by_bits<T>(sc, in, res, s, [&](unsigned nchunks, uint64_t *bits) {
+                select_k_flag_kernel<T, ORDER><<<nchunks, kCompactThreads, 0, s>>>(in->rowptr, in->colidx, val, M, nnz_in, seed, thr, tie, bits);
+            });
+            readbacks++;
+            launches += c.launches;
+            nnz = c.nnz;
+        });
+    }
+    fr.finish(res, nnz);
+    *st = osp_select_k_stats_t{};
+    st->nnz_in = nnz_in;
+    st->nnz_out = nnz;
+    st->rows_capped = n_wave + n_long;
+    st->rows_long = n_long;
+    st->ms_total = res->info.ms_total;
+    st->launches = launches;
+    st->readbacks = readbacks;
+    if (ctx->env.verbose)
+        fprintf(stderr, "[osp] select_k order=%d k=%u M=%llu nnz %llu -> %llu capped=%llu long=%llu launches=%u readbacks=%u %.3f ms\n", sk.order, k,
+                (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)nnz, (unsigned long long)(n_wave + n_long),
+                (unsigned long long)n_long, launches, readbacks, st->ms_total);
+}

@@ -20,7 +20,9 @@ and a greedy weighted matching on mxv with the winner's column ``osp_csr_mxv_arg
 (``bfs_parents``): the first traversal here that never forms the part of a product it would throw away, and matrices put
 together from results with the assignment into a region ``osp_csr_assign`` (``bipartite_adjacency``, ``disjoint_union``,
 ``replace_subgraph``), and product graphs and Kronecker powers on the Kronecker product of two results ``osp_csr_kron``
-(``tensor_product``, ``cartesian_product``, ``strong_product``, ``kronecker_power``, at the end).
+(``tensor_product``, ``cartesian_product``, ``strong_product``, ``kronecker_power``), and neighbour sampling, k-nearest-neighbour
+graphs and uniform random walks on the row-wise k-select ``osp_csr_select_k`` (``sample_neighbors``, ``knn_graph``,
+``random_walks``, at the end).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -2146,5 +2148,161 @@ def kronecker_power(rows, cols, n, k, *, directed=False, loops=True, dtype=np.fl
         if out is not None and out is not A:
             out.close()
         raise
+    finally:
+        _close_all(device, [A])
+
+
+# ---- the row-wise k-select (osp_csr_select_k): neighbour sampling, kNN graphs, random walks ----------------------------------------
+def _check_seed(seed):
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError("seed must be an integer in [0, 2^64)")
+    return int(seed)
+
+
+def _vertex_list(vertices, n, what):
+    """A list of vertex ids in [0, n), repeats allowed, as an int64 numpy array."""
+    a = np.asarray(vertices.cpu() if torch.is_tensor(vertices) else vertices)
+    if a.size and a.dtype.kind not in "iu":
+        raise ValueError(f"{what} must be integers")
+    vs = np.atleast_1d(a).astype(np.int64).ravel()
+    if vs.size and (vs.min() < 0 or vs.max() >= n):
+        raise ValueError(f"{what} must lie in [0, {n})")
+    return vs
+
+
+def _rows_of(A, vertices, device):
+    """``A.extract(rows=vertices)`` of an int64 tensor on the device: row i of the result is row ``vertices[i]`` of A."""
+    v32 = vertices.to(torch.int32).contiguous()
+    torch.cuda.synchronize(device)   # the library works on its own stream
+    return A.extract(rows=v32)[0]
+
+
+def sample_neighbors(rows, cols, n, seeds, fanouts, *, seed=0, directed=False, ctx=None):
+    """GraphSAGE's neighbour sampling on the graph with edges (rows[e], cols[e]) on vertices [0, n) (``directed=False``: a
+    simple graph, self loops dropped; ``directed=True``: the out-neighbours, self loops kept): ``len(fanouts)`` hops from
+    ``seeds``.  Per hop h, with ``frontier`` the vertex list so far (hop 0: ``seeds``):
+
+    1. ``F = A.extract(rows=frontier)`` -- one row per listed vertex, columns in the graph's numbering;
+    2. ``B_h = F.select_k(fanouts[h], "random", seed=seed + h)`` -- at most ``fanouts[h]`` uniformly chosen neighbours of each;
+    3. the next frontier is the current one followed by the columns of ``B_h`` it does not hold yet, ascending
+       (``reduce("cols", "count")`` and torch on the device; only this list comes to the host).
+
+    The random key hashes the FRONTIER-LOCAL row number, not the vertex: a vertex listed twice in ``seeds`` gets two
+    independent samples, and the same vertex in another position or hop another one.  For fixed arguments the result is
+    the same on every run.
+
+    Returns (blocks, frontiers, info): ``blocks[h]`` is ``B_h``, a ``len(frontiers[h]) x n`` CsrResult with unit float32
+    values, which the caller closes; ``frontiers`` has ``len(fanouts) + 1`` int64 arrays; info = nnz (per hop), launches
+    (the k-selects' kernels), rows_capped (per hop) and ms_total (the k-selects')."""
+    seed = _check_seed(seed)
+    fanouts = [int(f) for f in fanouts]
+    if any(f < 1 or f > 0xffffffff for f in fanouts):
+        raise ValueError("every fanout must lie in [1, 2^32 - 1]")
+    ctx, device, dtype = _setup(np.float32, ctx)
+    A = adjacency_matrix(rows, cols, n, directed=directed, loops=directed, dtype=dtype, ctx=ctx)
+    blocks = []
+    try:
+        n = A.shape[0]
+        first = _vertex_list(seeds, n, "seeds")
+        frontier = torch.as_tensor(first, device=device)
+        frontiers = [first]
+        seen = torch.zeros(n, dtype=torch.bool, device=device)
+        seen[frontier] = True
+        count = torch.empty(max(n, 1), dtype=_torch_dtype(dtype), device=device)
+        info = {"nnz": [], "launches": 0, "rows_capped": [], "ms_total": 0.0}
+        for h, fanout in enumerate(fanouts):
+            F = _rows_of(A, frontier, device)
+            try:
+                B, st = F.select_k(fanout, "random", seed=(seed + h) % (1 << 64))
+            finally:
+                F.close()
+            blocks.append(B)
+            info["nnz"].append(B.nnz)
+            info["rows_capped"].append(st["rows_capped"])
+            info["launches"] += st["launches"]
+            info["ms_total"] += st["ms_total"]
+            B.reduce("cols", "count", out=count[:n])
+            new = ((count[:n] > 0) & ~seen).nonzero().flatten()
+            seen[new] = True
+            frontier = torch.cat([frontier, new])
+            frontiers.append(frontier.cpu().numpy())
+        return blocks, frontiers, info
+    except BaseException:
+        _close_all(device, blocks)
+        raise
+    finally:
+        _close_all(device, [A])
+
+
+def knn_graph(rows, cols, n, weights, k, *, largest=True, symmetric="union", dtype=np.float64, ctx=None):
+    """The k-nearest-neighbour sparsification of the weighted UNDIRECTED graph with edges (rows[e], cols[e]) on vertices
+    [0, n) (self loops dropped; of parallel edges the strongest counts: the largest weight with ``largest``, else the
+    smallest): ONE ``select_k(k, "largest" | "smallest")`` on the weighted adjacency S keeps every vertex's k strongest
+    edges (ties to the lower neighbour id; a NaN weight ranks after every number), then
+
+    * ``symmetric="union"``:  ``S.union(S^T, "max")`` (``"min"`` for smallest) -- an edge stays when EITHER end lists it;
+    * ``symmetric="mutual"``: ``S.intersect(S^T, "first")`` -- when BOTH ends list it;
+    * ``symmetric=None``:     S itself, the directed graph u -> (its k strongest neighbours).
+
+    Returns (result, info): the n x n CsrResult, which the caller closes; info = the k-select's stats, n and nnz (of the
+    result)."""
+    if symmetric not in ("union", "mutual", None):
+        raise ValueError('symmetric must be "union", "mutual" or None')
+    k = int(k)
+    if not 1 <= k <= 0xffffffff:
+        raise ValueError("k must lie in [1, 2^32 - 1]")
+    if weights is None:
+        raise ValueError("knn_graph needs weights")
+    ctx, device, dtype = _setup(dtype, ctx)
+    W = S = T = None
+    try:
+        W = adjacency_matrix(rows, cols, n, weights, dup="max" if largest else "min", dtype=dtype, ctx=ctx)
+        S, st = W.select_k(k, "largest" if largest else "smallest")
+        if symmetric is None:
+            out, S = S, None
+        else:
+            T, _ = S.transpose()
+            out = S.union(T, "max" if largest else "min")[0] if symmetric == "union" else S.intersect(T, "first")[0]
+        return out, dict(st, n=out.shape[0], nnz=out.nnz)
+    finally:
+        _close_all(device, [W, S, T])
+
+
+def random_walks(rows, cols, n, starts, length, *, seed=0, directed=False, ctx=None):
+    """Uniform random walks of ``length`` steps from every vertex of ``starts`` (repeats allowed) on the graph with edges
+    (rows[e], cols[e]) on vertices [0, n) (``directed`` as in ``sample_neighbors``).  One step moves every walker at once:
+    ``A.extract(rows=current).select_k(1, "random", seed=seed + step)`` -- row w of the extract is walker w's vertex, and
+    the one entry the select keeps is a uniformly chosen neighbour.  The key hashes the walker's number, so two walkers on
+    one vertex move independently.  A walker on a vertex without neighbours stays there, and from that step on its entries
+    are -1.
+
+    Returns an int64 array ``(len(starts), length + 1)``: column 0 is ``starts``, column t the walkers' vertices after t
+    steps (or -1)."""
+    seed = _check_seed(seed)
+    length = int(length)
+    if length < 0:
+        raise ValueError("length must be at least 0")
+    ctx, device, dtype = _setup(np.float32, ctx)
+    A = adjacency_matrix(rows, cols, n, directed=directed, loops=directed, dtype=dtype, ctx=ctx)
+    try:
+        current = _vertex_list(starts, A.shape[0], "starts").copy()
+        walks = np.full((current.size, length + 1), -1, np.int64)
+        walks[:, 0] = current
+        alive = np.ones(current.size, bool)
+        for step in range(length):
+            F = _rows_of(A, torch.as_tensor(current, device=device), device)
+            try:
+                B, _ = F.select_k(1, "random", seed=(seed + step) % (1 << 64))
+            finally:
+                F.close()
+            try:
+                rowptr, colidx, _ = B.to_host()
+            finally:
+                B.close()
+            moved = np.diff(rowptr) == 1
+            alive &= moved
+            current[moved] = colidx.astype(np.int64)
+            walks[alive, step + 1] = current[alive]
+        return walks
     finally:
         _close_all(device, [A])

@@ -342,6 +342,24 @@ class CsrResult:
         self._same_family(other)
         return _call(self._ctx, "osp_csr_kron", self._h, other._h, C.byref(kr), stats=_lib.KronStats())
 
+    def select_k(self, k, order="largest", *, seed=0):
+        """Of every row of this CSR the ``k`` entries that rank first under ``order``, as a new CSR result on the device
+        (``osp_csr_select_k``): a row of at most ``k`` entries is kept whole.  ``order`` ``"largest"`` / ``"smallest"``: by
+        value under IEEE comparison, -0.0 equal to +0.0, every NaN after every number, ties to the lower column (the tie
+        rule of ``inflate_prune``'s ``max_per_row``).  ``"random"``: by a 64-bit hash of (``seed``, row, column) -- values are
+        not read, no two entries tie, and a row's choice depends on the seed, the row's number and its columns alone; over
+        seeds every k-subset of a row is equally likely.  Kept entries keep their value bits and columns stay ascending.
+        Selecting with ``k`` and then with ``k2 <= k`` (same order and seed) equals selecting with ``k2``.  ``k`` is an int
+        in [1, 2^32 - 1], ``seed`` an int in [0, 2^64): anything else is a ValueError.  Returns (result, stats dict):
+        nnz_in, nnz_out, rows_capped, rows_long, ms_total, launches, readbacks."""
+        sk = _lib.SelectK()
+        sk.order = _enum(_lib.SELECT_K_ORDERS, order, "order")
+        for name, v, lo, hi in (("k", k, 1, 0xffffffff), ("seed", seed, 0, 0xffffffffffffffff)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise ValueError(f"{name} must be an integer in [{lo}, {hi}] (got {v!r})")
+        sk.k, sk.seed = int(k), int(seed)
+        return _call(self._ctx, "osp_csr_select_k", self._h, C.byref(sk), stats=_lib.SelectKStats())
+
     def transpose(self):
         """This CSR (M x N) transposed as a new N x M CSR result on the device (``osp_csr_transpose``): entry (j, i) exists
         iff this result has (i, j), columns ascend in every row, values keep their bits, and transposing twice gives the same
