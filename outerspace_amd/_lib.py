@@ -276,6 +276,34 @@ class SelectKStats(_Stats):
 # capped rows of a k-select longer than this are selected by a workgroup, shorter ones by one wave (kSelectKLongMin, osp_select_k.h)
 SELECT_K_LONG_MIN = 2048
 
+SCAN_OPS = {"plus": 0, "min": 1, "max": 2}  # the osp_reduce_op_t values osp_csr_scan takes
+SCAN_BLOCK = 32        # OSP_SCAN_BLOCK: entries of one block of the scan order
+SCAN_CHAIN_LANE = 16   # rows of more blocks than this are chained by a whole wave (kScanChainLane, osp_scan.h)
+SCAN_LOCAL_TILE = 128  # blocks of one workgroup of the scan's local pass (kScanLocalThreads, osp_scan.h)
+
+
+class Scan(_Stats):
+    """osp_scan_t"""
+    _fields_ = [("op", C.c_int32), ("reserved", C.c_uint32 * 8)]
+
+
+class ScanStats(_Stats):
+    """osp_scan_stats_t"""
+    _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("blocks", C.c_uint64), ("ms_total", C.c_float),
+                ("launches", C.c_uint32), ("readbacks", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+class Draw(_Stats):
+    """osp_draw_t"""
+    _fields_ = [("draws", C.c_uint32), ("reserved0", C.c_uint32), ("seed", C.c_uint64), ("reserved", C.c_uint32 * 8)]
+
+
+class DrawStats(_Stats):
+    """osp_draw_stats_t"""
+    _fields_ = [("nnz_in", C.c_uint64), ("nnz_out", C.c_uint64), ("rows_without", C.c_uint64), ("ms_total", C.c_float),
+                ("launches", C.c_uint32), ("readbacks", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
 PANEL_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Panel), C.c_void_p)
 
 MULTI_MAX_RANKS = 16
@@ -370,6 +398,9 @@ KRON_EXPORTS = ("osp_csr_kron",)
 
 # every symbol include/outerspace_spgemm_select_k.h declares
 SELECT_K_EXPORTS = ("osp_csr_select_k",)
+
+# every symbol include/outerspace_spgemm_scan.h declares
+SCAN_EXPORTS = ("osp_csr_scan", "osp_csr_draw")
 
 _lib = None
 
@@ -467,6 +498,8 @@ def lib():
     L.osp_csr_assign.argtypes = [vp, vp, C.POINTER(Assign), C.POINTER(vp), C.POINTER(AssignStats)]
     L.osp_csr_kron.argtypes = [vp, vp, C.POINTER(Kron), C.POINTER(vp), C.POINTER(KronStats)]
     L.osp_csr_select_k.argtypes = [vp, C.POINTER(SelectK), C.POINTER(vp), C.POINTER(SelectKStats)]
+    L.osp_csr_scan.argtypes = [vp, C.POINTER(Scan), C.POINTER(vp), C.POINTER(ScanStats)]
+    L.osp_csr_draw.argtypes = [vp, C.POINTER(Draw), vp, vp, i32, C.POINTER(DrawStats)]
     _lib = L
     return L
 

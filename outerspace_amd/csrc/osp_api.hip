@@ -40,6 +40,7 @@
 #include "../../include/outerspace_spgemm_assign.h"
 #include "../../include/outerspace_spgemm_kron.h"
 #include "../../include/outerspace_spgemm_select_k.h"
+#include "../../include/outerspace_spgemm_scan.h"
 #include "osp_internal.h"
 #include "osp_paths.h"
 #include "osp_kernels.h"
@@ -64,6 +65,7 @@
 #include "osp_assign.h"
 #include "osp_kron.h"
 #include "osp_select_k.h"
+#include "osp_scan.h"
 
 namespace osp {
 
@@ -1111,6 +1113,33 @@ int osp_csr_select_k(osp_result_t in_, const osp_select_k_t *sk, osp_result_t *o
         if (sk->k == 0) throw Error(OSP_ERR_ARG, "select_k: k must be at least 1");
         check_reserved(sk->reserved, "select_k");
     }, [&](auto tag, Result *res, osp_select_k_stats_t *st) { select_k_impl<decltype(tag)>(in->ctx, in, res, *sk, st); });
+}
+
+// (the kernels take a thread per block, per row and per entry chunk: see kThreadEachMax)
+static void check_scan_size(const Result *in, const char *op) {
+    if (in->info.nnz_c / kScanBlock + in->info.M > kThreadEachMax)
+        throw Error(OSP_ERR_ARG, std::string(op) + ": nnz / 32 + M must be at most 2^32 - 256");
+}
+
+int osp_csr_scan(osp_result_t in_, const osp_scan_t *sc, osp_result_t *out, osp_scan_stats_t *stats) {
+    Result *in = (Result *)in_;
+    return csr_op({in}, sc != nullptr, out, stats, [&] {
+        if (sc->op != OSP_REDUCE_PLUS && sc->op != OSP_REDUCE_MIN && sc->op != OSP_REDUCE_MAX) throw Error(OSP_ERR_ARG, "scan: op is not one of PLUS, MIN, MAX");
+        check_reserved(sc->reserved, "scan");
+        check_scan_size(in, "scan");
+    }, [&](auto tag, Result *res, osp_scan_stats_t *st) { scan_impl<decltype(tag)>(in->ctx, in, res, *sc, st); });
+}
+
+int osp_csr_draw(osp_result_t in_, const osp_draw_t *dr, int64_t *cols, int64_t *pos, osp_memspace_t space, osp_draw_stats_t *stats) {
+    Result *in = (Result *)in_;
+    return csr_vector_op(in, dr && cols, stats, [&] {
+        check_space(space);
+        if (dr->draws == 0) throw Error(OSP_ERR_ARG, "draw: draws must be at least 1");
+        if (in->info.M * (uint64_t)dr->draws > (1ull << 40)) throw Error(OSP_ERR_ARG, "draw: M * draws must be at most 2^40");
+        if (dr->reserved0) throw Error(OSP_ERR_ARG, "draw: reserved words must be 0");
+        check_reserved(dr->reserved, "draw");
+        check_scan_size(in, "draw");
+    }, [&](auto tag, osp_draw_stats_t *st) { draw_impl<decltype(tag)>(in->ctx, in, *dr, cols, pos, space, stats != nullptr, st); });
 }
 
 int osp_csr_build(osp_context_t ctx_, const osp_build_t *b, osp_result_t *out, osp_build_stats_t *stats) {

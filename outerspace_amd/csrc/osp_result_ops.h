@@ -1,5 +1,5 @@
 // osp_result_ops.h -- the host side of the operations on results: what they share (the frame of a call, the two-pass and
-// bit-compaction helpers) and every *_impl from bias_relu to kron, the conv stage and the masked product between them.  Part of
+// bit-compaction helpers) and every *_impl from bias_relu to draw, the conv stage and the masked product between them.  Part of
 // the ONE translation unit osp_api.hip (included there, inside namespace osp, after osp_pipeline.h and the ingest); the kernels
 // are in the headers the sections name.  DESIGN.md sections 8-20.
 #pragma once
@@ -1949,4 +1949,106 @@ static void select_k_impl(Context *ctx, const Result *in, Result *res, const osp
         fprintf(stderr, "[osp] select_k order=%d k=%u M=%llu nnz %llu -> %llu capped=%llu long=%llu launches=%u readbacks=%u %.3f ms\n", sk.order, k,
                 (unsigned long long)M, (unsigned long long)nnz_in, (unsigned long long)nnz, (unsigned long long)(n_wave + n_long),
                 (unsigned long long)n_long, launches, readbacks, st->ms_total);
+}
+
+// ---- the row-wise scan of a CSR result and the weighted draws from its rows (osp_scan.h) ----
+// The four steps of osp_scan.h over `in`'s rows: the entries of `src` scanned under OP into vals (nnz > 0 values, M > 0).
+// Returns the kernels it launched; reads nothing back.
+template <class T, int OP, class Src>
+static uint32_t scan_rows(Scratch &sc, hipStream_t s, const Result *in, Src src, T *vals) {
+    const uint64_t M = in->info.M, N = in->info.N, nnz = in->info.nnz_c;
+    const uint64_t bound = nnz / kScanBlock + M;   // sum ceil(m_i / 32) <= this; the exact number stays on the device
+    uint64_t *blkptr = sc.get<uint64_t>(M + 1);
+    uint64_t *tmp = sc.get<uint64_t>(scan_scratch_entries(M));
+    uint32_t launches = device_exclusive_scan<LoadRowBlocks, uint64_t>(LoadRowBlocks{in->rowptr}, M, blkptr, tmp, s);
+    T *totals = sc.get<T>(bound);
+    scan_local_kernel<T, OP, Src><<<grid_for(bound, kScanLocalThreads), kScanLocalThreads, 0, s>>>(in->rowptr, blkptr, M, src, vals, totals);
+    launches++;
+    if (std::min(N, nnz) > kScanBlock) {   // (else no row has a second block: columns are distinct)
+        T *carry = sc.get<T>(bound);
+        scan_chain_kernel<T, OP><<<grid_for(M, 256), 256, 0, s>>>(blkptr, M, totals, carry);
+        scan_add_kernel<T, OP><<<grid_for(nnz, (unsigned)kCompactChunk), kCompactThreads, 0, s>>>(in->rowptr, blkptr, M, nnz, carry, vals);
+        launches += 2;
+    }
+    return launches;
+}
+
+template <class T>
+static void scan_impl(Context *ctx, const Result *in, Result *res, const osp_scan_t &scn, osp_scan_stats_t *st) {
+    OpFrame fr(ctx);
+    hipStream_t s = fr.s;
+    Scratch &sc = fr.sc;
+    const uint64_t M = in->info.M, nnz = in->info.nnz_c;
+    res->info = in->info;
+    uint32_t launches = 0;
+    if (M == 0 || nnz == 0) {
+        empty_result<T>(res, M, s);
+    } else {
+        alloc_rowptr(res, M);
+        OSP_HIP(hipMemcpyAsync(res->rowptr, in->rowptr, (M + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        alloc_entries<T>(res, nnz);
+        OSP_HIP(hipMemcpyAsync(res->colidx, in->colidx, nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        const Values<T> src{(T *)in->vals};   // (read only)
+        T *out = (T *)res->vals;
+        if (scn.op == OSP_REDUCE_PLUS) launches = scan_rows<T, RED_PLUS>(sc, s, in, src, out);
+        else if (scn.op == OSP_REDUCE_MIN) launches = scan_rows<T, RED_MIN>(sc, s, in, src, out);
+        else launches = scan_rows<T, RED_MAX>(sc, s, in, src, out);
+    }
+    fr.finish(res, nnz);
+    *st = osp_scan_stats_t{};
+    st->nnz_in = st->nnz_out = nnz;
+    st->blocks = nnz / kScanBlock + M;
+    st->ms_total = res->info.ms_total;
+    st->launches = launches;
+    st->readbacks = 0;
+    if (ctx->env.verbose)
+        fprintf(stderr, "[osp] scan op=%d M=%llu nnz=%llu blocks<=%llu launches=%u %.3f ms\n", scn.op, (unsigned long long)M, (unsigned long long)nnz,
+                (unsigned long long)st->blocks, launches, st->ms_total);
+}
+
+// want_stats: the caller asked for stats, and rows_without is worth its kernel and its read-back
+template <class T>
+static void draw_impl(Context *ctx, const Result *in, const osp_draw_t &dr, int64_t *cols_out, int64_t *pos_out, osp_memspace_t space, bool want_stats,
+                      osp_draw_stats_t *st) {
+    OpFrame fr(ctx);
+    hipStream_t s = fr.s;
+    Scratch &sc = fr.sc;
+    const uint64_t M = in->info.M, nnz = in->info.nnz_c, total = M * dr.draws;
+    const bool ran = M && nnz;
+    uint64_t rows_without = M;
+    uint32_t launches = 0, readbacks = 0;
+    // (both arrays are formed in pool buffers and copied out last: a call that fails leaves cols and pos as they were.  pos is
+    // neither allocated nor written when the caller does not want it: a template parameter of the kernel)
+    int64_t *cols = sc.get<int64_t>(total), *pos = pos_out ? sc.get<int64_t>(total) : nullptr;
+    if (ran) {
+        T *cdf = sc.get<T>(nnz);
+        launches = scan_rows<T, RED_PLUS>(sc, s, in, Weights<T>{(const T *)in->vals}, cdf);
+        const uint64_t s0 = select_k_mix(dr.seed + 0x9E3779B97F4A7C15ull);
+        const unsigned grid = (unsigned)std::min<uint64_t>((total + 255) / 256, kDrawBlocks);   // (in 64 bits: total may be 2^40)
+        if (pos) draw_kernel<T, true><<<grid, 256, 0, s>>>(in->rowptr, in->colidx, cdf, total, dr.draws, s0, cols, pos);
+        else draw_kernel<T, false><<<grid, 256, 0, s>>>(in->rowptr, in->colidx, cdf, total, dr.draws, s0, cols, pos);
+        launches++;
+        if (want_stats) {
+            unsigned long long *without = (unsigned long long *)sc.get<uint64_t>(1);
+            zero_async(s, {{without, sizeof(uint64_t)}});
+            draw_without_kernel<<<(unsigned)std::min<uint64_t>(grid_for(M, 256), 256), 256, 0, s>>>(cols, M, dr.draws, without);
+            launches += 2;
+            rows_without = d2h((const uint64_t *)without, s);
+            readbacks++;
+        }
+    }
+    const float ms = fr.stop();
+    finish_dense(s, cols, cols_out, total, space, !ran, (int64_t)-1);
+    finish_dense(s, pos, pos_out, total, space, !ran, (int64_t)-1);
+    if (total) OSP_HIP(hipStreamSynchronize(s));
+    *st = osp_draw_stats_t{};
+    st->nnz_in = nnz;
+    st->nnz_out = total;
+    st->rows_without = rows_without;
+    st->ms_total = ms;
+    st->launches = launches;
+    st->readbacks = readbacks;
+    if (ctx->env.verbose)
+        fprintf(stderr, "[osp] draw draws=%u M=%llu nnz=%llu without=%llu launches=%u readbacks=%u %.3f ms\n", dr.draws, (unsigned long long)M,
+                (unsigned long long)nnz, (unsigned long long)rows_without, launches, readbacks, st->ms_total);
 }

@@ -22,7 +22,8 @@ together from results with the assignment into a region ``osp_csr_assign`` (``bi
 ``replace_subgraph``), and product graphs and Kronecker powers on the Kronecker product of two results ``osp_csr_kron``
 (``tensor_product``, ``cartesian_product``, ``strong_product``, ``kronecker_power``), and neighbour sampling, k-nearest-neighbour
 graphs and uniform random walks on the row-wise k-select ``osp_csr_select_k`` (``sample_neighbors``, ``knn_graph``,
-``random_walks``, at the end).
+``random_walks``), and their weighted counterparts on the weighted draws ``osp_csr_draw`` (``weighted_random_walks``,
+``weighted_sample_neighbors``, at the end).
 
 ``triangle_count`` is ``sum((L @ L.T) * L)`` for the adjacency L of the graph with every edge oriented from its
 lower-ranked end to its higher-ranked end, vertices ranked by (degree, id).  A vertex's out-neighbours then have at least
@@ -2304,5 +2305,108 @@ def random_walks(rows, cols, n, starts, length, *, seed=0, directed=False, ctx=N
             current[moved] = colidx.astype(np.int64)
             walks[alive, step + 1] = current[alive]
         return walks
+    finally:
+        _close_all(device, [A])
+
+
+# ---- the row-wise scan and the weighted draws (osp_csr_scan, osp_csr_draw): weighted walks and weighted neighbour sampling ----------
+def weighted_random_walks(rows, cols, n, weights, starts, length, *, seed=0, directed=False, dtype=np.float64, ctx=None):
+    """Random walks of ``length`` steps from every vertex of ``starts`` (repeats allowed) on the WEIGHTED graph with edges
+    (rows[e], cols[e], weights[e]) on vertices [0, n): a step goes to a neighbour with probability (the edge's weight) /
+    (the sum of the vertex's weights).  ``directed`` as in ``sample_neighbors``; parallel edges ADD (the adjacency is built
+    with ``dup="plus"``, in list order); an edge whose weight is not positive and finite is never taken.  One step moves
+    every walker at once: ``A.extract(rows=current).draw(1, seed=seed + step)`` -- row w of the extract is walker w's
+    vertex, and the draw hashes the walker's number, so two walkers on one vertex move independently.  Only the walkers'
+    vector moves between steps; no CSR comes to the host.  A walker on a vertex it cannot leave (no neighbour, or no positive
+    finite weight) stays there, and from that step on its entries are -1, as in ``random_walks``.
+
+    Returns an int64 array ``(len(starts), length + 1)``: column 0 is ``starts``, column t the walkers' vertices after t
+    steps (or -1)."""
+    seed = _check_seed(seed)
+    length = int(length)
+    if length < 0:
+        raise ValueError("length must be at least 0")
+    if weights is None:
+        raise ValueError("weighted_random_walks needs weights")
+    ctx, device, dtype = _setup(dtype, ctx)
+    A = adjacency_matrix(rows, cols, n, weights, directed=directed, loops=directed, dup="plus", dtype=dtype, ctx=ctx)
+    try:
+        current = torch.as_tensor(_vertex_list(starts, A.shape[0], "starts"), device=device)
+        walks = torch.full((current.numel(), length + 1), -1, dtype=torch.int64, device=device)
+        walks[:, 0] = current
+        alive = torch.ones(current.numel(), dtype=torch.bool, device=device)
+        for step in range(length):
+            F = _rows_of(A, current, device)
+            try:
+                picked, _ = F.draw(1, seed=(seed + step) % (1 << 64))
+            finally:
+                F.close()
+            picked = picked[:, 0]
+            moved = picked >= 0
+            alive &= moved
+            current = torch.where(moved, picked, current)
+            walks[:, step + 1] = torch.where(alive, current, torch.full_like(current, -1))
+        return walks.cpu().numpy()
+    finally:
+        _close_all(device, [A])
+
+
+def weighted_sample_neighbors(rows, cols, n, weights, seeds, fanouts, *, seed=0, directed=False, dtype=np.float64, ctx=None):
+    """Neighbour sampling in proportion to edge weights, with replacement, on the graph of ``weighted_random_walks``
+    (parallel edges add): ``len(fanouts)`` hops from ``seeds``.  Per hop h, with ``frontier`` the vertex list so far:
+
+    1. ``F = A.extract(rows=frontier)``;
+    2. ``F.draw(fanouts[h], seed=seed + h)`` -- ``fanouts[h]`` draws per frontier vertex;
+    3. the (frontier-local row, column) pairs that are not -1 go through ONE ``Context.build(dup="count")``: ``B_h``'s
+       values are the MULTIPLICITIES of the draws (the numerator of the importance-sampling estimator), and every row that
+       can be drawn from sums to ``fanouts[h]``;
+    4. the next frontier is formed as ``sample_neighbors`` forms it: the current one followed by the columns of ``B_h`` it
+       does not hold yet, ascending.
+
+    The draw hashes the FRONTIER-LOCAL row number, as ``sample_neighbors`` does.  Returns (blocks, frontiers, info):
+    ``blocks[h]`` is a ``len(frontiers[h]) x n`` CsrResult, which the caller closes; ``frontiers`` has ``len(fanouts) + 1``
+    int64 arrays; info = nnz (per hop), rows_without (per hop), launches (the draws' kernels) and ms_total (the draws')."""
+    seed = _check_seed(seed)
+    fanouts = [int(f) for f in fanouts]
+    if any(f < 1 or f > 0xffffffff for f in fanouts):
+        raise ValueError("every fanout must lie in [1, 2^32 - 1]")
+    if weights is None:
+        raise ValueError("weighted_sample_neighbors needs weights")
+    ctx, device, dtype = _setup(dtype, ctx)
+    A = adjacency_matrix(rows, cols, n, weights, directed=directed, loops=directed, dup="plus", dtype=dtype, ctx=ctx)
+    blocks = []
+    try:
+        n = A.shape[0]
+        first = _vertex_list(seeds, n, "seeds")
+        frontier = torch.as_tensor(first, device=device)
+        frontiers = [first]
+        seen = torch.zeros(n, dtype=torch.bool, device=device)
+        seen[frontier] = True
+        count = torch.empty(max(n, 1), dtype=_torch_dtype(dtype), device=device)
+        info = {"nnz": [], "rows_without": [], "launches": 0, "ms_total": 0.0}
+        for h, fanout in enumerate(fanouts):
+            F = _rows_of(A, frontier, device)
+            try:
+                picked, st = F.draw(fanout, seed=(seed + h) % (1 << 64))
+            finally:
+                F.close()
+            local = torch.arange(frontier.numel(), device=device).repeat_interleave(fanout)
+            picked = picked.flatten()
+            keep = picked >= 0
+            B = _build_device(ctx, device, frontier.numel(), n, local[keep], picked[keep], None, "count", dtype)
+            blocks.append(B)
+            info["nnz"].append(B.nnz)
+            info["rows_without"].append(st["rows_without"])
+            info["launches"] += st["launches"]
+            info["ms_total"] += st["ms_total"]
+            B.reduce("cols", "count", out=count[:n])
+            new = ((count[:n] > 0) & ~seen).nonzero().flatten()
+            seen[new] = True
+            frontier = torch.cat([frontier, new])
+            frontiers.append(frontier.cpu().numpy())
+        return blocks, frontiers, info
+    except BaseException:
+        _close_all(device, blocks)
+        raise
     finally:
         _close_all(device, [A])

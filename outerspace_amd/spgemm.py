@@ -360,6 +360,50 @@ class CsrResult:
         sk.k, sk.seed = int(k), int(seed)
         return _call(self._ctx, "osp_csr_select_k", self._h, C.byref(sk), stats=_lib.SelectKStats())
 
+    def scan(self, op="plus"):
+        """The inclusive scan of every row of this CSR under ``op`` (``"plus"``, ``"min"``, ``"max"``: a running sum,
+        minimum or maximum along ascending columns), as a new CSR result with this pattern on the device
+        (``osp_csr_scan``).  The order is defined to the bit: a row is cut into blocks of 32 entries, scanned
+        sequentially inside (from ``reduce``'s identity), the blocks' totals are scanned sequentially across the row, and an
+        entry's value is (carry into its block) ``op`` (its local scan).  A row of at most 32 entries is ``numpy.cumsum``
+        in the dtype, except that a leading -0.0 reads +0.0; min and max never take a NaN (the identity until a number
+        arrives); plus propagates one to the end of its row; on non-negative input the running sum never decreases, and a
+        zero entry beyond the first repeats the value before it bit for bit.  A row's scan depends on its values alone.
+        Nothing is read back.  Returns (result, stats dict): nnz_in, nnz_out, blocks (nnz // 32 + M: the bound the
+        kernels are launched for), ms_total, launches, readbacks (0)."""
+        sc = _lib.Scan()
+        sc.op = _enum(_lib.SCAN_OPS, op, "op")
+        return _call(self._ctx, "osp_csr_scan", self._h, C.byref(sc), stats=_lib.ScanStats())
+
+    def draw(self, draws=1, *, seed=0, out=None, out_pos=None, positions=False, space="device"):
+        """``draws`` weighted draws from every row of this CSR, with replacement (``osp_csr_draw``): row i's draw d picks an
+        entry with probability (its weight) / (the row's total weight) and returns its column; an entry's weight is its
+        value where that is positive and finite, and 0 otherwise (zeros, negatives, NaNs and infinities are never drawn).
+        The CDF is ``scan("plus")`` of the weights to the bit, the random number a 64-bit hash of (``seed``, i, d) -- the
+        draw is the first entry whose running sum exceeds (hash as a fraction in [0, 1)) * total -- so for a fixed seed a
+        row's draws depend on the row's number and values alone.  A row that is empty, has no positive finite weight or whose
+        total overflows gives -1.  ``draws`` is an int in [1, 2^32 - 1], ``seed`` an int in [0, 2^64): anything else is a
+        ValueError.  ``out`` / ``out_pos``: None, or (M, draws) int64 values to fill -- a device address or torch tensor, a
+        numpy array with ``space="host"``; ``positions=True`` (or an ``out_pos``) also returns every picked entry's index in
+        this result's arrays.  Returns (cols, stats dict) or (cols, pos, stats dict): torch int64 tensors (M, draws) on
+        the context's device, or numpy arrays (``space="host"``).  Stats: nnz_in, nnz_out (M * draws), rows_without,
+        ms_total, launches, readbacks (1: rows_without)."""
+        for name, v, lo, hi in (("draws", draws, 1, 0xffffffff), ("seed", seed, 0, 0xffffffffffffffff)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise ValueError(f"{name} must be an integer in [{lo}, {hi}] (got {v!r})")
+        sp = _space(space)
+        dr = _lib.Draw()
+        dr.draws, dr.seed = int(draws), int(seed)
+        M = self.shape[0]
+        if M * int(draws) > 1 << 40:
+            raise OspError(_lib.ERR_ARG, "M * draws must be at most 2^40")
+        positions = positions or out_pos is not None
+        cp, cbuf, cret = self._out_arg(out, (M, int(draws)), space, np.int64, "out")
+        pp, pbuf, pret = self._out_arg(out_pos, (M, int(draws)), space, np.int64, "out_pos") if positions else (None, None, None)
+        stats = _lib.DrawStats()
+        _lib.check(_lib.lib().osp_csr_draw(self._h, C.byref(dr), cp, pp, sp, C.byref(stats)))   # (cbuf and pbuf live until here)
+        return (cret, pret, stats.as_dict()) if positions else (cret, stats.as_dict())
+
     def transpose(self):
         """This CSR (M x N) transposed as a new N x M CSR result on the device (``osp_csr_transpose``): entry (j, i) exists
         iff this result has (i, j), columns ascend in every row, values keep their bits, and transposing twice gives the same
@@ -390,7 +434,8 @@ class CsrResult:
 
     def _out_arg(self, out, shape, space, dtype=None, what="out"):
         """The output of ``mxv`` (``shape`` (M,)) and ``mxd`` ((M, k)), and with ``dtype=np.int64`` the positions of
-        ``mxv_arg``: (pointer, buffer the pointer points into, what the method returns).  ``out=None`` allocates -- numpy on
+        ``mxv_arg`` and the (M, draws) columns and positions of ``draw`` (the one 2-D output that is not floating point):
+        (pointer, buffer the pointer points into, what the method returns).  ``out=None`` allocates -- numpy on
         the host, torch on the context's device --, else ``out`` is checked and filled.  The pointer is never null."""
         size = math.prod(shape)
         dtype = self.dtype if dtype is None else dtype
@@ -411,7 +456,7 @@ class CsrResult:
             return C.c_void_p(buf.ctypes.data), buf, out
         if np.dtype(dtype) == np.int64 and hasattr(out, "is_floating_point") and out.is_floating_point():
             raise OspError(_lib.ERR_ARG, f"{what} must be a contiguous tensor of {size} values of int64")
-        ptr, buf = _dense_arg(out, shape, dtype, "device", what, floating=len(shape) == 2)
+        ptr, buf = _dense_arg(out, shape, dtype, "device", what, floating=len(shape) == 2 and np.dtype(dtype) != np.int64)
         return ptr, buf, out
 
     def reduce(self, axis, op, out=None):
